@@ -24,11 +24,20 @@ shared HRF dilation (50k voxels, 20 outer x 100 inner iterations + the closing z
 all-reduce of K^2+K+2 float64 per outer iteration), 5 = regularisation path (50k voxels x 20
 lambdas = 10^6 problems sharing each voxel's series).  One JSON line each, same blocks.
 
-Prints ONE JSON line (rank 0): metric = voxel-iterations/s (whole job), plus `roofline`
-(dominant kernel against the fp32 vector-ALU peak that binds it; the HBM-algorithmic figure
-of SURVEY.md 8d and the measured HBM traffic as context) and `cpu_baseline` (the reference's
-dense-Toeplitz NumPy formulation fanned over the host cores, and the matrix-free C/OpenMP
-port, both from oracle/, on bounded samples of the same workload).
+Prints ONE JSON line (rank 0): metric = voxel-iterations/s (whole job), `ms_per_step`, `dtype`
+and the configuration.  A plain run does only that: set-up, warm-up, the timed steps, the
+line.  `--full` adds everything else the benchmark measures or checks: `roofline` (dominant
+kernel timed on its own against the peak that binds it; the HBM-algorithmic figure of
+SURVEY.md 8d and the measured HBM traffic as context), `sustained`, the host-buffer and
+outputs-inclusive wall clocks, `--extras`, the weak-scaling leg and the `collective` record
+of N > 1, `parity` against the CPU oracle and `cpu_baseline` (the reference's dense-Toeplitz
+NumPy formulation fanned over the host cores, and the matrix-free C/OpenMP port, both from
+oracle/, on bounded samples of the same workload).
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of the timed path
+receives it, to DIR/<name>.npy (rank 0; float64): `diff_z` (a fixed, seeded sample of rows
+when the whole array exceeds DUMP_BYTES) and `n_done`; config 4: `diff_z`, `hrf`, `theta`
+and `cost`.  The inputs are seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import math
@@ -52,6 +61,7 @@ N_LAMBDA = 20                        # config 5: lambdas per voxel
 
 
 DENSE_RATIO = 0.19        # include/pybold_hip.h: PB_PATH_DENSE_RATIO
+DUMP_BYTES = 48 << 20     # --dump-outputs: float64 bytes kept of a 2-D output, an eighth of it of a 1-D one (all < 64 MB)
 
 
 def executed_flops_per_voxel_iter(n, k):
@@ -104,8 +114,16 @@ def parse():
     ap.add_argument("--voxels", type=int, default=None,
                     help="voxels of the whole job (strong scaling) / per GPU (--scaling weak); "
                          "default: the configuration's own count (10k / 100k / 50k / 50k)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (roofline, sustained "
+                         "rate, host-buffer and outputs-inclusive wall clocks, weak scaling, parity against the "
+                         "CPU oracle, cpu_baseline); off by default: a plain run sets up, warms up, times the "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy "
+                         "(see the module docstring)")
     ap.add_argument("--busy-seconds", type=float, default=6.0,
-                    help="N = 1: untimed back-to-back solves after the timed region (sustained rate; also "
+                    help="--full, N = 1: untimed back-to-back solves after the timed region (sustained rate; also "
                          "keeps the GPU visibly busy between the two CPU legs)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="N > 1: shard --voxels over the ranks (strong, default) or give every "
@@ -114,9 +132,9 @@ def parse():
     ap.add_argument("--iters", type=int, default=500)
     ap.add_argument("--lbda", type=float, default=1.0)
     ap.add_argument("--extras", action="store_true",
-                    help="also time BASELINE config 2 (10k voxels), the 12 500-voxel shard of "
+                    help="implies --full; also time BASELINE config 2 (10k voxels), the 12 500-voxel shard of "
                          "config 3 on 8 GPUs and the chunked (pipelined) host-buffer solve (extra "
-                         "launches; off by default so that a rocprof summary of the default command "
+                         "launches; off by default so that a rocprof summary of the full command "
                          "holds only the config-3 launches)")
     ap.add_argument("--kernel", choices=["auto", "seq", "fast1", "generic"], default="auto",
                     help="auto = library dispatch; seq = the same without the internal side "
@@ -125,14 +143,16 @@ def parse():
     ap.add_argument("--spin-seconds", type=float, default=0.25,
                     help="untimed busy time before the warm-up steps (GPU clock ramp)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="target time of each cpu_baseline sample (0 = skip)")
+                    help="--full: target time of each cpu_baseline sample (0 = skip)")
     ap.add_argument("--master-port", type=int, default=0, help="self-launched ranks only")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="development aid: all N ranks share GPU 0 and synchronise over gloo (RCCL "
                          "refuses two ranks on one device); rehearses launch, sharding, barrier and "
                          "MAX-reduction of the N > 1 path on a one-GPU box. The line is marked "
                          "\"rehearsal\": true and is not a measurement")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.full = args.full or args.extras
+    return args
 
 
 def job_layout(voxels, scaling, world, rank):
@@ -201,7 +221,8 @@ def run(args):
     # CPU legs first (rank 0, one GPU): their worker processes are started before this
     # process initialises the GPU
     cpu_dense = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    cpu_legs = args.full and rank == 0 and world == 1 and args.cpu_seconds > 0
+    if cpu_legs:
         cpu_dense = cpu_dense_baseline(args.scans, args.iters, args.lbda, args.cpu_seconds)
 
     import numpy as np
@@ -225,7 +246,7 @@ def run(args):
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
     red_dev = torch.device("cpu") if args.rehearse_on_one_gpu else dev
     collective = None
-    if dist is not None:
+    if dist is not None and args.full:
         # what the communicator saw: one all-gather of every rank's PCI address (every rank takes part), so that a
         # multi-GPU line shows RCCL ran over N DIFFERENT devices (a rehearsal on one GPU shows 1)
         pr = torch.cuda.get_device_properties(dev)
@@ -302,7 +323,7 @@ def run(args):
         out = run_config4(args, world, rank, dev, dist, V, V_total, lo, timed, timed_local, barrier)
         if collective:
             out["collective"] = collective
-        if rank == 0 and world == 1 and args.cpu_seconds > 0:
+        if cpu_legs:
             out["cpu_baseline"] = cpu_baseline_block(cpu_dense, None, args.iters)
         if dist is not None:
             dist.destroy_process_group()
@@ -343,83 +364,100 @@ def run(args):
 
     elapsed, kern_ms = timed(one_step, args.steps, args.warmup, args.spin_seconds)
     value = float(V_total) * y_rep * n_iter * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"diff_z": plan.W, "n_done": plan.n_done})
 
-    # One step = ONE pb_fista_solve call = up to two kernels (solver.launch_plan): the whole
-    # rounds of waves on the dominant kernel, the remainder on the cheapest form.  The
-    # dominant kernel is timed on its own here (same grid, same data, a few launches after
-    # the timed region, THIS RANK ONLY: no collective, ranks may differ in their plans) so that
-    # its duration can be set against its rocprofv3 average.
-    # (per-problem lambdas -- config 5's regularisation path, sparse solutions by construction -- stay
-    # on the vector forms: the library does not put them on the matrix pipe)
     plan_force = "valu" if torch.is_tensor(lam) else None
     n_main, main_kernel, tail_kernel = solver.launch_plan(N, K, max(P, 1), force=plan_force)
-    P_dom = n_main if (args.kernel in ("auto", "seq") and n_main > 0) else P
     matrix_pipe = args.kernel in ("auto", "seq") and "matrix pipe" in (main_kernel if n_main else tail_kernel)
-    split_form = matrix_pipe and "split over two" in (main_kernel if n_main else tail_kernel)
-    if matrix_pipe and "four waves" in (main_kernel if n_main else tail_kernel):
-        split_form = 4                                          # (641 .. 1 280 scans: one series over the four waves of a workgroup)
-    if P_dom != P and P_dom % y_rep == 0:
-        lam_dom = lam[:P_dom] if torch.is_tensor(lam) else lam
-        plan_dom = solver.FistaPlan(Y[:P_dom // y_rep], hrf, lam_dom, step, n_iter, y_rep=y_rep,
-                                    force=("mfma2" if split_form else "mfma") if matrix_pipe else "fast2")
-        _, dom_ms = timed_local(lambda: plan_dom.launch(cold=True), max(3, min(args.steps, 5)), 1, 0.05)
-        del plan_dom
-    else:
-        P_dom, dom_ms = P, kern_ms
-    pair_form = args.kernel in ("auto", "seq") and "two problems per row" in (main_kernel if n_main else tail_kernel)
-    path_info = None
-    if lmax5 is not None:
-        # regularisation path partitioned on the device (pb_fista_solve_path): two big launches per step -- the dense
-        # class on the matrix-pipe form, the sparse class on the pair form; each is timed on its own (same lists), the
-        # longer one is the step's dominant kernel
-        n_dense = int((lam < DENSE_RATIO * lmax5.repeat_interleave(y_rep)).sum().item())     # (the library's own test, path.h)
-        # (the dense class alone, without the re-solve: what its guards leave at n_done = -1)
-        _, _, nd0 = solver.fista_solve(Y, hrf, lam, step, n_iter, y_rep=y_rep, lmax=lmax5, force="path_dense")
-        n_back = int((nd0[lam < DENSE_RATIO * lmax5.repeat_interleave(y_rep)] < 0).sum())
-        t_cls = {}
-        for tag, frc in (("dense", "path_dense"), ("sparse", "path_sparse")):
-            pl = solver.FistaPlan(Y, hrf, lam, step, n_iter, y_rep=y_rep, force=frc, lmax=lmax5, W=plan.W)
-            _, t_cls[tag] = timed_local(lambda: pl.launch(cold=True), 3, 1, 0.0)
-        plan.launch(cold=True)                                  # the complete result again (the aids leave a class unsolved)
-        torch.cuda.synchronize(dev)
-        matrix_pipe = t_cls["dense"] >= t_cls["sparse"]
-        pair_form, split_form = not matrix_pipe, False
-        P_dom, dom_ms = (n_dense, t_cls["dense"]) if matrix_pipe else (P - n_dense, t_cls["sparse"])
+    roofline = path_info = None
+    if args.full:
+        # One step = ONE pb_fista_solve call = up to two kernels (solver.launch_plan): the whole
+        # rounds of waves on the dominant kernel, the remainder on the cheapest form.  The
+        # dominant kernel is timed on its own here (same grid, same data, a few launches after
+        # the timed region, THIS RANK ONLY: no collective, ranks may differ in their plans) so that
+        # its duration can be set against its rocprofv3 average.
+        # (per-problem lambdas -- config 5's regularisation path, sparse solutions by construction -- stay
+        # on the vector forms: the library does not put them on the matrix pipe)
+        P_dom = n_main if (args.kernel in ("auto", "seq") and n_main > 0) else P
+        split_form = matrix_pipe and "split over two" in (main_kernel if n_main else tail_kernel)
+        if matrix_pipe and "four waves" in (main_kernel if n_main else tail_kernel):
+            split_form = 4                                          # (641 .. 1 280 scans: one series over the four waves of a workgroup)
+        if P_dom != P and P_dom % y_rep == 0:
+            lam_dom = lam[:P_dom] if torch.is_tensor(lam) else lam
+            plan_dom = solver.FistaPlan(Y[:P_dom // y_rep], hrf, lam_dom, step, n_iter, y_rep=y_rep,
+                                        force=("mfma2" if split_form else "mfma") if matrix_pipe else "fast2")
+            _, dom_ms = timed_local(lambda: plan_dom.launch(cold=True), max(3, min(args.steps, 5)), 1, 0.05)
+            del plan_dom
+        else:
+            P_dom, dom_ms = P, kern_ms
+        pair_form = args.kernel in ("auto", "seq") and "two problems per row" in (main_kernel if n_main else tail_kernel)
+        if lmax5 is not None:
+            # regularisation path partitioned on the device (pb_fista_solve_path): two big launches per step -- the dense
+            # class on the matrix-pipe form, the sparse class on the pair form; each is timed on its own (same lists), the
+            # longer one is the step's dominant kernel
+            n_dense = int((lam < DENSE_RATIO * lmax5.repeat_interleave(y_rep)).sum().item())     # (the library's own test, path.h)
+            # (the dense class alone, without the re-solve: what its guards leave at n_done = -1)
+            _, _, nd0 = solver.fista_solve(Y, hrf, lam, step, n_iter, y_rep=y_rep, lmax=lmax5, force="path_dense")
+            n_back = int((nd0[lam < DENSE_RATIO * lmax5.repeat_interleave(y_rep)] < 0).sum())
+            t_cls = {}
+            for tag, frc in (("dense", "path_dense"), ("sparse", "path_sparse")):
+                pl = solver.FistaPlan(Y, hrf, lam, step, n_iter, y_rep=y_rep, force=frc, lmax=lmax5, W=plan.W)
+                _, t_cls[tag] = timed_local(lambda: pl.launch(cold=True), 3, 1, 0.0)
+            plan.launch(cold=True)                                  # the complete result again (the aids leave a class unsolved)
+            torch.cuda.synchronize(dev)
+            matrix_pipe = t_cls["dense"] >= t_cls["sparse"]
+            pair_form, split_form = not matrix_pipe, False
+            P_dom, dom_ms = (n_dense, t_cls["dense"]) if matrix_pipe else (P - n_dense, t_cls["sparse"])
+            main_kernel, tail_kernel, n_main = solver.KERNEL_NAMES[4], solver.KERNEL_NAMES[2], n_dense
+            kernel_name = main_kernel if matrix_pipe else tail_kernel
+            path_info = {"dense_ratio": DENSE_RATIO, "dense_problems": n_dense, "sparse_problems": P - n_dense,
+                         "handed_back_by_the_guards": n_back, "handed_back_fraction_of_dense": n_back / max(n_dense, 1),
+                         "dense_launch_ms": t_cls["dense"], "sparse_launch_ms": t_cls["sparse"],
+                         "note": "each launch includes the three partition launches (lists built on the device, no host "
+                                 "synchronisation) and covers P slots: waves beyond a list's length leave at once"}
+        flops_launch = flops_per_voxel_iter(N, K) * float(P_dom) * n_iter      # dominant kernel, one launch
+        exec_launch = (executed_flops_per_voxel_iter(N, K) if pair_form else flops_per_voxel_iter(N, K)) * float(P_dom) * n_iter
+        mfma_block = None
+        if matrix_pipe:
+            # what the matrix-pipe kernel EXECUTES: mfma_per_wave_iteration() matrix instructions per wave of 16 problems
+            n_mfma = mfma_per_wave_iteration(N, K, split_form)
+            mfma_flop = n_mfma * MFMA_FLOP / 16.0
+            exec_launch = mfma_flop * float(P_dom) * n_iter
+            mfma_block = {"mfma_instructions_per_16_problems_and_iteration": n_mfma,
+                          "waves_per_16_problems": 4 if split_form == 4 else (2 if split_form else 1),
+                          "f16_flops_per_voxel_iteration": mfma_flop,
+                          "matrix_pipe_busy_estimate": n_mfma * 16.0 / 16.0 * float(P_dom) * n_iter /
+                                                       (1024.0 * 2.1e9 * dom_ms * 1e-3),
+                          "note": "three float16 split products per tile (hi.hi, hi.lo, lo.hi), scans folded into the "
+                                  "tiles (a third of the tile entries are structural zeros); one-wave form: the far field rides "
+                                  "in a sum slot of the near tiles (no product of its own), split form: one carry tile per block.  "
+                                  "The kernel is bound by the issue of one wave per SIMD (the matrix instructions hold the "
+                                  "vector issue port for 8 of their 16 cycles) at the package power limit, not by the matrix pipe"}
+        alg_bytes = BYTES_PER_VOXEL_ITER_PER_SCAN * N * float(P_dom) * n_iter
+        traffic = None
+        tfile = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tfile) and cfg == 3:
+            try:
+                tj = json.load(open(tfile))
+                if tj.get("voxels") == P_dom and tj.get("iters") == n_iter and tj.get("scans") == N:
+                    traffic = tj.get("hbm_bytes_per_launch")
+            except Exception:
+                traffic = None
+        roofline = roofline_block(matrix_pipe, kernel_name if path_info else (main_kernel if n_main else tail_kernel), dom_ms, P_dom, n_iter, N, K,
+                                  flops_launch, exec_launch, alg_bytes, traffic, mfma_block,
+                                  {"step_kernels_ms": kern_ms,
+                                   **({} if path_info else {
+                                       "step_frac": (exec_launch if matrix_pipe else flops_launch) * (float(P) / P_dom) /
+                                                    (kern_ms * 1e-3) / 1e12 /
+                                                    (MFMA_F16_PEAK_TFLOPS if matrix_pipe else VALU_FP32_PEAK_TFLOPS)})})
+    elif lmax5 is not None:
+        # plain run of the regularisation path: the two classes by the library's own test (path.h), no launch timed on its
+        # own; the arithmetic named is that of the class holding more problems (--full: of the class whose launch is longer)
+        n_dense = int((lam < DENSE_RATIO * lmax5.repeat_interleave(y_rep)).sum().item())
+        matrix_pipe = n_dense >= P - n_dense
         main_kernel, tail_kernel, n_main = solver.KERNEL_NAMES[4], solver.KERNEL_NAMES[2], n_dense
         kernel_name = main_kernel if matrix_pipe else tail_kernel
-        path_info = {"dense_ratio": DENSE_RATIO, "dense_problems": n_dense, "sparse_problems": P - n_dense,
-                     "handed_back_by_the_guards": n_back, "handed_back_fraction_of_dense": n_back / max(n_dense, 1),
-                     "dense_launch_ms": t_cls["dense"], "sparse_launch_ms": t_cls["sparse"],
-                     "note": "each launch includes the three partition launches (lists built on the device, no host "
-                             "synchronisation) and covers P slots: waves beyond a list's length leave at once"}
-    flops_launch = flops_per_voxel_iter(N, K) * float(P_dom) * n_iter      # dominant kernel, one launch
-    exec_launch = (executed_flops_per_voxel_iter(N, K) if pair_form else flops_per_voxel_iter(N, K)) * float(P_dom) * n_iter
-    mfma_block = None
-    if matrix_pipe:
-        # what the matrix-pipe kernel EXECUTES: mfma_per_wave_iteration() matrix instructions per wave of 16 problems
-        n_mfma = mfma_per_wave_iteration(N, K, split_form)
-        mfma_flop = n_mfma * MFMA_FLOP / 16.0
-        exec_launch = mfma_flop * float(P_dom) * n_iter
-        mfma_block = {"mfma_instructions_per_16_problems_and_iteration": n_mfma,
-                      "waves_per_16_problems": 4 if split_form == 4 else (2 if split_form else 1),
-                      "f16_flops_per_voxel_iteration": mfma_flop,
-                      "matrix_pipe_busy_estimate": n_mfma * 16.0 / 16.0 * float(P_dom) * n_iter /
-                                                   (1024.0 * 2.1e9 * dom_ms * 1e-3),
-                      "note": "three float16 split products per tile (hi.hi, hi.lo, lo.hi), scans folded into the "
-                              "tiles (a third of the tile entries are structural zeros); one-wave form: the far field rides "
-                              "in a sum slot of the near tiles (no product of its own), split form: one carry tile per block.  "
-                              "The kernel is bound by the issue of one wave per SIMD (the matrix instructions hold the "
-                              "vector issue port for 8 of their 16 cycles) at the package power limit, not by the matrix pipe"}
-    alg_bytes = BYTES_PER_VOXEL_ITER_PER_SCAN * N * float(P_dom) * n_iter
-    traffic = None
-    tfile = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tfile) and cfg == 3:
-        try:
-            tj = json.load(open(tfile))
-            if tj.get("voxels") == P_dom and tj.get("iters") == n_iter and tj.get("scans") == N:
-                traffic = tj.get("hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
 
     ms_step = elapsed / args.steps * 1e3
     what = {2: "BASELINE config 2: %d voxels x %d scans, L1 deconv" % (V_total, N),
@@ -454,18 +492,13 @@ def run(args):
                    if args.kernel in ("auto", "seq") else [{"kernel": kernel_name, "problems": P}],
                    **({"regularisation_path": path_info} if path_info else {}),
                    "parallelism": "contiguous voxel shards x%d, no data-path collective" % world},
-        "roofline": roofline_block(matrix_pipe, kernel_name if path_info else (main_kernel if n_main else tail_kernel), dom_ms, P_dom, n_iter, N, K,
-                                   flops_launch, exec_launch, alg_bytes, traffic, mfma_block,
-                                   {"step_kernels_ms": kern_ms,
-                                    **({} if path_info else {
-                                        "step_frac": (exec_launch if matrix_pipe else flops_launch) * (float(P) / P_dom) /
-                                                     (kern_ms * 1e-3) / 1e12 /
-                                                     (MFMA_F16_PEAK_TFLOPS if matrix_pipe else VALU_FP32_PEAK_TFLOPS)})}),
     }
+    if roofline:
+        out["roofline"] = roofline
 
     if collective:
         out["collective"] = collective
-    if world > 1 and args.scaling == "strong":
+    if args.full and world > 1 and args.scaling == "strong":
         # secondary figure: weak scaling (every rank its own `--voxels` voxels); every rank takes
         # part (the decision depends on `world` and the flags only, never on a rank's own plan)
         Yw = make_batch(args.voxels, 2000 + rank)
@@ -482,7 +515,7 @@ def run(args):
                                "ms_per_step": el_w / steps_w * 1e3, "steps": steps_w}
         del Yw, planw
 
-    if rank == 0 and world == 1 and args.busy_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.busy_seconds > 0:
         # sustained rate: back-to-back solves for several seconds (clocks and temperatures settled)
         n_busy, t0 = 0, time.perf_counter()
         while time.perf_counter() - t0 < args.busy_seconds:
@@ -494,7 +527,7 @@ def run(args):
         out["sustained"] = {"value": float(P) * n_iter * n_busy / dt, "unit": "voxel-iterations/s",
                             "seconds": dt, "solves": n_busy}
 
-    if rank == 0 and world == 1 and cfg in (2, 3):
+    if args.full and rank == 0 and world == 1 and cfg in (2, 3):
         # wall clock to eps on diff_z, z AND x -- the solve plus pb_fista_outputs (z = cumsum(w), x = h * z)
         taps_d = torch.from_numpy(np.ascontiguousarray(hrf, dtype=np.float64)).to(dev)
         Zb, Xb = torch.empty_like(plan.W), torch.empty_like(plan.W)
@@ -505,7 +538,7 @@ def run(args):
         _, ms_out = timed_local(solve_and_outputs, max(3, min(args.steps, 10)), 1, 0.05)
         out["wall_clock_to_eps_ms_incl_outputs"] = ms_out
         del Zb, Xb
-    if rank == 0 and world == 1 and cfg == 3:
+    if args.full and rank == 0 and world == 1 and cfg == 3:
         out.update(pcie_inclusive(plan, Y, hrf, args.lbda, step, n_iter, solver, torch, dev, args.extras))
 
     if rank == 0 and world == 1 and args.extras and cfg == 3:
@@ -519,13 +552,32 @@ def run(args):
                            "kernel": solver.which_kernel(N, K, V2)}
         out["other_configs"] = others
 
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if cpu_legs:
         port, out["parity"] = cpu_port_and_parity(Y, plan.W, hrf, lam, y_rep, step, n_iter, args.cpu_seconds,
                                                   cpu_dense, n_main)
         out["cpu_baseline"] = cpu_baseline_block(cpu_dense, port, n_iter)
     if dist is not None:
         dist.destroy_process_group()
     return json.dumps(out) if rank == 0 else None
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor or array) as DIR/<name>.npy in float64.  An array larger
+    than its share of DUMP_BYTES keeps a fixed sample of its rows (seed 0, ascending order: the same rows on every run)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach()
+        row_bytes = 8 * (a.shape[1] if a.ndim == 2 else 1)
+        cap = DUMP_BYTES if a.ndim == 2 else DUMP_BYTES // 8
+        if a.ndim >= 1 and a.shape[0] * row_bytes > cap:
+            keep = max(1, cap // row_bytes)
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[torch.from_numpy(rows).to(a.device)] if torch.is_tensor(a) else a[rows]
+        a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64))
 
 
 def dtype_fields(matrix_pipe):
@@ -662,44 +714,59 @@ def run_config4(args, world, rank, dev, dist, V, V_total, lo, timed, timed_local
 
     elapsed, step_ms = timed(one_step, args.steps, args.warmup, args.spin_seconds)
     res["W"], res["h"], res["d"] = runner.result()
-
-    def eager_step():
-        distributed.bd_shared(Y, t_r, lbda=lbda, theta_0=2.0, hrf_dur=hrf_dur, nb_iter=nb_outer, nb_inner=nb_inner, comm=comm)
-    el_eager, _ = timed(eager_step, max(2, min(args.steps, 5)), 1, 0.0)       # (every rank: the loop holds collectives)
-    eager_ms = el_eager / max(2, min(args.steps, 5)) * 1e3
+    d = res["d"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"diff_z": res["W"], "hrf": res["h"], "theta": d["theta"], "cost": d["J"]})
     n_z = nb_outer + 1
     value = float(V_total) * n_z * nb_inner * args.steps / elapsed
-    d = res["d"]
-    # the z-steps alone (this rank, no collective): the shared-HRF pair kernel reading taps and step
-    # from device memory, warm-started, n_z launches of nb_inner iterations
-    taps = torch.from_numpy(np.ascontiguousarray(res["h"])).to(dev)
-    stepc = 1.0 / solver.gram_frobenius_batch(taps.reshape(1, -1), N)
-    Wz = torch.zeros((V, N), dtype=torch.float64, device=dev)
-
-    def z_steps():
-        for _ in range(n_z):
-            solver.fista_solve_pp(Y, taps, stepc, lbda, nb_inner, W0=Wz, inplace=True)
-    _, z_ms = timed_local(z_steps, 3, 1, 0.05)
     n_main, main_kernel, tail_kernel = solver.launch_plan(N, K, max(V, 1))
-    V_dom = n_main if n_main > 0 else V
-    Wd = torch.zeros((V_dom, N), dtype=torch.float64, device=dev)
-    Yd = Y[:V_dom]
     matrix_pipe = "matrix pipe" in (main_kernel if n_main else tail_kernel)
-    split_form = matrix_pipe and "split over two" in (main_kernel if n_main else tail_kernel)
-    _, dom_ms = timed_local(lambda: solver.fista_solve_pp(Yd, taps, stepc, lbda, nb_inner, W0=Wd, inplace=True,
-                                                          force="intermediate" if matrix_pipe else "fast2"), 10, 2, 0.05)
     dom_kernel = main_kernel if n_main else tail_kernel
-    flops_launch = flops_per_voxel_iter(N, K) * float(V_dom) * nb_inner
-    exec_launch = executed_flops_per_voxel_iter(N, K) * float(V_dom) * nb_inner
-    mfma_block = None
-    if matrix_pipe:
-        n_mfma = mfma_per_wave_iteration(N, K, split_form)
-        exec_launch = n_mfma * MFMA_FLOP / 16.0 * float(V_dom) * nb_inner
-        mfma_block = {"mfma_instructions_per_16_problems_and_iteration": n_mfma,
-                      "waves_per_16_problems": 2 if split_form else 1,
-                      "f16_flops_per_voxel_iteration": n_mfma * MFMA_FLOP / 16.0}
-    alg_bytes = BYTES_PER_VOXEL_ITER_PER_SCAN * N * float(V_dom) * nb_inner
     ms_step = elapsed / args.steps * 1e3
+    timings, roofline = {}, None
+    if args.full:
+        def eager_step():
+            distributed.bd_shared(Y, t_r, lbda=lbda, theta_0=2.0, hrf_dur=hrf_dur, nb_iter=nb_outer, nb_inner=nb_inner, comm=comm)
+        el_eager, _ = timed(eager_step, max(2, min(args.steps, 5)), 1, 0.0)       # (every rank: the loop holds collectives)
+        eager_ms = el_eager / max(2, min(args.steps, 5)) * 1e3
+        # the z-steps alone (this rank, no collective): the shared-HRF pair kernel reading taps and step
+        # from device memory, warm-started, n_z launches of nb_inner iterations
+        taps = torch.from_numpy(np.ascontiguousarray(res["h"])).to(dev)
+        stepc = 1.0 / solver.gram_frobenius_batch(taps.reshape(1, -1), N)
+        Wz = torch.zeros((V, N), dtype=torch.float64, device=dev)
+
+        def z_steps():
+            for _ in range(n_z):
+                solver.fista_solve_pp(Y, taps, stepc, lbda, nb_inner, W0=Wz, inplace=True)
+        _, z_ms = timed_local(z_steps, 3, 1, 0.05)
+        V_dom = n_main if n_main > 0 else V
+        Wd = torch.zeros((V_dom, N), dtype=torch.float64, device=dev)
+        Yd = Y[:V_dom]
+        split_form = matrix_pipe and "split over two" in (main_kernel if n_main else tail_kernel)
+        _, dom_ms = timed_local(lambda: solver.fista_solve_pp(Yd, taps, stepc, lbda, nb_inner, W0=Wd, inplace=True,
+                                                              force="intermediate" if matrix_pipe else "fast2"), 10, 2, 0.05)
+        flops_launch = flops_per_voxel_iter(N, K) * float(V_dom) * nb_inner
+        exec_launch = executed_flops_per_voxel_iter(N, K) * float(V_dom) * nb_inner
+        mfma_block = None
+        if matrix_pipe:
+            n_mfma = mfma_per_wave_iteration(N, K, split_form)
+            exec_launch = n_mfma * MFMA_FLOP / 16.0 * float(V_dom) * nb_inner
+            mfma_block = {"mfma_instructions_per_16_problems_and_iteration": n_mfma,
+                          "waves_per_16_problems": 2 if split_form else 1,
+                          "f16_flops_per_voxel_iteration": n_mfma * MFMA_FLOP / 16.0}
+        alg_bytes = BYTES_PER_VOXEL_ITER_PER_SCAN * N * float(V_dom) * nb_inner
+        timings = {"eager_loop_end_to_end_ms": eager_ms,
+                   "z_steps_ms": z_ms, "theta_steps_and_glue_ms": ms_step - z_ms,
+                   "z_step_fraction": z_ms / ms_step}
+        roofline = roofline_block(matrix_pipe, dom_kernel, dom_ms, V_dom, nb_inner, N, K, flops_launch, exec_launch,
+                                  alg_bytes, None, mfma_block,
+                                  {"whole_job_frac": (exec_launch if matrix_pipe else flops_launch) * (float(V) / V_dom) * n_z /
+                                                     (step_ms * 1e-3) / 1e12 /
+                                                     (MFMA_F16_PEAK_TFLOPS if matrix_pipe else VALU_FP32_PEAK_TFLOPS),
+                                   "note_config4": "dominant kernel = one z-step launch (100 iterations, warm start read "
+                                                   "from and written to HBM) on the whole rounds of the batch, incl. the "
+                                                   "6 us re-solve launch; whole_job_frac prices the whole bd_shared call "
+                                                   "(theta-steps, all-reduce and launch gaps included) the same way"})
     theta = np.asarray(d["theta"], dtype=np.float64)
     dt = dtype_fields(matrix_pipe)
     dt["dtype_note"] = ("z-steps: " + dt["dtype_note"] + ".  Intermediate z-steps of the outer loop run without the "
@@ -729,24 +796,15 @@ def run_config4(args, world, rank, dev, dist, V, V_total, lo, timed, timed_local
                                   "iteration" % (world, K * K + K + 2)},
         "config4": {"end_to_end_ms": ms_step, "submission": ("one HIP graph per bd_shared call" if runner.graph is not None
                                                              else "eager loop (%s)" % runner.fallback),
-                    "eager_loop_end_to_end_ms": eager_ms,
-                    "z_steps_ms": z_ms, "theta_steps_and_glue_ms": ms_step - z_ms,
-                    "z_step_fraction": z_ms / ms_step,
+                    **timings,
                     "theta_final": float(theta[-1]), "theta_true": theta_true,
                     "theta_trajectory": [round(float(t), 9) for t in theta],
                     "theta_trajectory_sha256_16": hashlib.sha256(np.round(theta, 9).tobytes()).hexdigest()[:16],
                     "cost_first_last": [float(d["J"][1]), float(d["J"][-1])]},
-        "roofline": roofline_block(matrix_pipe, dom_kernel, dom_ms, V_dom, nb_inner, N, K, flops_launch, exec_launch,
-                                   alg_bytes, None, mfma_block,
-                                   {"whole_job_frac": (exec_launch if matrix_pipe else flops_launch) * (float(V) / V_dom) * n_z /
-                                                      (step_ms * 1e-3) / 1e12 /
-                                                      (MFMA_F16_PEAK_TFLOPS if matrix_pipe else VALU_FP32_PEAK_TFLOPS),
-                                    "note_config4": "dominant kernel = one z-step launch (100 iterations, warm start read "
-                                                    "from and written to HBM) on the whole rounds of the batch, incl. the "
-                                                    "6 us re-solve launch; whole_job_frac prices the whole bd_shared call "
-                                                    "(theta-steps, all-reduce and launch gaps included) the same way"}),
     }
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if roofline:
+        out["roofline"] = roofline
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         out["parity"] = config4_parity(res["W"], res["h"], d, Y, t_r, hrf_dur, lbda, nb_outer, nb_inner, N, K,
                                        n_main, distributed, solver, torch, dev)
     return out

@@ -148,6 +148,29 @@ def test_bench_job_layout_and_self_launch_guard():
         assert r.returncode == 2 and "needs 2 GPUs" in r.stderr and r.stdout.strip() == ""
 
 
+def test_bench_dump_outputs_and_full_option(tmp_path, monkeypatch):
+    """bench.py: a plain run is not --full (--extras implies it); --dump-outputs writes float64 .npy files, a seeded
+    sample of ascending rows once an output exceeds DUMP_BYTES -- the same rows on every run, the dump under 64 MB."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert not args.full and args.steps == 7 and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--extras"])
+    assert bench.parse().full
+    W = torch.arange(30000 * 300, dtype=torch.float64).reshape(30000, 300)
+    n_done = torch.full((30000,), 500, dtype=torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"diff_z": W, "n_done": n_done})
+    a, b = np.load(tmp_path / "a" / "diff_z.npy"), np.load(tmp_path / "b" / "diff_z.npy")
+    assert a.dtype == np.float64 and a.shape == (bench.DUMP_BYTES // (8 * 300), 300) and np.array_equal(a, b)
+    rows = (a[:, 0] / 300).astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, W.numpy()[rows])
+    nd = np.load(tmp_path / "a" / "n_done.npy")
+    assert nd.dtype == np.float64 and np.array_equal(nd, np.full(30000, 500.0))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 64 << 20
+
+
 def test_launch_plan_of_a_plain_solve():
     """pb_fista_plan is a host-only query: whole rounds of pair waves (16 384 problems on 256
     CUs; the same default when no device is visible), half a round + a concurrent remainder

@@ -8,16 +8,16 @@ tag=${1:-r3k}
 out=$PWD/gpurun_out
 mkdir -p "$out"
 for c in 2 4 5; do
-  python3 bench.py --config $c > "$out/${tag}_bench_c$c.json" 2> "$out/${tag}_bench_c$c.err" || exit 1
+  python3 bench.py --full --config $c > "$out/${tag}_bench_c$c.json" 2> "$out/${tag}_bench_c$c.err" || exit 1
   echo "config $c done"
 done
-python3 bench.py > "$out/${tag}_bench_c3.json" 2> "$out/${tag}_bench_c3.err" || exit 1
+python3 bench.py --full > "$out/${tag}_bench_c3.json" 2> "$out/${tag}_bench_c3.err" || exit 1
 echo "config 3 done"
 cd /tmp && export TMPDIR=/tmp
 cd "$OLDPWD"
 run() {  # name, rocprofv3 args...
   local name=$1; shift
-  ( cd /tmp && timeout -k 10 400 rocprofv3 "$@" --output-format csv -d "$out/${tag}_$name" -o run -- python3 "$out/../bench.py" --steps 3 --warmup 1 --cpu-seconds 0 > "$out/${tag}_$name.json" 2> "$out/${tag}_$name.err" ) || { echo "$name failed"; return 1; }
+  ( cd /tmp && timeout -k 10 400 rocprofv3 "$@" --output-format csv -d "$out/${tag}_$name" -o run -- python3 "$out/../bench.py" --full --steps 3 --warmup 1 --cpu-seconds 0 > "$out/${tag}_$name.json" 2> "$out/${tag}_$name.err" ) || { echo "$name failed"; return 1; }
   echo "$name done"
 }
 run trace --kernel-trace --stats || exit 1

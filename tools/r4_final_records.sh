@@ -9,20 +9,20 @@ tag=${1:-r4k}
 out=$PWD/gpurun_out
 mkdir -p "$out"
 for c in 2 4 5; do
-  python3 bench.py --config $c > "$out/${tag}_bench_c$c.json" 2> "$out/${tag}_bench_c$c.err" || exit 1
+  python3 bench.py --full --config $c > "$out/${tag}_bench_c$c.json" 2> "$out/${tag}_bench_c$c.err" || exit 1
   echo "config $c done"
 done
-python3 bench.py > "$out/${tag}_bench_c3.json" 2> "$out/${tag}_bench_c3.err" || exit 1
+python3 bench.py --full > "$out/${tag}_bench_c3.json" 2> "$out/${tag}_bench_c3.err" || exit 1
 echo "config 3 done"
-python3 bench.py --scans 600 --voxels 50000 --cpu-seconds 4 > "$out/${tag}_bench_600_scans.json" 2> "$out/${tag}_bench_600_scans.err" || exit 1
+python3 bench.py --full --scans 600 --voxels 50000 --cpu-seconds 4 > "$out/${tag}_bench_600_scans.json" 2> "$out/${tag}_bench_600_scans.err" || exit 1
 for v in 12500 25000 50000; do
-  python3 bench.py --voxels $v --cpu-seconds 0 --busy-seconds 0 > "$out/${tag}_bench_${v}_voxels.json" 2> "$out/${tag}_bench_${v}_voxels.err" || exit 1
+  python3 bench.py --full --voxels $v --cpu-seconds 0 --busy-seconds 0 > "$out/${tag}_bench_${v}_voxels.json" 2> "$out/${tag}_bench_${v}_voxels.err" || exit 1
 done
-python3 bench.py --config 4 --voxels 6250 --cpu-seconds 0 > "$out/${tag}_bench_c4_6250_voxels.json" 2> "$out/${tag}_bench_c4_6250_voxels.err" || exit 1
+python3 bench.py --full --config 4 --voxels 6250 --cpu-seconds 0 > "$out/${tag}_bench_c4_6250_voxels.json" 2> "$out/${tag}_bench_c4_6250_voxels.err" || exit 1
 echo "shard sizes done"
 run() {  # name, bench args (quoted), rocprofv3 args...
   local name=$1 bargs=$2; shift 2
-  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 "$@" --output-format csv -d "$out/${tag}_$name" -o run -- python3 "$out/../bench.py" $bargs --steps 3 --warmup 1 --cpu-seconds 0 --busy-seconds 0 > "$out/${tag}_$name.json" 2> "$out/${tag}_$name.err" ) || { echo "$name failed"; return 1; }
+  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 "$@" --output-format csv -d "$out/${tag}_$name" -o run -- python3 "$out/../bench.py" --full $bargs --steps 3 --warmup 1 --cpu-seconds 0 --busy-seconds 0 > "$out/${tag}_$name.json" 2> "$out/${tag}_$name.err" ) || { echo "$name failed"; return 1; }
   echo "$name done"
 }
 run trace "" --kernel-trace --stats || exit 1

@@ -65,7 +65,7 @@ def main():
         known_out = voxels * scans * 8
         hbm = 2.0 * f_kb * 1024 + w_kb * 1024
         out = {"command": "rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) --output-format csv "
-                          "-- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0",
+                          "-- python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0",
                **info, "voxels": voxels, "scans": scans, "iters": iters,
                "raw": {"FETCH_SIZE_KB_per_dispatch": fetch["FETCH_SIZE"], "WRITE_SIZE_KB_per_dispatch": write["WRITE_SIZE"]},
                "known_input_bytes": known_in, "known_output_bytes": known_out,
@@ -99,7 +99,7 @@ def main():
             d["note_units"] = ("SQ_WAVE_CYCLES and SQ_ACTIVE_INST_* count quad-cycles (MI355X_MICROARCH.md); one "
                                "wave64 VALU instruction = 1 quad-cycle = 4 cycles")
         counters = " ".join(sorted(m))
-        out = {"command": "rocprofv3 --pmc %s --output-format csv -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0" % counters,
+        out = {"command": "rocprofv3 --pmc %s --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0" % counters,
                **info, "mean_per_dispatch": m, "derived": d}
         json.dump(out, open(sys.argv[3], "w"), indent=1)
         print(json.dumps(out)[:600])
