@@ -42,12 +42,17 @@ int check_launch(const char* what) {
 }
 
 constexpr int LDS_DOUBLES_MAX = 20000;  // 160 KB of LDS per workgroup
+// the generic kernel's LDS in doubles: the row and two iterates, the taps, the reduction slots, the window rule's iterates
+inline int64_t gen_lds_doubles(int N, int K, int stop_mode, int wind) {
+  return 3 * (int64_t)N + K + 2 * pb::GEN_WAVES + (stop_mode == PB_STOP_WINDOW ? (int64_t)wind * N : 0);
+}
 
 // ---- register-resident specialisations --------------------------------------
 typedef int (*fast_launch_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j,
                               int stop, hipStream_t);
 typedef int (*fast_launch_pp_fn)(const pb::FistaArgs&, int stop, hipStream_t);
-typedef int (*pair_launch_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j, hipStream_t);
+// the pair form and the three matrix-pipe forms
+typedef int (*launch_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j, hipStream_t);
 typedef int (*pair_cert_fn)(const pb::FistaArgs&, const double* taps, int K, hipStream_t);
 typedef int (*pair_split_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j, bool cert, hipStream_t);
 
@@ -55,8 +60,8 @@ struct FastEntry {
   int S, KT;
   fast_launch_fn fn;
   fast_launch_pp_fn fn_pp;
-  pair_launch_fn fn_pair;     // two-problems-per-row kernel (S <= 20, KT <= 32 only), else nullptr
-  pair_launch_fn fn_pair_ffa; // the same with 2-parallel fast FIRs (fista_pair_ffa.h)
+  launch_fn fn_pair;          // two-problems-per-row kernel (S <= 20, KT <= 32 only), else nullptr
+  launch_fn fn_pair_ffa;      // the same with 2-parallel fast FIRs (fista_pair_ffa.h)
   int (*fn_pair_dev)(const pb::FistaArgs&, hipStream_t);   // ... reading ONE shared HRF from device memory
   pair_cert_fn fn_pair_cert;  // ... carrying the window rule (wind = 6) as a no-fire certificate
   pair_split_fn fn_pair_split; // ... ONE series of 16 S < N <= 32 S scans per row (its halves in the two slots)
@@ -94,45 +99,43 @@ PB_MFMA4(6) PB_MFMA4(7) PB_MFMA4(8) PB_MFMA4(9) PB_MFMA4(10)
 }
 namespace {
 // the matrix-pipe form with one series split over the two waves of a workgroup (fista_mfma2.h): nb = ceil(N / 32)
-// blocks of 32 samples (it keeps round 3's carry tile: its waves are bound by the vector work of the exchange, not by
+// blocks of 32 samples (it keeps the carry tile: its waves are bound by the vector work of the exchange, not by
 // their matrix instructions -- the sum-slot form of fista_mfma.h measured 4 % slower there), 5 <= nb <= 20
 // (129 .. 640 scans), floor(nb / 2) of them in the left wave; K <= 33; plain solves, the cost
 // trace and the window rule (wind = 6) as a no-fire certificate; the shared-HRF z-step plain only
-typedef int (*mfma2_launch_fn)(const pb::FistaArgs&, const double*, int, bool, hipStream_t);
 // (34 <= K <= 65: three near tiles -- series of 225+ scans (four blocks per wave; the one-wave form carries shorter ones, and
-// everything up to 310 scans but the certificate), plain solves, the cost
-// trace, the certificate and the _loops_deconv rule: `extras` = taps from device memory wanted)
-mfma2_launch_fn pick_mfma2(int N, int K, bool extras = true) {
-  static const mfma2_launch_fn tab[] = {
+// everything up to 310 scans but the certificate), plain solves, the cost trace, the certificate and the _loops_deconv rule;
+// `two_tiles_only`: K <= 33)
+launch_fn pick_mfma2(int N, int K, bool two_tiles_only) {
+  static const launch_fn tab[] = {
       &pb::launch_mfma2<2, 3>, &pb::launch_mfma2<3, 3>, &pb::launch_mfma2<3, 4>, &pb::launch_mfma2<4, 4>,
       &pb::launch_mfma2<4, 5>, &pb::launch_mfma2<5, 5>, &pb::launch_mfma2<5, 6>, &pb::launch_mfma2<6, 6>,
       &pb::launch_mfma2<6, 7>, &pb::launch_mfma2<7, 7>, &pb::launch_mfma2<7, 8>, &pb::launch_mfma2<8, 8>,
       &pb::launch_mfma2<8, 9>, &pb::launch_mfma2<9, 9>, &pb::launch_mfma2<9, 10>, &pb::launch_mfma2<10, 10>};
   const int nb = (N + 31) / 32;
   if (K < 1 || K > 65 || nb < 5 || nb > 20) return nullptr;
-  if (K > 33 && (extras || N <= 224)) return nullptr;         // (three near tiles: four blocks at least per wave)
+  if (K > 33 && (two_tiles_only || N <= 224)) return nullptr;   // (three near tiles: four blocks at least per wave)
   return tab[nb - 5];
 }
 // the same with one series split over the FOUR waves of a workgroup (fista_mfma4.h): 641 .. 1 280 scans, A = ceil(N / 128)
 // blocks per wave (6 .. 10); K <= 33 with two near tiles: the call shapes of the two-wave form; 34 <= K <= 65 with three: plain
-// solves, the cost trace, the certificate and the _loops_deconv rule (`extras` = taps from device memory: two tiles only)
-mfma2_launch_fn pick_mfma4(int N, int K, bool extras = false) {
-  static const mfma2_launch_fn tab[] = {&pb::launch_mfma4<6>, &pb::launch_mfma4<7>, &pb::launch_mfma4<8>, &pb::launch_mfma4<9>,
-                                        &pb::launch_mfma4<10>};
-  if (K < 1 || K > 65 || (K > 33 && extras) || N <= 640 || N > 1280) return nullptr;
+// solves, the cost trace, the certificate and the _loops_deconv rule (`two_tiles_only`: K <= 33)
+launch_fn pick_mfma4(int N, int K, bool two_tiles_only) {
+  static const launch_fn tab[] = {&pb::launch_mfma4<6>, &pb::launch_mfma4<7>, &pb::launch_mfma4<8>, &pb::launch_mfma4<9>,
+                                  &pb::launch_mfma4<10>};
+  if (K < 1 || K > 65 || (K > 33 && two_tiles_only) || N <= 640 || N > 1280) return nullptr;
   return tab[(N + 127) / 128 - 6];
 }
-typedef int (*mfma_launch_fn)(const pb::FistaArgs&, const double*, int, bool, hipStream_t);
 // the matrix-pipe form (fista_mfma.h): NB = ceil(N / 31) blocks of 31 samples + one sum slot, 129 <= N <= 310; K <= 33
-// with two near tiles (every variant), 34 <= K <= 64 with three (`extras` = window-rule certificate:
-// not built for those)
+// with two near tiles (every variant), 34 <= K <= 64 with three (plain solves and the cost trace only: `stop_rule` = the
+// window-rule certificate or the _loops_deconv rule rides the kernel)
 constexpr int MFMA_K2 = 33, MFMA_K3 = 64;
 constexpr int MFMA1_NMAX = 10 * pb::MFMA_SPAN;   // longer series (up to 640 scans) run on the split form (fista_mfma2.h)
-mfma_launch_fn pick_mfma(int N, int K, bool extras = false) {
-  static const mfma_launch_fn tab[] = {&pb::launch_mfma<5>, &pb::launch_mfma<6>, &pb::launch_mfma<7>,
-                                       &pb::launch_mfma<8>, &pb::launch_mfma<9>, &pb::launch_mfma<10>};
+launch_fn pick_mfma(int N, int K, bool stop_rule) {
+  static const launch_fn tab[] = {&pb::launch_mfma<5>, &pb::launch_mfma<6>, &pb::launch_mfma<7>,
+                                  &pb::launch_mfma<8>, &pb::launch_mfma<9>, &pb::launch_mfma<10>};
   const int nb = (N + pb::MFMA_SPAN - 1) / pb::MFMA_SPAN;
-  if (K < 1 || K > MFMA_K3 || (K > MFMA_K2 && extras) || N <= 128 || nb > 10) return nullptr;   // (129 .. 310 scans: 5 .. 10 blocks)
+  if (K < 1 || K > MFMA_K3 || (K > MFMA_K2 && stop_rule) || N <= 128 || nb > 10) return nullptr;   // (129 .. 310 scans: 5 .. 10 blocks)
   return tab[nb - 5];
 }
 }  // namespace
@@ -180,6 +183,8 @@ const ExactEntry kExact[] = {
 
 // window lengths the register-resident forms carry (increment ring of wind - 2 slots in LDS)
 inline bool ring_wind(int wind) { return wind == 4 || wind == 6 || wind == 8; }
+// an entry of S samples per lane carries the call's stop rule: the window rule needs its increment ring (S <= 20)
+inline bool ring_fits(int S, int stop_mode, int wind) { return stop_mode != PB_STOP_WINDOW || (ring_wind(wind) && S <= 20); }
 
 // all-float64 register-resident form (one problem per wave): cheapest entry that holds (N, K)
 const ExactEntry* pick_exact(int N, int K) {
@@ -203,11 +208,11 @@ const WideEntry* pick_wide(int N, int K) {
 }
 
 template <int S, int KT>
-constexpr pair_launch_fn pair_or_null() {
+constexpr launch_fn pair_or_null() {
   if constexpr (S <= 20 && KT <= 32) return &pb::launch_pair<S, KT>; else return nullptr;
 }
 template <int S, int KT>
-constexpr pair_launch_fn pair_ffa_or_null() {
+constexpr launch_fn pair_ffa_or_null() {
   if constexpr (S <= 20 && KT <= 32) return &pb::launch_pair_ffa<S, KT>; else return nullptr;
 }
 template <int S, int KT>
@@ -260,7 +265,7 @@ constexpr int SPLIT_MIN_P = 1024;
 // is considered -- 305..310 scans fit ten blocks of 31 samples but have no single-slot pair entry, and one
 // matrix-pipe wave beats the pair form over two slots.
 bool mfma_serves_plain(int N, int K) {
-  return pick_mfma(N, K) != nullptr && (pick_fast(N, K) != nullptr || pick_wide(N, K) != nullptr);
+  return pick_mfma(N, K, false) != nullptr && (pick_fast(N, K) != nullptr || pick_wide(N, K) != nullptr);
 }
 // without a single-row entry (305..310 scans and more than 32 taps) the remainder of the whole rounds goes to the
 // one-problem-per-wave form when it is small, else everything runs on the matrix pipe (a partial last pass)
@@ -352,7 +357,7 @@ constexpr int MFMA2_LONG_MIN_P = 5120;
 // (HRFs of 34+ taps have no pair form to compete with, and the one-problem-per-wave form pays for every tap: N = 600, K = 42,
 // 4 096 problems 2.31 ms on the split form against 4.61 -- profiles/r5_long_series_42_taps.txt)
 inline int mfma2_long_min_p(int K) { return K > 33 ? 2048 : MFMA2_LONG_MIN_P; }
-bool mfma2_serves_long(int N, int K, bool extras = true) { return N > MFMA1_NMAX && pick_mfma2(N, K, extras) != nullptr && pick_wide(N, K) != nullptr; }
+bool mfma2_serves_long(int N, int K) { return N > MFMA1_NMAX && pick_mfma2(N, K, false) != nullptr && pick_wide(N, K) != nullptr; }
 // 225 .. 310 scans with 34+ taps and the window rule: the one-wave form has no certificate beside three near tiles (its state does
 // not fit), the split form has -- it takes such calls like a long series
 bool mfma2_takes_short_cert(int N, int K, int stop_mode, int wind) {     // (... and the _loops_deconv rule, which the one-wave form lacks there too)
@@ -368,7 +373,7 @@ int mfma2_long_base(int P, bool one_launch) {
 // the batch; whole passes, a remainder above MFMA4_MIN_R of a pass too, a smaller one -- and batches below it -- on the
 // one-problem-per-wave form
 constexpr int MFMA4_MIN_R_NUM = 10, MFMA4_MIN_R_DEN = 16;   // (N = 1 200: 2 048 problems 1.89 ms against 2.31, 3 072 2.59 against 2.30 -- profiles/r5_long_series_1200_scans.txt)
-bool mfma4_serves(int N, int K, bool extras = false) { return pick_mfma4(N, K, extras) != nullptr && pick_wide(N, K) != nullptr; }
+bool mfma4_serves(int N, int K) { return pick_mfma4(N, K, false) != nullptr && pick_wide(N, K) != nullptr; }
 int mfma4_base(int P, bool one_launch) {
   const int pass = (int)wave_slots() * 2;            // 16 problems x (slots / 2 per SIMD / 4 SIMDs per workgroup)
   const int base = (P / pass) * pass;
@@ -564,6 +569,294 @@ int normal_eq_impl(const double* z_dev, int64_t ldz, const TY* y_dev, int64_t ld
 }
 }  // namespace
 
+namespace {
+// the one-problem-per-wave entry worth using for SHORT series (the cheapest-per-problem tail
+// form): only entries whose strips are at most 8 samples
+const WideEntry* pick_wide_small(int N, int K) {
+  const WideEntry* we = pick_wide(N, K);
+  return (we && we->S <= 8) ? we : nullptr;
+}
+
+// Flag masks of the dispatch.  The forms split over waves, and the one-wave matrix-pipe form beside them, stay off under
+// a pinned vector form or PB_FLAG_NO_MFMA
+constexpr unsigned FLAGS_VECTOR_ONLY = PB_FLAG_FORCE_GENERIC | PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_FORCE_WIDE |
+                                       PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA;
+// ... the one-wave matrix-pipe form as a piece of a single-row entry's plan (whose entry PB_FLAG_FORCE_GENERIC / _FORCE_WIDE
+// have already ruled out); plan_ex reads these flags as "the plan without the matrix pipe"
+constexpr unsigned FLAGS_PAIR_PIN_OR_NO_MFMA = PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA;
+// the split pair form (one series over the two slots of a row)
+constexpr unsigned FLAGS_NO_SPLIT_PAIR = PB_FLAG_FORCE_GENERIC | PB_FLAG_NO_PAIR | PB_FLAG_FORCE_WIDE | PB_FLAG_DIRECT_FIR;
+// the partition on the device
+constexpr unsigned FLAGS_NO_PARTITION = PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_PAIR | PB_FLAG_FORCE_WIDE | PB_FLAG_NO_PAIR |
+                                        PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA | PB_FLAG_ONE_LAUNCH | PB_FLAG_FORCE_MFMA2 |
+                                        PB_FLAG_CERT_NO_RESOLVE | PB_FLAG_NO_PARTITION;
+
+// The window rule at the reference's wind = 6 as a per-iteration no-fire certificate (fista_pair_ffa.h, the matrix-pipe
+// forms), then an exact re-solve of the problems it could not clear (n_done = -1).  Worth it when the rule is not expected
+// to fire: the criterion decays like ~0.9/k on this problem class, so it cannot pass below tol before k ~ 0.9/tol --
+// tol * n_iter < CERT_TN_VECTOR.  The matrix-pipe forms' bound rests on four tracked samples per problem instead of
+// sixteen: only where the rule is far from firing, tol * n_iter < CERT_TN_MATRIX_PIPE; closer calls stay on the pair form.
+constexpr double CERT_TN_VECTOR = 0.5, CERT_TN_MATRIX_PIPE = 0.02;
+
+// ---- the dispatch of a float32 call: pb_fista_solve runs its route, the queries report it -------------------------------
+struct Call {
+  int N, K, P, stop_mode, wind;
+  unsigned flags;
+  bool cost_trace;     // J_dev given
+  bool lbda_vec;       // one lambda per problem
+  bool n_done;         // n_done_dev given
+  double tol_iters;    // tol * n_iter
+  bool taps_dev;       // the taps in device memory too
+  bool workspace;      // a partition workspace can be used
+  bool reported;       // a query: the cells where the queries have always answered otherwise than the solve runs (below)
+};
+
+enum Path {
+  PATH_PART_LONG,      // 311 .. 1 280 scans partitioned on the device: a split matrix-pipe form, the split pair form, the backup form
+  PATH_SPLIT_LONG,     // whole passes of a split matrix-pipe form, the remainder and the re-solve on the backup form
+  PATH_SPLIT_PAIR,     // the pair form with the two halves of ONE series in the slots of a row
+  PATH_PART_SHORT,     // a single-row entry's shape partitioned on the device: the one-wave matrix-pipe form and vector forms
+  PATH_PIECES,         // the host-side plan of a single-row entry's shape (plan.h), or one pinned form
+  PATH_MFMA_WIDE,      // the one-wave matrix-pipe form beside the one-problem-per-wave form
+  PATH_WIDE,           // one problem per wave
+  PATH_GENERIC         // the any-size LDS kernel
+};
+
+struct Route {
+  Path path;
+  const FastEntry* fe;   // single-row entry: PIECES, PART_SHORT; the backup form of SPLIT_LONG / PART_LONG unless backup_wide
+  const WideEntry* we;   // one-problem-per-wave entry: WIDE, MFMA_WIDE, SPLIT_PAIR's re-solve, the backup form when backup_wide
+  const FastEntry* se;   // split pair entry: SPLIT_PAIR, PART_LONG
+  launch_fn mfma;        // one-wave matrix-pipe form: PIECES, PART_SHORT, MFMA_WIDE (PART_SHORT without it: no dense class)
+  launch_fn split;       // the form split over two waves (over four beyond 640 scans)
+  bool backup_wide;
+  bool cert;             // the window rule as a certificate on the pair form (SPLIT_PAIR, PART_LONG: the split pair form)
+  bool mfma_cert;        // ... on the one-wave matrix-pipe form too
+  bool has_pair, has_wide, has_mfma2;   // the forms a plan may use (PART_LONG: has_pair = the split pair form)
+  int one_form;          // PIECES: this form over every problem in one launch (0: the plan)
+  int base;              // SPLIT_LONG, MFMA_WIDE: problems [0, base) on the matrix-pipe form
+};
+
+Route route(const Call& c) {
+  const int N = c.N, K = c.K, P = c.P, stop = c.stop_mode;
+  const unsigned fl = c.flags;
+  const bool plain = stop == PB_STOP_NONE, window6 = stop == PB_STOP_WINDOW && c.wind == 6;
+  Route r{};
+  const bool part_ws = c.workspace && c.n_done && P >= PART_MIN_P && K <= pb::LMAX_KT && N <= 1280 && !(fl & FLAGS_NO_PARTITION);
+  // the window rule as a certificate on a form with this limit of tol * n_iter
+  auto cert_clears = [&](double limit) { return !(fl & PB_FLAG_NO_CERT) && ((fl & PB_FLAG_FORCE_CERT) || c.tol_iters < limit); };
+  // the split matrix-pipe forms: plain solves, the certificate, the _loops_deconv rule in full inside the kernel (no cost
+  // trace); one lambda per problem only when asked for
+  const bool split_cert = window6 && c.n_done && cert_clears(CERT_TN_MATRIX_PIPE);
+  const bool split_rule = plain || split_cert || (stop == PB_STOP_LOOPS && !c.cost_trace);
+  const bool split_shape = split_rule && c.n_done && !(fl & FLAGS_VECTOR_ONLY) &&
+                           (!c.lbda_vec || (fl & (PB_FLAG_FORCE_MFMA | PB_FLAG_FORCE_MFMA2)));
+  const launch_fn mfma2 = split_shape ? pick_mfma2(N, K, false) : nullptr;
+  const launch_fn mfma4 = (split_shape && mfma4_serves(N, K)) ? pick_mfma4(N, K, false) : nullptr;
+  const bool four = N > 640;
+  const bool long_shape = mfma2_serves_long(N, K) || mfma2_takes_short_cert(N, K, stop, c.wind);
+  const bool long_call = long_shape && P >= mfma2_long_min_p(K);
+  // the exact vector form behind a split form (remainder, re-solve): single row, else one per wave -- with the window rule it
+  // must hold the rule's increment ring (the queries check the one-problem-per-wave entry's: 311..320 scans)
+  const FastEntry* fe1 = pick_fast(N, K);
+  const WideEntry* we1 = pick_wide(N, K);
+  r.backup_wide = we1 && (!fe1 || N > 320);
+  const bool backup_ok = (fe1 || we1) && ring_fits((r.backup_wide || (c.reported && we1)) ? we1->S : fe1->S, stop, c.wind);
+  // series of 16 S < N <= 32 S scans (the reference's 600-scan demo): the pair form with the two halves of ONE series in the
+  // slots of a row; the window rule as a certificate, re-solved on the one-problem-per-wave form
+  r.se = pick_split(N, K);
+  const bool split_pair_cert = r.se && window6 && c.n_done && we1 && ring_fits(we1->S, stop, c.wind) && cert_clears(CERT_TN_VECTOR);
+
+  // 311 .. 1 280 scans partitioned on the device: the dense class on whole passes of the split form, the sparse class on the
+  // pair form over two slots (or the backup form), handed-back problems compacted
+  if (part_ws && split_rule && (four ? mfma4_serves(N, K) : long_call) && backup_ok) {
+    r.path = PATH_PART_LONG;
+    r.split = four ? pick_mfma4(N, K, false) : pick_mfma2(N, K, false);
+    r.fe = fe1;
+    r.we = we1;
+    r.cert = split_pair_cert;
+    r.has_pair = r.se && (plain || split_pair_cert);
+    return r;
+  }
+  // Series of 311 .. 640 scans on the two-wave split form from mfma2_long_min_p problems on, 641 .. 1 280 on the four-wave
+  // form: whole passes (and a large remainder), the rest and whatever its guards hand back on the backup form.  Shorter
+  // series meet the two-wave form as a piece of the plan below (small batches, remainders) or through PB_FLAG_FORCE_MFMA2.
+  // (PB_FLAG_FORCE_MFMA2 as the queries report it: the long shapes, and plain solves or the certificate with up to 33 taps
+  // whatever the backup form)
+  const bool forced = (fl & PB_FLAG_FORCE_MFMA2) != 0;
+  const bool forced_short = c.reported && forced && (plain || window6) && pick_mfma2(N, K, true);
+  const launch_fn split = mfma4 ? mfma4 : ((mfma2 && ((forced && (!c.reported || long_shape || forced_short)) || long_call)) ? mfma2 : nullptr);
+  if (split && (backup_ok || forced_short)) {
+    r.path = PATH_SPLIT_LONG;
+    r.split = split;
+    r.fe = fe1;
+    r.we = we1;
+    const bool one_launch = (fl & PB_FLAG_ONE_LAUNCH) != 0;
+    r.base = (fl & PB_FLAG_FORCE_MFMA2) ? P : (mfma4 ? mfma4_base(P, one_launch) : mfma2_long_base(P, one_launch));
+    return r;
+  }
+  const bool mfma_plain = plain && c.n_done && (!c.lbda_vec || (fl & PB_FLAG_FORCE_MFMA)) && !(fl & FLAGS_VECTOR_ONLY) &&
+                          mfma_serves_plain(N, K);
+  if (!mfma_plain && !(fl & FLAGS_NO_SPLIT_PAIR) && r.se && (P >= SPLIT_MIN_P || (fl & PB_FLAG_FORCE_PAIR)) &&
+      (plain || split_pair_cert)) {
+    r.path = PATH_SPLIT_PAIR;
+    r.we = we1;
+    r.cert = split_pair_cert;
+    return r;
+  }
+  // the register-resident window rule keeps wind-1 iterates: wind = 4, 6 or 8 on entries small enough to hold them
+  const FastEntry* fe = (fl & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_WIDE)) ? nullptr : fe1;
+  if (fe && !ring_fits(fe->S, stop, c.wind)) fe = nullptr;
+  if (fe) {
+    r.fe = fe;
+    // (the queries report the certificate for a single problem too)
+    r.cert = window6 && fe->fn_pair_cert && c.n_done && (P >= 2 || c.reported) && !(fl & (PB_FLAG_NO_PAIR | PB_FLAG_DIRECT_FIR)) &&
+             cert_clears(CERT_TN_VECTOR);
+    // Plain solves (cost trace or not) of 129..310 scans, HRFs up to 33 taps (34..65: plain solves only): both operators on
+    // the matrix pipe (fista_mfma.h).  Needs n_done_dev: a problem whose scaled operands left the float16 range comes back
+    // with n_done = -1 and is re-solved on the single-row form.  Not with one lambda per problem, unless asked for
+    // (PB_FLAG_FORCE_MFMA): along a regularisation path a third of the problems (lambda near lambda_max) fail that
+    // kernel's accuracy guard and would be solved twice.  The window rule rides it as the certificate; the _loops_deconv
+    // rule is evaluated exactly inside it (no cost trace, K <= 33).
+    r.mfma_cert = r.cert && ((fl & PB_FLAG_FORCE_MFMA) || c.tol_iters < CERT_TN_MATRIX_PIPE);
+    const bool mfma_rule = plain || r.mfma_cert || (stop == PB_STOP_LOOPS && !c.cost_trace && K <= MFMA_K2);
+    const launch_fn mfma_shape = mfma_rule ? pick_mfma(N, K, !plain) : nullptr;
+    const launch_fn mfma = (mfma_shape && c.n_done && (!c.lbda_vec || (fl & PB_FLAG_FORCE_MFMA)) && !(fl & FLAGS_PAIR_PIN_OR_NO_MFMA))
+                               ? mfma_shape : nullptr;
+    r.has_pair = (fe->fn_pair && plain) || r.cert;
+    r.has_wide = pick_wide_small(N, K) != nullptr;
+    r.path = PATH_PIECES;
+    if (fl & PB_FLAG_NO_PAIR) {
+      r.one_form = FORM_FAST1;
+      return r;
+    }
+    // A call no matrix-pipe form carries -- another window, a cost trace beside the _loops_deconv rule, a long HRF -- is
+    // partitioned all the same, with an empty dense class: the conditioning guard is the partition's, and float32 vector
+    // forms need it too (ill-conditioned series: 3e-5 .. 5e-3 without it)
+    const bool part_mfma = mfma || (c.lbda_vec && mfma_shape);
+    if (part_ws && (part_mfma || !(fl & PB_FLAG_NO_ILL_GUARD))) {
+      r.path = PATH_PART_SHORT;
+      r.mfma = part_mfma ? mfma_shape : nullptr;
+      r.split = !part_mfma ? nullptr
+                : (mfma2 || !c.lbda_vec) ? mfma2
+                : ((plain || split_cert) && K <= MFMA_K2) ? pick_mfma2(N, K, false) : nullptr;
+      r.has_mfma2 = r.split && (plain || r.mfma_cert);
+      return r;
+    }
+    r.mfma = mfma;
+    r.split = mfma2;
+    // (the queries plan the two-wave form with up to 33 taps)
+    r.has_mfma2 = c.reported ? (plain || window6) && pick_mfma2(N, K, true) : mfma2 && (plain || r.mfma_cert);
+    if (fl & PB_FLAG_FORCE_PAIR) r.one_form = (r.cert || (fe->fn_pair && P >= 2 && plain)) ? FORM_PAIR : FORM_FAST1;
+    return r;
+  }
+  // 305..310 scans with more than 32 taps: no single-row entry, but ten blocks of 31 samples fit the matrix-pipe form --
+  // whole rounds (or everything) on it, a small remainder and the problems its guards hand back on the one-problem-per-wave form
+  const launch_fn mf = mfma_plain ? pick_mfma(N, K, false) : nullptr;
+  if (mf && we1) {
+    r.path = PATH_MFMA_WIDE;
+    r.mfma = mf;
+    r.we = we1;
+    r.base = mfma_wide_base(P, (fl & PB_FLAG_ONE_LAUNCH) != 0);
+    return r;
+  }
+  // long series: one problem per wave
+  if (!(fl & PB_FLAG_FORCE_GENERIC) && we1 && ring_fits(we1->S, stop, c.wind)) {
+    r.path = PATH_WIDE;
+    r.we = we1;
+    return r;
+  }
+  r.path = PATH_GENERIC;
+  return r;
+}
+
+// PATH_PIECES: the pinned form over every problem, else the plan of its forms (plan.h)
+int route_pieces(const Route& r, int N, int P, bool one_launch, bool one_stream, Piece* pc) {
+  if (r.one_form) {
+    pc[0] = Piece{r.one_form, 0, P, false, false};
+    return 1;
+  }
+  if (r.mfma) return plan_pieces_mfma(P, r.has_pair, r.has_wide, one_launch, one_stream, r.has_mfma2, beside_chunks_for(N), pc);
+  return plan_pieces(P, r.has_pair, r.has_wide, one_launch, one_stream, pc);
+}
+
+// What the queries report of a route: problems [0, n_main) on main_form, the rest (mostly) on tail_form.  Of pieces, the
+// leading ones of one form are the "main" part, the first other form the tail (of several: the one that carries most
+// of the remaining problems).  A partitioned call reports its host-side plan: the queries describe calls without a workspace.
+void report(const Route& r, int N, int P, bool one_launch, bool one_stream, int* nm, int* mf, int* tf) {
+  auto passes = [&](int base, int form, int rest) {
+    if (base > 0 && base < P) { *nm = base; *mf = form; *tf = rest; }
+    else *tf = base > 0 ? form : rest;
+  };
+  *nm = *mf = *tf = 0;
+  switch (r.path) {
+    case PATH_SPLIT_LONG: passes(r.base, N > 640 ? pb::FORM_MFMA4 : FORM_MFMA2, r.backup_wide ? FORM_WIDE : FORM_FAST1); return;
+    case PATH_MFMA_WIDE: passes(r.base, FORM_MFMA, FORM_WIDE); return;
+    case PATH_SPLIT_PAIR: *tf = FORM_PAIR; return;
+    case PATH_WIDE: *tf = FORM_WIDE; return;
+    case PATH_PIECES: {
+      Piece pc[pb::MAX_PIECES];
+      const int npc = route_pieces(r, N, P, one_launch, one_stream, pc);
+      int i = 1;
+      while (i < npc && pc[i].form == pc[0].form) ++i;
+      if (i == npc) { *tf = pc[0].form; return; }
+      *nm = pc[i - 1].p1;
+      *mf = pc[0].form;
+      int big = i;
+      for (int k = i + 1; k < npc; ++k)
+        if (pc[k].p1 - pc[k].p0 > pc[big].p1 - pc[big].p0) big = k;
+      *tf = pc[big].form;
+      return;
+    }
+    default: *tf = FORM_GENERIC; return;
+  }
+}
+
+int launched(int rejected, const char* why, const char* name) {
+  return rejected ? fail(PB_ERR_INVALID, "%s", why) : check_launch(name);
+}
+
+// Whole passes [0, base) on a matrix-pipe form (`main`), the remainder [base, P) on a vector form (`rest`), then `rest`
+// again over [0, base) for the problems the matrix-pipe form's guards handed back (only_flagged: n_done = -1)
+template <class Main, class Rest>
+int run_passes(const pb::FistaArgs& a, int base, bool resolve, hipStream_t st, Main&& main, Rest&& rest) {
+  pb::FistaArgs b = a;
+  if (base > 0) {
+    b.P = base;
+    const int rc = main(b, st);
+    if (rc != PB_OK) return rc;
+  }
+  if (base < a.P) {
+    b = a;
+    b.p0 = base;
+    const int rc = rest(b, st);
+    if (rc != PB_OK) return rc;
+  }
+  if (base > 0 && resolve) {
+    b = a;
+    b.P = base;
+    b.only_flagged = 1;
+    return rest(b, st);
+  }
+  return PB_OK;
+}
+
+// the fields every FISTA entry point fills alike (the series, cost trace and per-problem taps are the caller's)
+pb::FistaArgs fista_args(int P, int N, int K, int n_iter, int y_rep, int64_t ldy, double* w, int64_t ldw, double step,
+                         double lbda, const double* lbda_vec, const double* betas, int stop_mode, double tol,
+                         int32_t* n_done, unsigned flags) {
+  pb::FistaArgs a;
+  a.y = nullptr; a.y64 = nullptr; a.ldy = ldy; a.w = w; a.ldw = ldw; a.lbda_vec = lbda_vec;
+  a.betas = betas; a.J = nullptr; a.J64 = nullptr; a.ldj = 0; a.n_done = n_done;
+  a.step = step; a.lbda = lbda; a.tol = tol;
+  a.y_rep = y_rep; a.P = P; a.N = N; a.n_iter = n_iter; a.stop_mode = stop_mode;
+  a.taps_pp = nullptr; a.ldt = 0; a.step_vec = nullptr; a.step_shared = 0; a.K = K; a.p0 = 0;
+  a.cold = (flags & PB_FLAG_COLD_START) ? 1 : 0;
+  a.rho_guard = (flags & PB_FLAG_NO_RHO_GUARD) ? 0 : 1;
+  return a;
+}
+}  // namespace
+
 extern "C" {
 
 int pb_version(void) { return 100; }
@@ -581,50 +874,13 @@ int pb_fista_has_fast_path(int N, int K) {
   return (N >= 1 && K >= 1 && (pick_fast(N, K) || pick_wide(N, K))) ? 1 : 0;
 }
 
-// the one-problem-per-wave entry worth using for SHORT series (the cheapest-per-problem tail
-// form): only entries whose strips are at most 8 samples
-static const WideEntry* pick_wide_small(int N, int K) {
-  const WideEntry* we = pick_wide(N, K);
-  return (we && we->S <= 8) ? we : nullptr;
-}
-
-// the pair form carries plain solves and, as a no-fire certificate with an exact re-solve of what
-// it cannot clear, the window rule at the reference's wind = 6 (the queries assume the tolerance
-// is small enough for that path: tol * n_iter < 0.5, see pb_fista_solve)
-static bool pair_carries(const FastEntry* fe, int stop_mode, int wind) {
-  if (stop_mode == PB_STOP_NONE) return fe->fn_pair != nullptr;
-  return stop_mode == PB_STOP_WINDOW && wind == 6 && fe->fn_pair_cert != nullptr;
-}
-
+// The queries describe the call they stand for -- one lambda, n_done given, the tolerance below both certificate limits,
+// no workspace -- and report its route
 int pb_fista_which_kernel(int N, int K, int P, int with_cost_trace, int stop_mode, int wind) {
   if (N < 1 || K < 1 || P < 1) return 0;
-  const bool mfma_plain = stop_mode == PB_STOP_NONE && mfma_serves_plain(N, K);
-  const bool split_shape = stop_mode == PB_STOP_NONE || (stop_mode == PB_STOP_WINDOW && wind == 6) || (stop_mode == PB_STOP_LOOPS && !with_cost_trace);
-  const bool mfma2_ok = (stop_mode == PB_STOP_NONE || (stop_mode == PB_STOP_WINDOW && wind == 6)) && pick_mfma2(N, K) != nullptr;
-  if (split_shape && mfma4_serves(N, K, false) && (stop_mode != PB_STOP_WINDOW || pick_wide(N, K)->S <= 20))
-    return mfma4_base(P, false) > 0 ? pb::FORM_MFMA4 : FORM_WIDE;
-  if (split_shape && (mfma2_serves_long(N, K, false) || mfma2_takes_short_cert(N, K, stop_mode, wind)) && P >= mfma2_long_min_p(K) && (stop_mode != PB_STOP_WINDOW || pick_wide(N, K)->S <= 20))
-    return mfma2_long_base(P, false) > 0 ? FORM_MFMA2 : ((pick_fast(N, K) && N <= 320) ? FORM_FAST1 : FORM_WIDE);   // (the solve's own backup form)
-  if (const FastEntry* se = pick_split(N, K))
-    if (!mfma_plain && P >= SPLIT_MIN_P && pair_carries(se, stop_mode, wind) && (stop_mode == PB_STOP_NONE || pick_wide(N, K)))
-      return FORM_PAIR;
-  const FastEntry* fe = pick_fast(N, K);
-  if (!fe && mfma_plain) return mfma_wide_base(P, false) > 0 ? FORM_MFMA : FORM_WIDE;
-  if (fe && (pair_carries(fe, stop_mode, wind) || stop_mode == PB_STOP_NONE || (stop_mode == PB_STOP_LOOPS && !with_cost_trace)) &&
-      pick_mfma(N, K, stop_mode != PB_STOP_NONE)) {   // plain solves, the window-rule certificate, the _loops_deconv rule
-    Piece pc[6];
-    plan_pieces_mfma(P, fe->fn_pair != nullptr && stop_mode != PB_STOP_LOOPS, pick_wide_small(N, K) != nullptr, false, false, mfma2_ok, beside_chunks_for(N), pc);
-    return pc[0].form;
-  }
-  if (fe && stop_mode == PB_STOP_WINDOW && (!ring_wind(wind) || fe->S > 20)) fe = nullptr;
-  if (!fe) {
-    const WideEntry* we = pick_wide(N, K);
-    if (we && stop_mode == PB_STOP_WINDOW && (!ring_wind(wind) || we->S > 20)) we = nullptr;
-    return we ? 3 : 0;
-  }
-  Piece pc[4];
-  plan_pieces(P, pair_carries(fe, stop_mode, wind), pick_wide_small(N, K) != nullptr, false, false, pc);
-  return pc[0].form;                                    // the form that carries most problems
+  int nm, mf, tf;
+  report(route(Call{N, K, P, stop_mode, wind, 0u, with_cost_trace != 0, false, true, 0.0, false, false, true}), N, P, false, false, &nm, &mf, &tf);
+  return nm ? mf : tf;                                  // the form that carries most problems
 }
 
 int pb_fista_plan(int N, int K, int P, int stop_mode, int wind, int* n_main, int* main_form,
@@ -632,74 +888,17 @@ int pb_fista_plan(int N, int K, int P, int stop_mode, int wind, int* n_main, int
   return pb_fista_plan_ex(N, K, P, stop_mode, wind, 0u, n_main, main_form, tail_form);
 }
 
+// (no cost trace; of the flags: the pins of the pair form and direct FIRs read as PB_FLAG_NO_MFMA -- the plan without the
+// matrix pipe --, PB_FLAG_ONE_LAUNCH, _FORCE_MFMA2 and _ONE_STREAM)
 int pb_fista_plan_ex(int N, int K, int P, int stop_mode, int wind, unsigned flags, int* n_main,
                      int* main_form, int* tail_form) {
   int nm = 0, mf = 0, tf = 0;
-  const bool no_mfma = (flags & (PB_FLAG_NO_MFMA | PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_DIRECT_FIR)) != 0;
-  const FastEntry* se = (N >= 1 && K >= 1 && P >= SPLIT_MIN_P) ? pick_split(N, K) : nullptr;
-  const bool mfma_plain = N >= 1 && K >= 1 && stop_mode == PB_STOP_NONE && !no_mfma && mfma_serves_plain(N, K);
-  const bool mfma2_ok = N >= 1 && K >= 1 && (stop_mode == PB_STOP_NONE || (stop_mode == PB_STOP_WINDOW && wind == 6)) && !no_mfma &&
-                        pick_mfma2(N, K) != nullptr;
-  const bool split_shape = stop_mode == PB_STOP_NONE || (stop_mode == PB_STOP_WINDOW && wind == 6) || stop_mode == PB_STOP_LOOPS;
-  if (N >= 1 && K >= 1 && P >= 1 && split_shape && !no_mfma &&
-      mfma4_serves(N, K, false) && (stop_mode != PB_STOP_WINDOW || pick_wide(N, K)->S <= 20)) {
-    const int base = mfma4_base(P, (flags & (PB_FLAG_ONE_LAUNCH | PB_FLAG_FORCE_MFMA2)) != 0);
-    if (base > 0 && base < P) { nm = base; mf = pb::FORM_MFMA4; tf = FORM_WIDE; }
-    else tf = base > 0 ? pb::FORM_MFMA4 : FORM_WIDE;
-  } else if (N >= 1 && K >= 1 && split_shape && !no_mfma && (mfma2_serves_long(N, K, false) || mfma2_takes_short_cert(N, K, stop_mode, wind)) && (P >= mfma2_long_min_p(K) || (flags & PB_FLAG_FORCE_MFMA2)) &&
-      (stop_mode != PB_STOP_WINDOW || pick_wide(N, K)->S <= 20)) {
-    const int base = mfma2_long_base(P, (flags & (PB_FLAG_ONE_LAUNCH | PB_FLAG_FORCE_MFMA2)) != 0);
-    const int backup_form = (pick_fast(N, K) && N <= 320) ? FORM_FAST1 : FORM_WIDE;      // what pb_fista_solve uses behind the split form
-    if (base > 0 && base < P) { nm = base; mf = FORM_MFMA2; tf = backup_form; }
-    else tf = base > 0 ? FORM_MFMA2 : backup_form;
-  } else if (mfma2_ok && (flags & PB_FLAG_FORCE_MFMA2) && P >= 1) {
-    tf = FORM_MFMA2;
-  } else if (se && !mfma_plain && pair_carries(se, stop_mode, wind) && (stop_mode == PB_STOP_NONE || pick_wide(N, K))) {
-    tf = FORM_PAIR;                                     // one launch of the split pair form
-  } else if (mfma_plain && P >= 1 && !pick_fast(N, K)) {
-    const int base = mfma_wide_base(P, (flags & PB_FLAG_ONE_LAUNCH) != 0);
-    if (base > 0 && base < P) { nm = base; mf = FORM_MFMA; tf = FORM_WIDE; }
-    else tf = base > 0 ? FORM_MFMA : FORM_WIDE;
-  } else if (N >= 1 && K >= 1 && P >= 1 && !no_mfma && pick_fast(N, K) &&
-             (pair_carries(pick_fast(N, K), stop_mode, wind) || stop_mode == PB_STOP_NONE || stop_mode == PB_STOP_LOOPS) &&
-             pick_mfma(N, K, stop_mode != PB_STOP_NONE)) {
-    Piece pc[6];
-    const int npc = plan_pieces_mfma(P, pick_fast(N, K)->fn_pair != nullptr && stop_mode != PB_STOP_LOOPS, pick_wide_small(N, K) != nullptr,
-                                     (flags & PB_FLAG_ONE_LAUNCH) != 0, (flags & PB_FLAG_ONE_STREAM) != 0, mfma2_ok, beside_chunks_for(N), pc);
-    int i = 1;
-    while (i < npc && pc[i].form == pc[0].form) ++i;
-    if (i < npc) {
-      nm = pc[i - 1].p1;
-      mf = pc[0].form;
-      int big = i;
-      for (int k = i + 1; k < npc; ++k)
-        if (pc[k].p1 - pc[k].p0 > pc[big].p1 - pc[big].p0) big = k;
-      tf = pc[big].form;
-    } else { nm = 0; mf = 0; tf = pc[0].form; }
-  } else if (N >= 1 && K >= 1 && P >= 1) {
-    const FastEntry* fe = pick_fast(N, K);
-    if (fe && stop_mode == PB_STOP_WINDOW && (!ring_wind(wind) || fe->S > 20)) fe = nullptr;
-    if (fe) {
-      Piece pc[4];
-      const int npc = plan_pieces(P, pair_carries(fe, stop_mode, wind),
-                                  pick_wide_small(N, K) != nullptr, false, false, pc);
-      // leading pieces of one form = the "main" part; the first other form = the tail
-      // (of several: the one that carries most of the remaining problems)
-      int i = 1;
-      while (i < npc && pc[i].form == pc[0].form) ++i;
-      if (i < npc) {
-        nm = pc[i - 1].p1;
-        mf = pc[0].form;
-        int big = i;
-        for (int k = i + 1; k < npc; ++k)
-          if (pc[k].p1 - pc[k].p0 > pc[big].p1 - pc[big].p0) big = k;
-        tf = pc[big].form;
-      } else { nm = 0; mf = 0; tf = pc[0].form; }
-    } else {
-      const WideEntry* we = pick_wide(N, K);
-      if (we && stop_mode == PB_STOP_WINDOW && (!ring_wind(wind) || we->S > 20)) we = nullptr;
-      tf = we ? FORM_WIDE : FORM_GENERIC;
-    }
+  if (N >= 1 && K >= 1 && P >= 1) {
+    const unsigned fl = ((flags & FLAGS_PAIR_PIN_OR_NO_MFMA) ? PB_FLAG_NO_MFMA : 0u) |
+                        (flags & (PB_FLAG_ONE_LAUNCH | PB_FLAG_FORCE_MFMA2 | PB_FLAG_ONE_STREAM));
+    const Route r = route(Call{N, K, P, stop_mode, wind, fl, false, false, true, 0.0, false, false, true});
+    // (the plan of the vector forms alone is reported as planned without PB_FLAG_ONE_LAUNCH / _ONE_STREAM)
+    report(r, N, P, r.mfma && (fl & PB_FLAG_ONE_LAUNCH), r.mfma && (fl & PB_FLAG_ONE_STREAM), &nm, &mf, &tf);
   }
   if (n_main) *n_main = nm;
   if (main_form) *main_form = mf;
@@ -732,49 +931,41 @@ static int solve_impl(const float* y_dev, int64_t ldy, int y_rep, double* w_dev,
     return fail(PB_ERR_INVALID, "pb_fista_solve: wind must be >= 2");
   if (P == 0) return PB_OK;
 
-  pb::FistaArgs a;
-  a.y = y_dev; a.y64 = nullptr; a.ldy = ldy; a.w = w_dev; a.ldw = ldw; a.lbda_vec = lbda_dev;
-  a.betas = betas_dev; a.J = J_dev; a.J64 = nullptr; a.ldj = ldj; a.n_done = n_done_dev;
-  a.step = step; a.lbda = lbda; a.tol = tol;
-  a.y_rep = y_rep; a.P = P; a.N = N; a.n_iter = n_iter; a.stop_mode = stop_mode;
-  a.taps_pp = nullptr; a.ldt = 0; a.step_vec = nullptr; a.step_shared = 0; a.K = K; a.p0 = 0;
-  a.cold = (flags & PB_FLAG_COLD_START) ? 1 : 0;
-  a.rho_guard = (flags & PB_FLAG_NO_RHO_GUARD) ? 0 : 1;
-  a.wind = wind;
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, step, lbda, lbda_dev, betas_dev, stop_mode, tol,
+                               n_done_dev, flags);
+  a.y = y_dev; a.J = J_dev; a.ldj = ldj; a.wind = wind;
 #ifdef PB_DEVELOPMENT                            // (development builds only: the series scale of the matrix-pipe form)
   if (const char* yb = getenv("PB_MFMA_YBITS")) {
     const int v = atoi(yb);
     if (v >= 8 && v <= 15) a.ybits = v;
   }
 #endif
+  const int V_series = (P + y_rep - 1) / y_rep;
+  // (PB_FLAG_FORCE_MFMA without the caller's lambda_max: "everything on the matrix pipe", unpartitioned)
+  const bool workspace = work_dev && work_len >= work_layout(P, V_series).total && !((flags & PB_FLAG_FORCE_MFMA) && !lmax_dev);
+  const Route r = route(Call{N, K, P, stop_mode, wind, flags, J_dev != nullptr, lbda_dev != nullptr, n_done_dev != nullptr,
+                             tol * (double)n_iter, taps_dev != nullptr, workspace, false});
+  const hipStream_t user = (hipStream_t)stream;
+  const bool wj = J_dev != nullptr;
+  const bool resolve = !(flags & PB_FLAG_CERT_NO_RESOLVE);
 
-
-  // ---- round 5: partition BEFORE solving (dense class -> matrix pipe, sparse class -> float32 vector forms) and a
-  // compacted re-solve of what a guard or certificate hands back; list lengths and launch plans live on the device
-  // (path.h, plan.h).  For every call a matrix-pipe form would carry: one lambda or one per problem, cost trace,
-  // window-rule certificate, _loops_deconv rule; series of 129..310 scans (fista_mfma_kernel) and of 311..640
-  // (fista_mfma2_kernel).  Without it a batch whose lambda lies near lambda_max was solved twice -- matrix pipe, then one
-  // handed-back problem per wave (profiles/r4_path_partition.txt: 2.05 against 3.20e9).
+  // ---- the partition BEFORE solving (dense class -> matrix pipe, sparse class -> float32 vector forms) and a compacted
+  // re-solve of what a guard or certificate hands back; list lengths and launch plans live on the device (path.h, plan.h).
+  // Without it a batch whose lambda lies near lambda_max was solved twice -- matrix pipe, then one handed-back problem per
+  // wave (profiles/r4_path_partition.txt: 2.05 against 3.20e9).
   //   launch_form(form, args, stream, exact_rule) -> 0 / 1 (rejected);  has_form(form, list) says which candidates exist
   //   (list 0: the call's one list -- matrix-pipe forms for its dense head, vector forms for the rest --, 1 / 2: the
   //   measurement aids "matrix-pipe candidates only" / "vector candidates only", 3: handed-back problems);
   //   bound(cand) = grid bound of a candidate in slots
-  const int V_series = (P + y_rep - 1) / y_rep;
-  const bool part_ws = work_dev && P >= PART_MIN_P && K <= pb::LMAX_KT && N <= 1280 && n_done_dev &&
-                       work_len >= work_layout(P, V_series).total &&
-                       !(flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_PAIR | PB_FLAG_FORCE_WIDE | PB_FLAG_NO_PAIR | PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA |
-                                  PB_FLAG_ONE_LAUNCH | PB_FLAG_FORCE_MFMA2 | PB_FLAG_CERT_NO_RESOLVE | PB_FLAG_NO_PARTITION)) &&
-                       !((flags & PB_FLAG_FORCE_MFMA) && !lmax_dev);      // ("everything on the matrix pipe", as before)
   // (the ill-conditioned class: register-resident float64 kernel where the shape has an entry; its window rule is wind = 6)
   auto ill_exact = [&]() -> const ExactEntry* {
     const ExactEntry* e = pick_exact(N, K);
     return (e && stop_mode == PB_STOP_WINDOW && wind != 6) ? nullptr : e;
   };
-  bool no_dense_class = false;                     // a partitioned call without a matrix-pipe form: every problem in the vector class
-  auto run_partition = [&](const pb::PlanSpec& dense, const pb::PlanSpec& sparse, const pb::PlanSpec& flagged,
+  const int64_t nd_g = gen_lds_doubles(N, K, stop_mode, wind);
+  auto run_partition = [&](const pb::PlanSpec& dense, const pb::PlanSpec& sparse, const pb::PlanSpec& flagged, bool no_dense_class,
                            auto&& launch_form, auto&& has_form, auto&& bound) -> int {
     const WorkLayout wl = work_layout(P, V_series);
-    hipStream_t user = (hipStream_t)stream;
     // lambda_max of every series (the caller's lmax_dev is not needed any more: the pass also sees max|y| and marks the
     // ill-conditioned series, which the caller's numbers do not tell) -- float32, ~55 us per 100 k series
     double* lm = reinterpret_cast<double*>(work_dev + wl.lmax);
@@ -784,7 +975,6 @@ static int solve_impl(const float* y_dev, int64_t ldy, int y_rep, double* w_dev,
       for (int k = 0; k < pb::LMAX_KT; ++k) lt.h[k] = k < K ? (float)taps_host[k] : 0.0f;
       for (int t = 0; t < N; ++t) { if (t < K) run += taps_host[t]; csum += std::fabs(run); }
       // (the marked series: float64 register-resident kernel, or the LDS one, which needs the taps in device memory and the row in LDS)
-      const int64_t nd_g = 3 * (int64_t)N + K + 2 * pb::GEN_WAVES + (stop_mode == PB_STOP_WINDOW ? (int64_t)wind * N : 0);
       const bool guard = !(flags & PB_FLAG_NO_ILL_GUARD);
       const double unit = csum / std::sqrt((double)N);
       const float f64_bound = (guard && (ill_exact() || (taps_dev && nd_g <= LDS_DOUBLES_MAX))) ? (float)(PART_GAMMA_F64 * unit) : 0.0f;
@@ -857,12 +1047,11 @@ static int solve_impl(const float* y_dev, int64_t ldy, int y_rep, double* w_dev,
       b.perm = work_dev;
       b.perm_side = 1;
       b.range = rg_ill;
-      const int64_t nd_g = 3 * (int64_t)N + K + 2 * pb::GEN_WAVES + (stop_mode == PB_STOP_WINDOW ? (int64_t)wind * N : 0);
       // (the register-resident float64 kernel where the shape has an entry: 1.0e9 voxel-iterations/s against 0.17e9)
       const ExactEntry* ee = ill_exact();
       if (ee) {
         b.grid_slots = P;
-        if (ee->fn(b, taps_host, K, J_dev != nullptr, stop_mode, user) != 0)
+        if (ee->fn(b, taps_host, K, wj, stop_mode, user) != 0)
           return fail(PB_ERR_INVALID, "pb_fista_solve: float64 kernel rejected the launch (ill-conditioned series)");
         rc = check_launch("fista_exact_kernel(ill-conditioned series)");
         if (rc != PB_OK) return rc;
@@ -886,404 +1075,187 @@ static int solve_impl(const float* y_dev, int64_t ldy, int y_rep, double* w_dev,
     return solve_list(rg_flag, 3, 3, true);
   };
 
-  // series of 16 S < N <= 32 S scans (the reference's 600-scan demo): the pair form with the two
-  // halves of ONE series in the slots of a row, in one launch; the window rule as a certificate,
-  // re-solved on the one-problem-per-wave form
-  const bool mfma_plain = stop_mode == PB_STOP_NONE && n_done_dev && (!lbda_dev || (flags & PB_FLAG_FORCE_MFMA)) &&
-                          !(flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_FORCE_WIDE |
-                                     PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA)) && mfma_serves_plain(N, K);
-  // The matrix-pipe form with every series split over two waves (fista_mfma2.h): plain solves without cost trace.
-  // Series of 311..640 scans run on it from MFMA2_LONG_MIN_P problems on: whole passes (and a remainder above a
-  // quarter of a pass), the rest and whatever its guards hand back on the one-problem-per-wave form.  Shorter series
-  // meet it as a piece of the plan below (small batches, remainders) or through PB_FLAG_FORCE_MFMA2.
-  // (the window rule rides it as the no-fire certificate of the one-wave form: wind = 6, far from firing)
-  const bool mfma2_cert = stop_mode == PB_STOP_WINDOW && wind == 6 && n_done_dev && !(flags & PB_FLAG_NO_CERT) &&
-                          ((flags & PB_FLAG_FORCE_CERT) || tol * (double)n_iter < 0.02);
-  // (the _loops_deconv rule in full inside the kernel, as on the one-wave form: no cost trace)
-  const bool split_loops = stop_mode == PB_STOP_LOOPS && !J_dev;
-  const mfma2_launch_fn mfma2 =
-      ((stop_mode == PB_STOP_NONE || mfma2_cert || split_loops) && n_done_dev && (!lbda_dev || (flags & (PB_FLAG_FORCE_MFMA | PB_FLAG_FORCE_MFMA2))) &&
-       !(flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_FORCE_WIDE | PB_FLAG_DIRECT_FIR |
-                  PB_FLAG_NO_MFMA))) ? pick_mfma2(N, K, false) : nullptr;
-  // (round 5) the same call shapes at 311..640 scans, partitioned on the device: dense class on whole passes of the split
-  // form, sparse class on the pair form over two slots (or the backup form), handed-back problems compacted
-  {
-    const bool four = N > 640;                       // 641 .. 1 280 scans: the form split over four waves (fista_mfma4.h)
-    const bool shape_ok = (stop_mode == PB_STOP_NONE || mfma2_cert || split_loops) && n_done_dev &&
-                          !(flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_FORCE_WIDE | PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA));
-    const mfma2_launch_fn mfma2_l = four ? ((shape_ok && mfma4_serves(N, K, false)) ? pick_mfma4(N, K, false) : nullptr)
-                                         : ((mfma2 || !lbda_dev || !(stop_mode == PB_STOP_NONE || mfma2_cert || split_loops)) ? mfma2 : pick_mfma2(N, K, false));
-    if (mfma2_l && part_ws && (four || ((mfma2_serves_long(N, K, false) || mfma2_takes_short_cert(N, K, stop_mode, wind)) && P >= mfma2_long_min_p(K)))) {
-      const FastEntry* fe1 = pick_fast(N, K);
-      const WideEntry* we1 = pick_wide(N, K);
-      const bool use_wide = we1 && (!fe1 || N > 320);
-      const bool backup_ok = (fe1 || we1) && (stop_mode != PB_STOP_WINDOW || (use_wide ? we1->S <= 20 : fe1->S <= 20));
-      const FastEntry* se = pick_split(N, K);
-      const bool scert_l = se && stop_mode == PB_STOP_WINDOW && wind == 6 && we1 && we1->S <= 20 && !(flags & PB_FLAG_NO_CERT) &&
-                           ((flags & PB_FLAG_FORCE_CERT) || tol * (double)n_iter < 0.5);
-      const bool split_ok = se != nullptr && (stop_mode == PB_STOP_NONE || scert_l);
-      if (backup_ok) {
-        const double slots = wave_slots();
-        pb::PlanSpec dense{3, 0, 0, 0, 1, 1, 0, slots};
-        if (four) { dense.pass_mult = 2; dense.rem_num16 = MFMA4_MIN_R_NUM; }
-        pb::PlanSpec sparse{4, split_ok ? 1 : 0, 0, 0, 1, 0, 0, slots};
-        pb::PlanSpec flagged{4, 0, 0, 0, 1, 0, 0, slots};
-        dense.backup_form = sparse.backup_form = flagged.backup_form = use_wide ? FORM_WIDE : FORM_FAST1;
-        sparse.min_pair = SPLIT_MIN_P;
-        const bool wj = J_dev != nullptr;
-        return run_partition(dense, sparse, flagged,
-          [&](int form, const pb::FistaArgs& b, hipStream_t st, bool exact_rule) -> int {
-            if (form == FORM_MFMA2) return mfma2_l(b, taps_host, K, wj, st);
-            if (form == FORM_PAIR) return se->fn_pair_split(b, taps_host, K, wj, scert_l && !exact_rule, st);
-            if (form == FORM_WIDE) return we1->fn(b, taps_host, K, wj, stop_mode, st);
-            return fe1->fn(b, taps_host, K, wj, stop_mode, st);
-          },
-          [&](int form, int list) -> bool {
-            if (form == FORM_MFMA2) return list <= 1;
-            if (list == 1) return false;
-            if (form == FORM_PAIR) return list != 3 && split_ok;
-            if (form == FORM_WIDE) return use_wide;
-            if (form == FORM_FAST1) return !use_wide;
-            return false;
-          },
-          [&](int c) -> int { return (c == pb::CAND_MFMA2 || c == pb::CAND_PAIR0 || c == pb::CAND_FAST0 || c == pb::CAND_WIDE) ? P : 0; });
-      }
+  switch (r.path) {
+    case PATH_PART_LONG: {
+      const bool four = N > 640;                     // 641 .. 1 280 scans: the form split over four waves (fista_mfma4.h)
+      const double slots = wave_slots();
+      pb::PlanSpec dense{3, 0, 0, 0, 1, 1, 0, slots};
+      if (four) { dense.pass_mult = 2; dense.rem_num16 = MFMA4_MIN_R_NUM; }
+      pb::PlanSpec sparse{4, r.has_pair ? 1 : 0, 0, 0, 1, 0, 0, slots};
+      pb::PlanSpec flagged{4, 0, 0, 0, 1, 0, 0, slots};
+      dense.backup_form = sparse.backup_form = flagged.backup_form = r.backup_wide ? FORM_WIDE : FORM_FAST1;
+      sparse.min_pair = SPLIT_MIN_P;
+      return run_partition(dense, sparse, flagged, false,
+        [&](int form, const pb::FistaArgs& b, hipStream_t st, bool exact_rule) -> int {
+          if (form == FORM_MFMA2) return r.split(b, taps_host, K, wj, st);
+          if (form == FORM_PAIR) return r.se->fn_pair_split(b, taps_host, K, wj, r.cert && !exact_rule, st);
+          if (form == FORM_WIDE) return r.we->fn(b, taps_host, K, wj, stop_mode, st);
+          return r.fe->fn(b, taps_host, K, wj, stop_mode, st);
+        },
+        [&](int form, int list) -> bool {
+          if (form == FORM_MFMA2) return list <= 1;
+          if (list == 1) return false;
+          if (form == FORM_PAIR) return list != 3 && r.has_pair;
+          if (form == FORM_WIDE) return r.backup_wide;
+          if (form == FORM_FAST1) return !r.backup_wide;
+          return false;
+        },
+        [&](int c) -> int { return (c == pb::CAND_MFMA2 || c == pb::CAND_PAIR0 || c == pb::CAND_FAST0 || c == pb::CAND_WIDE) ? P : 0; });
     }
-  }
-  // 641 .. 1 280 scans: the same call shapes on the form split over four waves (fista_mfma4.h)
-  const mfma2_launch_fn mfma4 =
-      ((stop_mode == PB_STOP_NONE || mfma2_cert || split_loops) && n_done_dev && (!lbda_dev || (flags & (PB_FLAG_FORCE_MFMA | PB_FLAG_FORCE_MFMA2))) &&
-       !(flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_FORCE_WIDE | PB_FLAG_DIRECT_FIR |
-                  PB_FLAG_NO_MFMA)) && mfma4_serves(N, K, false)) ? pick_mfma4(N, K, false) : nullptr;
-  if (mfma4) {
-    const WideEntry* we1 = pick_wide(N, K);
-    if (stop_mode != PB_STOP_WINDOW || we1->S <= 20) {     // (the window rule's re-solve needs the rule's increment ring)
-      auto backup = [&](const pb::FistaArgs& b) -> int { return we1->fn(b, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream); };
-      const int base = (flags & PB_FLAG_FORCE_MFMA2) ? P : mfma4_base(P, (flags & PB_FLAG_ONE_LAUNCH) != 0);
-      pb::FistaArgs b = a;
-      if (base > 0) {
-        b.P = base;
-        if (mfma4(b, taps_host, K, J_dev != nullptr, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: four-wave matrix-pipe kernel rejected the launch");
-        const int rc = check_launch("fista_mfma4_kernel");
-        if (rc != PB_OK) return rc;
-      }
-      if (base < P) {
-        b = a;
-        b.p0 = base;
-        if (backup(b) != 0) return fail(PB_ERR_INVALID, "pb_fista_solve: no vector form for the remainder");
-        const int rc = check_launch("fista_fast_kernel(wide, remainder)");
-        if (rc != PB_OK) return rc;
-      }
-      if (base > 0 && !(flags & PB_FLAG_CERT_NO_RESOLVE)) {
-        b = a;
-        b.P = base;
-        b.only_flagged = 1;
-        if (backup(b) != 0) return fail(PB_ERR_INVALID, "pb_fista_solve: no vector form for the re-solve");
-        return check_launch("fista_fast_kernel(wide, re-solve)");
-      }
-      return PB_OK;
+    case PATH_SPLIT_LONG: {
+      const bool four = N > 640;
+      return run_passes(a, r.base, resolve, user,
+        [&](const pb::FistaArgs& b, hipStream_t st) {
+          return four ? launched(r.split(b, taps_host, K, wj, st), "pb_fista_solve: four-wave matrix-pipe kernel rejected the launch", "fista_mfma4_kernel")
+                      : launched(r.split(b, taps_host, K, wj, st), "pb_fista_solve: split matrix-pipe kernel rejected the launch", "fista_mfma2_kernel");
+        },
+        [&](const pb::FistaArgs& b, hipStream_t st) {
+          const int bad = r.backup_wide ? r.we->fn(b, taps_host, K, wj, stop_mode, st) : r.fe->fn(b, taps_host, K, wj, stop_mode, st);
+          if (b.only_flagged)
+            return launched(bad, "pb_fista_solve: no vector form for the re-solve", four ? "fista_fast_kernel(wide, re-solve)" : "fista_fast_kernel(re-solve)");
+          return launched(bad, "pb_fista_solve: no vector form for the remainder", four ? "fista_fast_kernel(wide, remainder)" : "fista_fast_kernel(remainder)");
+        });
     }
-  }
-  if (mfma2 && ((flags & PB_FLAG_FORCE_MFMA2) || ((mfma2_serves_long(N, K, false) || mfma2_takes_short_cert(N, K, stop_mode, wind)) && P >= mfma2_long_min_p(K)))) {
-    const FastEntry* fe1 = pick_fast(N, K);
-    const WideEntry* we1 = pick_wide(N, K);
-    const bool use_wide = we1 && (!fe1 || N > 320);
-    // the exact vector form behind it (remainder, re-solve): single row, else one per wave -- with the window rule it
-    // must hold the rule's increment ring (strips of at most 20 samples)
-    const bool backup_ok = (fe1 || we1) && (stop_mode != PB_STOP_WINDOW || (use_wide ? we1->S <= 20 : fe1->S <= 20));
-    if (backup_ok) {
-      auto backup = [&](const pb::FistaArgs& b) -> int {
-        return use_wide ? we1->fn(b, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream)
-                        : fe1->fn(b, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream);
-      };
-      const int base = (flags & PB_FLAG_FORCE_MFMA2) ? P : mfma2_long_base(P, (flags & PB_FLAG_ONE_LAUNCH) != 0);
-      pb::FistaArgs b = a;
-      if (base > 0) {
-        b.P = base;
-        if (mfma2(b, taps_host, K, J_dev != nullptr, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: split matrix-pipe kernel rejected the launch");
-        const int rc = check_launch("fista_mfma2_kernel");
-        if (rc != PB_OK) return rc;
-      }
-      if (base < P) {
-        b = a;
-        b.p0 = base;
-        if (backup(b) != 0) return fail(PB_ERR_INVALID, "pb_fista_solve: no vector form for the remainder");
-        const int rc = check_launch("fista_fast_kernel(remainder)");
-        if (rc != PB_OK) return rc;
-      }
-      if (base > 0 && !(flags & PB_FLAG_CERT_NO_RESOLVE)) {
-        b = a;
-        b.P = base;
-        b.only_flagged = 1;
-        if (backup(b) != 0) return fail(PB_ERR_INVALID, "pb_fista_solve: no vector form for the re-solve");
-        return check_launch("fista_fast_kernel(re-solve)");
-      }
-      return PB_OK;
-    }
-  }
-  if (!mfma_plain && !(flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_NO_PAIR | PB_FLAG_FORCE_WIDE | PB_FLAG_DIRECT_FIR))) {
-    const FastEntry* se = pick_split(N, K);
-    const WideEntry* wre = se ? pick_wide(N, K) : nullptr;
-    const bool scert = se && stop_mode == PB_STOP_WINDOW && wind == 6 && n_done_dev && wre && wre->S <= 20 &&
-                       !(flags & PB_FLAG_NO_CERT) && ((flags & PB_FLAG_FORCE_CERT) || tol * (double)n_iter < 0.5);
-    if (se && (P >= SPLIT_MIN_P || (flags & PB_FLAG_FORCE_PAIR)) && (stop_mode == PB_STOP_NONE || scert)) {
-      if (se->fn_pair_split(a, taps_host, K, J_dev != nullptr, scert, (hipStream_t)stream) != 0)
-        return fail(PB_ERR_INVALID, "pb_fista_solve: split pair kernel rejected the launch");
-      int rc = check_launch("fista_pair_ffa_kernel(split)");
-      if (rc == PB_OK && scert && !(flags & PB_FLAG_CERT_NO_RESOLVE)) {
+    case PATH_SPLIT_PAIR: {
+      int rc = launched(r.se->fn_pair_split(a, taps_host, K, wj, r.cert, user), "pb_fista_solve: split pair kernel rejected the launch",
+                        "fista_pair_ffa_kernel(split)");
+      if (rc == PB_OK && r.cert && resolve) {
         pb::FistaArgs b = a;
         b.only_flagged = 1;
-        if (wre->fn(b, taps_host, K, J_dev != nullptr, PB_STOP_WINDOW, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: no one-problem-per-wave form for the re-solve");
-        rc = check_launch("fista_fast_kernel(wide, re-solve)");
+        rc = launched(r.we->fn(b, taps_host, K, wj, PB_STOP_WINDOW, user), "pb_fista_solve: no one-problem-per-wave form for the re-solve",
+                      "fista_fast_kernel(wide, re-solve)");
       }
       return rc;
     }
-  }
-  const FastEntry* fe = (flags & PB_FLAG_FORCE_GENERIC) ? nullptr : pick_fast(N, K);
-  // the register-resident window rule keeps wind-1 = 5 iterates in VGPRs: wind = 6
-  // (the reference default) on entries small enough to hold them; else LDS kernel
-  if (fe && stop_mode == PB_STOP_WINDOW && (!ring_wind(wind) || fe->S > 20)) fe = nullptr;
-  if (fe && (flags & PB_FLAG_FORCE_WIDE)) fe = nullptr;
-  // Window rule on the pair form: a per-iteration no-fire certificate (fista_pair_ffa.h), then an
-  // exact re-solve of the problems it could not clear (n_done = -1) on the single-row form.  Worth
-  // it when the rule is not expected to fire: the criterion decays like ~0.9/k on this problem
-  // class, so it cannot pass below tol before k ~ 0.9/tol.
-  const bool cert = fe && stop_mode == PB_STOP_WINDOW && wind == 6 && fe->fn_pair_cert && n_done_dev &&
-                    P >= 2 && !(flags & (PB_FLAG_NO_PAIR | PB_FLAG_NO_CERT | PB_FLAG_DIRECT_FIR)) &&
-                    ((flags & PB_FLAG_FORCE_CERT) || tol * (double)n_iter < 0.5);
-  // plain solves (cost trace or not) of 129..310 scans, HRFs up to 33 taps (34..65: no certificate): both operators on the
-  // matrix pipe (fista_mfma.h).  Needs n_done_dev: a problem whose scaled operands left the float16
-  // range comes back with n_done = -1 and is re-solved on the single-row form.
-  // Not with one lambda per problem, unless asked for (PB_FLAG_FORCE_MFMA): along a regularisation
-  // path a third of the problems (lambda near lambda_max) fail that kernel's accuracy guard and
-  // would be solved twice.
-  // The window rule rides it as the same no-fire certificate as on the pair form (`cert` above).
-  // (its bound rests on four tracked samples per problem instead of sixteen: only where the rule is
-  // far from firing, tol * n_iter < 0.02; closer calls stay on the pair form)
-  const bool mfma_cert = cert && ((flags & PB_FLAG_FORCE_MFMA) || tol * (double)n_iter < 0.02);
-  // (the _loops_deconv rule rides it too, evaluated exactly inside the kernel: no cost trace, K <= 33)
-  const bool mfma_loops = stop_mode == PB_STOP_LOOPS && !J_dev && K <= MFMA_K2;
-  const mfma_launch_fn mfma = (fe && (stop_mode == PB_STOP_NONE || mfma_cert || mfma_loops) && n_done_dev &&
-                               (!lbda_dev || (flags & PB_FLAG_FORCE_MFMA)) &&
-                               !(flags & (PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA)))
-                                  ? pick_mfma(N, K, stop_mode != PB_STOP_NONE) : nullptr;
-  if (fe) {
-    auto run = [&](int form, int p0, int p1) -> int {
-      pb::FistaArgs b = a;
-      b.p0 = p0;
-      b.P = p1;
-      if (form == FORM_MFMA) {
-        if (!mfma || mfma(b, taps_host, K, J_dev != nullptr, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: matrix-pipe kernel rejected the launch");
-        return check_launch("fista_mfma_kernel");
-      }
-      if (form == FORM_MFMA2) {
-        if (!mfma2 || mfma2(b, taps_host, K, J_dev != nullptr, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: split matrix-pipe kernel rejected the launch");
-        return check_launch("fista_mfma2_kernel");
-      }
-      if (form == FORM_PAIR && cert) {
-        if (fe->fn_pair_cert(b, taps_host, K, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: certificate kernel rejected the launch");
-        return check_launch("fista_pair_ffa_kernel(cert)");
-      }
-      if (form == FORM_PAIR) {
-        const pair_launch_fn fn = (fe->fn_pair_ffa && !(flags & PB_FLAG_DIRECT_FIR)) ? fe->fn_pair_ffa
-                                                                                      : fe->fn_pair;
-        if (fn(b, taps_host, K, J_dev != nullptr, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: pair kernel rejected the launch");
-        return check_launch("fista_pair_kernel");
-      }
-      if (form == FORM_WIDE) {
-        const WideEntry* we = pick_wide_small(N, K);
-        if (!we || we->fn(b, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: no one-problem-per-wave form");
-        return check_launch("fista_fast_kernel(wide)");
-      }
-      if (fe->fn(b, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-        return fail(PB_ERR_INVALID, "pb_fista_solve: no register-resident form for this stop rule");
-      return check_launch("fista_fast_kernel");
-    };
-    // flagged problems of the pair pieces [q0, q1): exact window rule, on `stream` (after the join)
-    auto resolve = [&](int q0, int q1) -> int {
-      if (flags & PB_FLAG_CERT_NO_RESOLVE) return PB_OK;
-      pb::FistaArgs b = a;
-      b.p0 = q0;
-      b.P = q1;
-      b.only_flagged = 1;
-      if (fe->fn(b, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-        return fail(PB_ERR_INVALID, "pb_fista_solve: no single-row form for the re-solve");
-      return check_launch("fista_fast_kernel(re-solve)");
-    };
-    if (flags & PB_FLAG_NO_PAIR) return run(FORM_FAST1, 0, P);
-    // (round 5: the call partitioned on the device -- run_partition above)
-    const bool part_mfma = mfma != nullptr || (fe && (stop_mode == PB_STOP_NONE || mfma_cert || mfma_loops) && lbda_dev &&
-                                               pick_mfma(N, K, stop_mode != PB_STOP_NONE) != nullptr);
-    // (... and a call no matrix-pipe form carries -- another window, a cost trace beside the _loops_deconv rule, a long HRF --
-    // is partitioned all the same, with an empty dense class: the conditioning guard is the partition's, and float32 vector
-    // forms need it too (ill-conditioned series: 3e-5 .. 5e-3 without it))
-    const bool part_guard_only = !part_mfma && !(flags & PB_FLAG_NO_ILL_GUARD);
-    if ((part_mfma || part_guard_only) && part_ws) {
-      no_dense_class = !part_mfma;
-      const mfma_launch_fn mfma_p = !part_mfma ? nullptr : (mfma ? mfma : pick_mfma(N, K, stop_mode != PB_STOP_NONE));
-      const mfma2_launch_fn mfma2_p = !part_mfma ? nullptr : ((mfma2 || !lbda_dev) ? mfma2 : (((stop_mode == PB_STOP_NONE || mfma2_cert) && K <= MFMA_K2) ? pick_mfma2(N, K) : nullptr));
-      const bool one_stream = (flags & PB_FLAG_ONE_STREAM) != 0 || stream_is_capturing((hipStream_t)stream);
+    case PATH_PART_SHORT: {
+      const FastEntry* fe = r.fe;
+      const bool one_stream = (flags & PB_FLAG_ONE_STREAM) != 0 || stream_is_capturing(user);
       const double slots = wave_slots();
-      const bool has_wide = pick_wide_small(N, K) != nullptr;
-      const bool has_pair = (fe->fn_pair != nullptr && stop_mode == PB_STOP_NONE) || cert;
-      const bool has_mfma2 = mfma2_p != nullptr && (stop_mode == PB_STOP_NONE || mfma_cert);
-      const pb::PlanSpec dense{1, has_pair ? 1 : 0, has_wide ? 1 : 0, 0, one_stream ? 1 : 0, has_mfma2 ? 1 : 0, beside_chunks_for(N), slots};
-      const pb::PlanSpec sparse{2, has_pair ? 1 : 0, has_wide ? 1 : 0, 0, one_stream ? 1 : 0, 0, 0, slots};
-      const pb::PlanSpec flagged{2, 0, has_wide ? 1 : 0, 0, 1, 0, 0, slots};
-      const bool wj = J_dev != nullptr;
-      return run_partition(dense, sparse, flagged,
+      const pb::PlanSpec dense{1, r.has_pair ? 1 : 0, r.has_wide ? 1 : 0, 0, one_stream ? 1 : 0, r.has_mfma2 ? 1 : 0, beside_chunks_for(N), slots};
+      const pb::PlanSpec sparse{2, r.has_pair ? 1 : 0, r.has_wide ? 1 : 0, 0, one_stream ? 1 : 0, 0, 0, slots};
+      const pb::PlanSpec flagged{2, 0, r.has_wide ? 1 : 0, 0, 1, 0, 0, slots};
+      return run_partition(dense, sparse, flagged, r.mfma == nullptr,
         [&](int form, const pb::FistaArgs& b, hipStream_t st, bool exact_rule) -> int {
-          if (form == FORM_MFMA) return mfma_p(b, taps_host, K, wj, st);
-          if (form == FORM_MFMA2) return mfma2_p(b, taps_host, K, wj, st);
-          if (form == FORM_PAIR && cert && !exact_rule) return fe->fn_pair_cert(b, taps_host, K, st);
+          if (form == FORM_MFMA) return r.mfma(b, taps_host, K, wj, st);
+          if (form == FORM_MFMA2) return r.split(b, taps_host, K, wj, st);
+          if (form == FORM_PAIR && r.cert && !exact_rule) return fe->fn_pair_cert(b, taps_host, K, st);
           if (form == FORM_PAIR) return fe->fn_pair_ffa(b, taps_host, K, wj, st);
           if (form == FORM_WIDE) return pick_wide_small(N, K)->fn(b, taps_host, K, wj, stop_mode, st);
           return fe->fn(b, taps_host, K, wj, stop_mode, st);
         },
         [&](int form, int list) -> bool {
-          if (form == FORM_MFMA) return list <= 1 && mfma_p != nullptr;
-          if (form == FORM_MFMA2) return list <= 1 && has_mfma2;
+          if (form == FORM_MFMA) return list <= 1 && r.mfma != nullptr;
+          if (form == FORM_MFMA2) return list <= 1 && r.has_mfma2;
           if (list == 1) return false;                                // (aid: matrix-pipe candidates only)
-          if (form == FORM_PAIR) return list != 3 && has_pair;
-          if (form == FORM_WIDE) return has_wide;
+          if (form == FORM_PAIR) return list != 3 && r.has_pair;
+          if (form == FORM_WIDE) return r.has_wide;
           return true;
         },
         [&](int c) -> int { return pb::cand_max_slots(c, P, slots); });
     }
-    if (flags & PB_FLAG_FORCE_PAIR) {
-      if (cert) {
-        const int rc = run(FORM_PAIR, 0, P);
-        return rc != PB_OK ? rc : resolve(0, P);
-      }
-      if (!fe->fn_pair || P < 2 || stop_mode != PB_STOP_NONE) return run(FORM_FAST1, 0, P);
-      return run(FORM_PAIR, 0, P);
-    }
-    // whole rounds on the densest form, the remainder on the cheapest (the pair form has no
-    // stop rules; the one-problem-per-wave form has them all); a remainder that fits beside
-    // half a round of pair waves runs on the side stream
-    const bool pair_ok = (fe->fn_pair != nullptr && stop_mode == PB_STOP_NONE) || cert;
-    Piece pc[6];
-    const bool one_stream = (flags & PB_FLAG_ONE_STREAM) != 0 || stream_is_capturing((hipStream_t)stream);
-    const int npc = mfma ? plan_pieces_mfma(P, pair_ok, pick_wide_small(N, K) != nullptr,
-                                            (flags & PB_FLAG_ONE_LAUNCH) != 0, one_stream,
-                                            mfma2 != nullptr && (stop_mode == PB_STOP_NONE || mfma_cert), beside_chunks_for(N), pc)
-                         : plan_pieces(P, pair_ok, pick_wide_small(N, K) != nullptr,
-                                       (flags & PB_FLAG_ONE_LAUNCH) != 0, one_stream, pc);
-    bool any_side = false;
-    int q0 = P, q1 = 0;                          // range of the pieces that may leave n_done = -1 (contiguous)
-    for (int i = 0; i < npc; ++i) {
-      any_side |= pc[i].side;
-      if ((pc[i].form == FORM_PAIR && cert) || pc[i].form == FORM_MFMA || pc[i].form == FORM_MFMA2) {
-        q0 = pc[i].p0 < q0 ? pc[i].p0 : q0;
-        q1 = pc[i].p1 > q1 ? pc[i].p1 : q1;
-      }
-    }
-    auto finish = [&](int rc) -> int { return (rc == PB_OK && q1 > q0) ? resolve(q0, q1) : rc; };
-    if (!any_side) {
+    case PATH_PIECES: {
+      // whole rounds on the densest form, the remainder on the cheapest (the pair form has no
+      // stop rules; the one-problem-per-wave form has them all); a remainder that fits beside
+      // half a round of pair waves runs on the side stream
+      const FastEntry* fe = r.fe;
+      auto run = [&](int form, int p0, int p1, hipStream_t st) -> int {
+        pb::FistaArgs b = a;
+        b.p0 = p0;
+        b.P = p1;
+        if (form == FORM_MFMA)
+          return launched(!r.mfma || r.mfma(b, taps_host, K, wj, st) != 0, "pb_fista_solve: matrix-pipe kernel rejected the launch", "fista_mfma_kernel");
+        if (form == FORM_MFMA2)
+          return launched(!r.split || r.split(b, taps_host, K, wj, st) != 0, "pb_fista_solve: split matrix-pipe kernel rejected the launch", "fista_mfma2_kernel");
+        if (form == FORM_PAIR && r.cert)
+          return launched(fe->fn_pair_cert(b, taps_host, K, st), "pb_fista_solve: certificate kernel rejected the launch", "fista_pair_ffa_kernel(cert)");
+        if (form == FORM_PAIR) {
+          const launch_fn fn = (fe->fn_pair_ffa && !(flags & PB_FLAG_DIRECT_FIR)) ? fe->fn_pair_ffa : fe->fn_pair;
+          return launched(fn(b, taps_host, K, wj, st), "pb_fista_solve: pair kernel rejected the launch", "fista_pair_kernel");
+        }
+        if (form == FORM_WIDE) {
+          const WideEntry* we = pick_wide_small(N, K);
+          return launched(!we || we->fn(b, taps_host, K, wj, stop_mode, st) != 0, "pb_fista_solve: no one-problem-per-wave form", "fista_fast_kernel(wide)");
+        }
+        return launched(fe->fn(b, taps_host, K, wj, stop_mode, st), "pb_fista_solve: no register-resident form for this stop rule", "fista_fast_kernel");
+      };
+      Piece pc[pb::MAX_PIECES];
+      const bool one_stream = r.one_form || (flags & PB_FLAG_ONE_STREAM) != 0 || stream_is_capturing(user);
+      const int npc = route_pieces(r, N, P, (flags & PB_FLAG_ONE_LAUNCH) != 0, one_stream, pc);
+      bool any_side = false;
+      int q0 = P, q1 = 0;                          // range of the pieces that may leave n_done = -1 (contiguous)
       for (int i = 0; i < npc; ++i) {
-        const int rc = run(pc[i].form, pc[i].p0, pc[i].p1);
-        if (rc != PB_OK) return rc;
+        any_side |= pc[i].side;
+        if ((pc[i].form == FORM_PAIR && r.cert) || pc[i].form == FORM_MFMA || pc[i].form == FORM_MFMA2) {
+          q0 = pc[i].p0 < q0 ? pc[i].p0 : q0;
+          q1 = pc[i].p1 > q1 ? pc[i].p1 : q1;
+        }
       }
-      return finish(PB_OK);
-    }
-    std::lock_guard<std::mutex> lock(g_side_mutex);
-    SideStream* ss = side_stream_locked();
-    if (!ss) {                                   // no side stream: same pieces, one after the other
-      for (int i = 0; i < npc; ++i) {
-        const int rc = run(pc[i].form, pc[i].p0, pc[i].p1);
-        if (rc != PB_OK) return rc;
-      }
-      return finish(PB_OK);
-    }
-    hipStream_t user = (hipStream_t)stream;
-    int rc_all = PB_OK;
-    bool forked = false;
-    for (int i = 0; i < npc && rc_all == PB_OK; ++i) {
-      if (pc[i].group && !forked) {              // whole rounds are in the queue: the group starts here
-        if (hipEventRecord(ss->fork, user) != hipSuccess || hipStreamWaitEvent(ss->stream, ss->fork, 0) != hipSuccess)
-          return fail(PB_ERR_HIP, "pb_fista_solve: fork to the side stream failed");
-        forked = true;
-      }
-      stream = pc[i].side ? (void*)ss->stream : (void*)user;      // `run` launches on `stream`
-      rc_all = run(pc[i].form, pc[i].p0, pc[i].p1);
-    }
-    stream = (void*)user;
-    if (!forked) return finish(rc_all);
-    // join even after an error so that the caller's stream never runs ahead of the side stream
-    if (hipEventRecord(ss->join, ss->stream) != hipSuccess || hipStreamWaitEvent(user, ss->join, 0) != hipSuccess)
-      return fail(PB_ERR_HIP, "pb_fista_solve: join of the side stream failed");
-    return finish(rc_all);
-  }
-  // 305..310 scans with more than 32 taps: no single-row entry, but ten blocks of 31 samples fit the matrix-pipe
-  // form -- whole rounds (or everything) on it, a small remainder and the problems its guards hand back on the
-  // one-problem-per-wave form
-  if (!fe && mfma_plain) {
-    const WideEntry* we = pick_wide(N, K);
-    const mfma_launch_fn mf = pick_mfma(N, K);
-    if (we && mf) {
-      const int base = mfma_wide_base(P, (flags & PB_FLAG_ONE_LAUNCH) != 0);
-      pb::FistaArgs b = a;
-      if (base > 0) {
-        b.P = base;
-        if (mf(b, taps_host, K, J_dev != nullptr, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: matrix-pipe kernel rejected the launch");
-        const int rc = check_launch("fista_mfma_kernel");
-        if (rc != PB_OK) return rc;
-      }
-      if (base < P) {
-        b = a;
-        b.p0 = base;
-        if (we->fn(b, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: no one-problem-per-wave form");
-        const int rc = check_launch("fista_fast_kernel(wide)");
-        if (rc != PB_OK) return rc;
-      }
-      if (base > 0 && !(flags & PB_FLAG_CERT_NO_RESOLVE)) {
-        b = a;
-        b.P = base;
+      // flagged problems of the pieces [q0, q1): exact rule on the single-row form, on the caller's stream (after the join)
+      auto finish = [&](int rc) -> int {
+        if (rc != PB_OK || q1 <= q0 || !resolve) return rc;
+        pb::FistaArgs b = a;
+        b.p0 = q0;
+        b.P = q1;
         b.only_flagged = 1;
-        if (we->fn(b, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: no one-problem-per-wave form for the re-solve");
-        return check_launch("fista_fast_kernel(wide, re-solve)");
+        return launched(fe->fn(b, taps_host, K, wj, stop_mode, user), "pb_fista_solve: no single-row form for the re-solve", "fista_fast_kernel(re-solve)");
+      };
+      std::unique_lock<std::mutex> lock(g_side_mutex, std::defer_lock);
+      SideStream* ss = nullptr;
+      if (any_side) {
+        lock.lock();
+        ss = side_stream_locked();
       }
-      return PB_OK;
+      if (!ss) {                                   // (no side stream: the same pieces, one after the other)
+        for (int i = 0; i < npc; ++i) {
+          const int rc = run(pc[i].form, pc[i].p0, pc[i].p1, user);
+          if (rc != PB_OK) return rc;
+        }
+        return finish(PB_OK);
+      }
+      int rc_all = PB_OK;
+      bool forked = false;
+      for (int i = 0; i < npc && rc_all == PB_OK; ++i) {
+        if (pc[i].group && !forked) {              // whole rounds are in the queue: the group starts here
+          if (hipEventRecord(ss->fork, user) != hipSuccess || hipStreamWaitEvent(ss->stream, ss->fork, 0) != hipSuccess)
+            return fail(PB_ERR_HIP, "pb_fista_solve: fork to the side stream failed");
+          forked = true;
+        }
+        rc_all = run(pc[i].form, pc[i].p0, pc[i].p1, pc[i].side ? ss->stream : user);
+      }
+      if (!forked) return finish(rc_all);
+      // join even after an error so that the caller's stream never runs ahead of the side stream
+      if (hipEventRecord(ss->join, ss->stream) != hipSuccess || hipStreamWaitEvent(user, ss->join, 0) != hipSuccess)
+        return fail(PB_ERR_HIP, "pb_fista_solve: join of the side stream failed");
+      return finish(rc_all);
     }
-  }
-  // long series: one problem per wave (window rule: wind = 6 and S <= 20, as above)
-  if (!(flags & PB_FLAG_FORCE_GENERIC)) {
-    const WideEntry* we = pick_wide(N, K);
-    if (we && stop_mode == PB_STOP_WINDOW && (!ring_wind(wind) || we->S > 20)) we = nullptr;
-    if (we) {
-      if (we->fn(a, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-        return fail(PB_ERR_INVALID, "pb_fista_solve: no one-problem-per-wave form for this stop rule");
-      return check_launch("fista_fast_kernel(wide)");
-    }
+    case PATH_MFMA_WIDE:
+      return run_passes(a, r.base, resolve, user,
+        [&](const pb::FistaArgs& b, hipStream_t st) {
+          return launched(r.mfma(b, taps_host, K, wj, st), "pb_fista_solve: matrix-pipe kernel rejected the launch", "fista_mfma_kernel");
+        },
+        [&](const pb::FistaArgs& b, hipStream_t st) {
+          const int bad = r.we->fn(b, taps_host, K, wj, stop_mode, st);
+          if (b.only_flagged) return launched(bad, "pb_fista_solve: no one-problem-per-wave form for the re-solve", "fista_fast_kernel(wide, re-solve)");
+          return launched(bad, "pb_fista_solve: no one-problem-per-wave form", "fista_fast_kernel(wide)");
+        });
+    case PATH_WIDE:
+      return launched(r.we->fn(a, taps_host, K, wj, stop_mode, user), "pb_fista_solve: no one-problem-per-wave form for this stop rule",
+                      "fista_fast_kernel(wide)");
+    case PATH_GENERIC:
+      break;
   }
   if (flags & PB_FLAG_FORCE_FAST)
     return fail(PB_ERR_INVALID, "pb_fista_solve: no register-resident kernel for N=%d K=%d stop=%d",
                 N, K, stop_mode);
-
   // generic path (any N, K that fit LDS; all stop rules)
   if (!taps_dev) return fail(PB_ERR_INVALID, "pb_fista_solve: taps_dev required for the generic kernel");
-  const int64_t nd = 3 * (int64_t)N + K + 2 * pb::GEN_WAVES +
-                     (stop_mode == PB_STOP_WINDOW ? (int64_t)wind * N : 0);
-  if (nd > LDS_DOUBLES_MAX)
+  if (nd_g > LDS_DOUBLES_MAX)
     return fail(PB_ERR_INVALID, "pb_fista_solve: N=%d K=%d wind=%d exceeds LDS", N, K, wind);
-  const size_t lds = (size_t)nd * sizeof(double);
+  const size_t lds = (size_t)nd_g * sizeof(double);
   if (J_dev)
-    hipLaunchKernelGGL((pb::fista_generic_kernel<true>), dim3(P), dim3(pb::GEN_THREADS), lds,
-                       (hipStream_t)stream, a, taps_dev, K, wind);
+    hipLaunchKernelGGL((pb::fista_generic_kernel<true>), dim3(P), dim3(pb::GEN_THREADS), lds, user, a, taps_dev, K, wind);
   else
-    hipLaunchKernelGGL((pb::fista_generic_kernel<false>), dim3(P), dim3(pb::GEN_THREADS), lds,
-                       (hipStream_t)stream, a, taps_dev, K, wind);
+    hipLaunchKernelGGL((pb::fista_generic_kernel<false>), dim3(P), dim3(pb::GEN_THREADS), lds, user, a, taps_dev, K, wind);
   return check_launch("fista_generic_kernel");
 }
 
@@ -1361,22 +1333,16 @@ int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
   if (ee && stop_mode == PB_STOP_WINDOW && wind != 6) ee = nullptr;
   if (!ee && (flags & PB_FLAG_FORCE_FAST))
     return fail(PB_ERR_INVALID, "pb_fista_solve_d: no register-resident float64 kernel for N=%d K=%d", N, K);
-  const int64_t nd = 3 * (int64_t)N + K + 2 * pb::GEN_WAVES +
-                     (stop_mode == PB_STOP_WINDOW ? (int64_t)wind * N : 0);
+  const int64_t nd = gen_lds_doubles(N, K, stop_mode, wind);
   if (!ee && nd > LDS_DOUBLES_MAX)
     return fail(PB_ERR_INVALID, "pb_fista_solve_d: N=%d K=%d wind=%d exceeds LDS", N, K, wind);
   if (P == 0) return PB_OK;
   if (!y_dev || !w_dev || (!ee && !taps_dev) || (n_iter > 0 && !betas_dev))
     return fail(PB_ERR_INVALID, "pb_fista_solve_d: NULL pointer");
   if (P > (1 << 25)) return fail(PB_ERR_INVALID, "pb_fista_solve_d: more than 2^25 problems per launch");
-  pb::FistaArgs a;
-  a.y = nullptr; a.y64 = y_dev; a.ldy = ldy; a.w = w_dev; a.ldw = ldw; a.lbda_vec = lbda_dev;
-  a.betas = betas_dev; a.J = nullptr; a.J64 = J_dev; a.ldj = ldj; a.n_done = n_done_dev;
-  a.step = step; a.lbda = lbda; a.tol = tol;
-  a.y_rep = y_rep; a.P = P; a.N = N; a.n_iter = n_iter; a.stop_mode = stop_mode;
-  a.taps_pp = nullptr; a.ldt = 0; a.step_vec = nullptr; a.step_shared = 0; a.K = K; a.p0 = 0;
-  a.cold = (flags & PB_FLAG_COLD_START) ? 1 : 0;
-  a.rho_guard = (flags & PB_FLAG_NO_RHO_GUARD) ? 0 : 1;
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, step, lbda, lbda_dev, betas_dev, stop_mode, tol,
+                               n_done_dev, flags);
+  a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj;
   if (ee) {
     if (ee->fn(a, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
       return fail(PB_ERR_INVALID, "pb_fista_solve_d: launch rejected");
@@ -1405,13 +1371,9 @@ int pb_fista_solve_backtrack_d(const double* y_dev, int64_t ldy, int y_rep, doub
   if (nd > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "pb_fista_solve_backtrack_d: N=%d K=%d exceeds LDS", N, K);
   if (P == 0) return PB_OK;
   if (!y_dev || !w_dev || !taps_dev || (n_iter > 0 && !betas_dev)) return fail(PB_ERR_INVALID, "pb_fista_solve_backtrack_d: NULL pointer");
-  pb::FistaArgs a;
-  a.y = nullptr; a.y64 = y_dev; a.ldy = ldy; a.w = w_dev; a.ldw = ldw; a.lbda_vec = lbda_dev;
-  a.betas = betas_dev; a.J = nullptr; a.J64 = nullptr; a.ldj = 0; a.n_done = n_done_dev;
-  a.step = step0; a.lbda = lbda; a.tol = 0.0;
-  a.y_rep = y_rep; a.P = P; a.N = N; a.n_iter = n_iter; a.stop_mode = PB_STOP_NONE;
-  a.taps_pp = nullptr; a.ldt = 0; a.step_vec = nullptr; a.step_shared = 0; a.K = K; a.p0 = 0;
-  a.cold = (flags & PB_FLAG_COLD_START) ? 1 : 0;
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, step0, lbda, lbda_dev, betas_dev, PB_STOP_NONE, 0.0,
+                               n_done_dev, flags & PB_FLAG_COLD_START);     // (no matrix-pipe guard here)
+  a.y64 = y_dev;
   hipLaunchKernelGGL(pb::fista_backtrack_kernel, dim3(P), dim3(pb::GEN_THREADS), (size_t)nd * sizeof(double), (hipStream_t)stream,
                      a, taps_dev, K, eta, max_halvings_per_iter, step_out_dev, halvings_out_dev);
   return check_launch("fista_backtrack_kernel");
@@ -1680,50 +1642,29 @@ int pb_fista_solve_pp(const float* y_dev, int64_t ldy, double* w_dev, int64_t ld
   if (stop_mode != PB_STOP_NONE && stop_mode != PB_STOP_LOOPS)
     return fail(PB_ERR_INVALID, "pb_fista_solve_pp: stop_mode must be PB_STOP_NONE or PB_STOP_LOOPS");
 
-  pb::FistaArgs a;
-  a.y = y_dev; a.y64 = nullptr; a.ldy = ldy; a.w = w_dev; a.ldw = ldw; a.lbda_vec = lbda_dev;
-  a.betas = betas_dev; a.J = nullptr; a.J64 = nullptr; a.ldj = 0; a.n_done = n_done_dev;
-  a.step = 0.0; a.lbda = lbda; a.tol = tol;
-  a.y_rep = 1; a.P = P; a.N = N; a.n_iter = n_iter; a.stop_mode = stop_mode;
-  a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = (ldt == 0); a.K = K;
-  a.p0 = 0;
-  a.cold = (flags & PB_FLAG_COLD_START) ? 1 : 0;
-  a.rho_guard = (flags & PB_FLAG_NO_RHO_GUARD) ? 0 : 1;
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, 1, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, stop_mode, tol, n_done_dev, flags);
+  a.y = y_dev; a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = (ldt == 0);
+  const hipStream_t user = (hipStream_t)stream;
+  const bool resolve = !(flags & PB_FLAG_CERT_NO_RESOLVE);
 
-  // ONE shared HRF, no stop rule, series of 311 .. 1 280 scans (round 5): whole passes on the matrix-pipe form split over two
+  // ONE shared HRF, no stop rule, series of 311 .. 1 280 scans: whole passes on the matrix-pipe form split over two
   // (up to 640 scans) or four waves, which read the HRF and its step from device memory; the rest, and what the guards hand
   // back, on the one-problem-per-wave form
-  if (N > MFMA1_NMAX && ldt == 0 && stop_mode == PB_STOP_NONE && n_done_dev && K <= 65 &&
-      !(flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_PAIR | PB_FLAG_NO_PAIR | PB_FLAG_NO_MFMA | PB_FLAG_FORCE_WIDE | PB_FLAG_DIRECT_FIR))) {
+  if (N > MFMA1_NMAX && ldt == 0 && stop_mode == PB_STOP_NONE && n_done_dev && K <= 65 && !(flags & FLAGS_VECTOR_ONLY)) {
     const bool four = N > 640;
-    const mfma2_launch_fn split = four ? pick_mfma4(N, K, false) : pick_mfma2(N, K, false);
+    const launch_fn split = four ? pick_mfma4(N, K, false) : pick_mfma2(N, K, false);
     const WideEntry* we = pick_wide(N, K);
     if (split && we && (four || P >= mfma2_long_min_p(K) || (flags & PB_FLAG_FORCE_MFMA2))) {
       const bool all = (flags & (PB_FLAG_ONE_LAUNCH | PB_FLAG_FORCE_MFMA2)) != 0;
-      const int base = four ? mfma4_base(P, all) : mfma2_long_base(P, all);
-      pb::FistaArgs b = a;
-      if (base > 0) {
-        b.P = base;
-        if (split(b, nullptr, K, false, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve_pp: split matrix-pipe kernel rejected the launch");
-        const int rc = check_launch(four ? "fista_mfma4_kernel(shared taps)" : "fista_mfma2_kernel(shared taps)");
-        if (rc != PB_OK) return rc;
-      }
-      if (base < P) {
-        b = a;
-        b.p0 = base;
-        if (we->fn_pp(b, stop_mode, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "pb_fista_solve_pp: launch rejected");
-        const int rc = check_launch("fista_fast_kernel(wide, pp, remainder)");
-        if (rc != PB_OK) return rc;
-      }
-      if (base > 0 && !(flags & PB_FLAG_CERT_NO_RESOLVE)) {
-        b = a;
-        b.P = base;
-        b.only_flagged = 1;
-        if (we->fn_pp(b, stop_mode, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "pb_fista_solve_pp: launch rejected");
-        return check_launch("fista_fast_kernel(wide, pp, re-solve)");
-      }
-      return PB_OK;
+      return run_passes(a, four ? mfma4_base(P, all) : mfma2_long_base(P, all), resolve, user,
+        [&](const pb::FistaArgs& b, hipStream_t st) {
+          return launched(split(b, nullptr, K, false, st), "pb_fista_solve_pp: split matrix-pipe kernel rejected the launch",
+                          four ? "fista_mfma4_kernel(shared taps)" : "fista_mfma2_kernel(shared taps)");
+        },
+        [&](const pb::FistaArgs& b, hipStream_t st) {
+          return launched(we->fn_pp(b, stop_mode, st), "pb_fista_solve_pp: launch rejected",
+                          b.only_flagged ? "fista_fast_kernel(wide, pp, re-solve)" : "fista_fast_kernel(wide, pp, remainder)");
+        });
     }
   }
   const FastEntry* fe = (flags & PB_FLAG_FORCE_GENERIC) ? nullptr : pick_fast(N, K);
@@ -1735,23 +1676,21 @@ int pb_fista_solve_pp(const float* y_dev, int64_t ldy, double* w_dev, int64_t ld
       // (the remainder of the whole rounds on the single-row or the one-problem-per-wave kernel,
       // both reading the shared HRF through their per-problem-taps form)
       const WideEntry* ws = pick_wide_small(N, K);
-      auto run = [&](int form, int p0, int p1) -> int {
+      auto run = [&](int form, int p0, int p1, hipStream_t st) -> int {
         pb::FistaArgs b = a;
         b.p0 = p0;
         b.P = p1;
-        const int bad = (form == FORM_PAIR)   ? fe->fn_pair_dev(b, (hipStream_t)stream)
-                        : (form == FORM_WIDE) ? ws->fn_pp(b, stop_mode, (hipStream_t)stream)
-                                              : fe->fn_pp(b, stop_mode, (hipStream_t)stream);
-        if (bad) return fail(PB_ERR_INVALID, "pb_fista_solve_pp: launch rejected");
-        return check_launch(form == FORM_PAIR ? "fista_pair_ffa_kernel(shared taps)" : "fista_fast_kernel(pp)");
+        const int bad = (form == FORM_PAIR)   ? fe->fn_pair_dev(b, st)
+                        : (form == FORM_WIDE) ? ws->fn_pp(b, stop_mode, st)
+                                              : fe->fn_pp(b, stop_mode, st);
+        return launched(bad, "pb_fista_solve_pp: launch rejected", form == FORM_PAIR ? "fista_pair_ffa_kernel(shared taps)" : "fista_fast_kernel(pp)");
       };
       // whole rounds (and a remainder above half a round) on the matrix-pipe form, which reads the
       // shared HRF and its step from device memory like the pair form; what the whole rounds leave goes to the
       // split form (fista_mfma2.h: half the latency for up to half a round) where plan_pieces_mfma would put it
-      int base = 0;
-      const mfma_launch_fn mfma = (n_done_dev && !(flags & (PB_FLAG_FORCE_PAIR | PB_FLAG_NO_MFMA))) ? pick_mfma(N, K) : nullptr;
-      const mfma2_launch_fn mfma2 = (mfma && K <= MFMA_K2) ? pick_mfma2(N, K) : nullptr;
-      int base2 = 0;                               // problems [base, base2) on the split form
+      const launch_fn mfma = (n_done_dev && !(flags & (PB_FLAG_FORCE_PAIR | PB_FLAG_NO_MFMA))) ? pick_mfma(N, K, false) : nullptr;
+      const launch_fn mfma2 = (mfma && K <= MFMA_K2) ? pick_mfma2(N, K, false) : nullptr;
+      int base = 0, base2 = 0;                     // problems [0, base) on the matrix-pipe form, [base, base2) on the split form
       if (mfma) {
         const int round = (int)wave_slots() * 8, half = round / 2;
         base = (P / round) * round;
@@ -1761,73 +1700,54 @@ int pb_fista_solve_pp(const float* y_dev, int64_t ldy, double* w_dev, int64_t ld
         else if (mfma2 && R > MFMA2_MIN_R && R <= half) base2 = P;
         else if (mfma2 && ws && R > half && R - half <= (int)wave_slots()) base2 = base + half;
         else if (R > half) base = base2 = P;
-        if (base > 0) {
-          pb::FistaArgs b = a;
-          b.P = base;
-          if (mfma(b, nullptr, K, false, (hipStream_t)stream) != 0)
-            return fail(PB_ERR_INVALID, "pb_fista_solve_pp: matrix-pipe kernel rejected the launch");
-          const int rc = check_launch("fista_mfma_kernel(shared taps)");
-          if (rc != PB_OK) return rc;
-        }
-        if (base2 > base) {
-          pb::FistaArgs b = a;
+      }
+      return run_passes(a, base2, resolve, user,
+        [&](const pb::FistaArgs& m, hipStream_t st) -> int {
+          pb::FistaArgs b = m;
+          if (base > 0) {
+            b.P = base;
+            const int rc = launched(mfma(b, nullptr, K, false, st), "pb_fista_solve_pp: matrix-pipe kernel rejected the launch",
+                                    "fista_mfma_kernel(shared taps)");
+            if (rc != PB_OK || base2 == base) return rc;
+          }
+          b = m;
           b.p0 = base;
-          b.P = base2;
-          if (mfma2(b, nullptr, K, false, (hipStream_t)stream) != 0)
-            return fail(PB_ERR_INVALID, "pb_fista_solve_pp: split matrix-pipe kernel rejected the launch");
-          const int rc = check_launch("fista_mfma2_kernel(shared taps)");
-          if (rc != PB_OK) return rc;
-          base = base2;
-        }
-      }
-      if (base < P) {
-        Plan pl{0, FORM_GENERIC, FORM_PAIR};
-        if (!(flags & PB_FLAG_FORCE_PAIR))
-          pl = plan_plain(P - base, P - base >= 2, ws != nullptr, (flags & PB_FLAG_ONE_LAUNCH) != 0);
-        if (pl.n_main > 0) {
-          const int rc = run(pl.main_form, base, base + pl.n_main);
-          if (rc != PB_OK) return rc;
-        }
-        const int rc = run(pl.tail_form, base + pl.n_main, P);
-        if (rc != PB_OK) return rc;
-      }
-      if (base > 0 && !(flags & PB_FLAG_CERT_NO_RESOLVE)) {   // problems the matrix-pipe form handed back (n_done = -1)
-        pb::FistaArgs b = a;
-        b.P = base;
-        b.only_flagged = 1;
-        if (fe->fn_pp(b, stop_mode, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve_pp: launch rejected");
-        return check_launch("fista_fast_kernel(pp, re-solve)");
-      }
-      return PB_OK;
+          return launched(mfma2(b, nullptr, K, false, st), "pb_fista_solve_pp: split matrix-pipe kernel rejected the launch",
+                          "fista_mfma2_kernel(shared taps)");
+        },
+        [&](const pb::FistaArgs& b, hipStream_t st) -> int {
+          if (b.only_flagged)                      // (problems the matrix-pipe form handed back: n_done = -1)
+            return launched(fe->fn_pp(b, stop_mode, st), "pb_fista_solve_pp: launch rejected", "fista_fast_kernel(pp, re-solve)");
+          Plan pl{0, FORM_GENERIC, FORM_PAIR};
+          if (!(flags & PB_FLAG_FORCE_PAIR))
+            pl = plan_plain(P - base2, P - base2 >= 2, ws != nullptr, (flags & PB_FLAG_ONE_LAUNCH) != 0);
+          if (pl.n_main > 0) {
+            const int rc = run(pl.main_form, base2, base2 + pl.n_main, st);
+            if (rc != PB_OK) return rc;
+          }
+          return run(pl.tail_form, base2 + pl.n_main, P, st);
+        });
     }
     // one HRF per problem: single-row form, or one problem per wave where that finishes first
     // (small batches are latency-bound: 0.37 ms against 0.93 ms per 500 iterations up to 2 048)
     if (!(flags & (PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_ONE_LAUNCH))) {
       const WideEntry* ws = pick_wide_small(N, K);
       if (ws && best_form(P, false, true) == FORM_WIDE) {
-        if (ws->fn_pp(a, stop_mode, (hipStream_t)stream) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve_pp: launch rejected");
-        return check_launch("fista_fast_kernel(wide, pp)");
+        return launched(ws->fn_pp(a, stop_mode, user), "pb_fista_solve_pp: launch rejected", "fista_fast_kernel(wide, pp)");
       }
     }
-    if (fe->fn_pp(a, stop_mode, (hipStream_t)stream) != 0)
-      return fail(PB_ERR_INVALID, "pb_fista_solve_pp: launch rejected");
-    return check_launch("fista_fast_kernel(pp)");
+    return launched(fe->fn_pp(a, stop_mode, user), "pb_fista_solve_pp: launch rejected", "fista_fast_kernel(pp)");
   }
   if (!(flags & PB_FLAG_FORCE_GENERIC)) {
-    if (const WideEntry* we = pick_wide(N, K)) {
-      if (we->fn_pp(a, stop_mode, (hipStream_t)stream) != 0)
-        return fail(PB_ERR_INVALID, "pb_fista_solve_pp: launch rejected");
-      return check_launch("fista_fast_kernel(wide, pp)");
-    }
+    if (const WideEntry* we = pick_wide(N, K))
+      return launched(we->fn_pp(a, stop_mode, user), "pb_fista_solve_pp: launch rejected", "fista_fast_kernel(wide, pp)");
   }
   if (flags & PB_FLAG_FORCE_FAST)
     return fail(PB_ERR_INVALID, "pb_fista_solve_pp: no register-resident kernel for N=%d K=%d", N, K);
-  const int64_t nd = 3 * (int64_t)N + K + 2 * pb::GEN_WAVES;
+  const int64_t nd = gen_lds_doubles(N, K, stop_mode, 0);
   if (nd > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "pb_fista_solve_pp: N=%d K=%d exceeds LDS", N, K);
   hipLaunchKernelGGL((pb::fista_generic_kernel<false>), dim3(P), dim3(pb::GEN_THREADS),
-                     (size_t)nd * sizeof(double), (hipStream_t)stream, a, taps_dev, K, 0);
+                     (size_t)nd * sizeof(double), user, a, taps_dev, K, 0);
   return check_launch("fista_generic_kernel(pp)");
 }
 
@@ -1838,8 +1758,7 @@ int pb_fista_solve_path(const float* y_dev, int64_t ldy, int y_rep, double* w_de
                         const double* lbda_dev, const double* lmax_dev, double dense_ratio,
                         const double* betas_dev, int n_iter, int32_t* n_done_dev, int32_t* work_dev,
                         int64_t work_len, unsigned flags, void* stream) {
-  // (round 4's entry point for regularisation paths; since round 5 every call shape is partitioned:
-  // pb_fista_solve_ex with per-problem lambdas, the caller's lambda_max and workspace)
+  // (pb_fista_solve_ex with per-problem lambdas, the caller's lambda_max and workspace)
   if (P > 0 && (!lbda_dev || !n_done_dev))
     return fail(PB_ERR_INVALID, "pb_fista_solve_path: NULL pointer (per-problem lambdas and n_done are required)");
   return solve_impl(y_dev, ldy, y_rep, w_dev, ldw, P, N, taps_host, taps_dev, K, step, 0.0, lbda_dev, betas_dev, n_iter,

@@ -106,6 +106,43 @@ def test_version_and_dispatch_table(lib):
     assert lib.pb_fista_which_kernel(1281, 30, 100000, 0, 0, 6) == 3
     assert lib.pb_fista_which_kernel(5000, 30, 10, 0, 0, 6) == 0
 
+    # pb_fista_plan_ex, (n_main, main form, tail form), one case or more per path of the dispatch
+    def plan_ex(N, K, P, stop, wind, flags):
+        nm, mf, tf = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+        assert lib.pb_fista_plan_ex(N, K, P, stop, wind, flags, ctypes.byref(nm), ctypes.byref(mf), ctypes.byref(tf)) == 0
+        return nm.value, mf.value, tf.value
+    no_mfma, force_mfma2, one_launch, force_pair, one_stream = 8192, 65536, 32, 8, 128
+    # whole passes of a split matrix-pipe form, the remainder on the backup form
+    assert plan_ex(1200, 28, 5000, 0, 6, 0) == (4096, 6, 3)              # four waves per series
+    assert plan_ex(1200, 28, 5000, 0, 6, one_launch) == (0, 0, 6)
+    assert plan_ex(1200, 28, 2000, 0, 6, 0) == (0, 0, 3)
+    assert plan_ex(600, 30, 20000, 0, 6, 0) == (0, 0, 5)                 # two waves per series
+    assert plan_ex(600, 30, 20000, 2, 6, 0) == (0, 0, 5)
+    assert plan_ex(300, 30, 5000, 0, 6, force_mfma2) == (0, 0, 5)        # forced on shorter series
+    assert plan_ex(300, 30, 5000, 1, 6, force_mfma2) == (0, 0, 3)        # (reported as the vector plan; the solve runs the two-wave form)
+    # the split pair form
+    assert plan_ex(600, 30, 2000, 0, 6, no_mfma) == (0, 0, 2)
+    assert plan_ex(600, 30, 2000, 2, 6, 0) == (0, 0, 2)
+    assert plan_ex(315, 30, 6000, 2, 6, 0) == (0, 0, 5)                  # (reported as the two-wave form; the solve runs the split pair form)
+    # the plan of a single-row entry's forms: with the one-wave matrix-pipe form, and without it
+    assert plan_ex(300, 30, 12500, 0, 6, 0) == (0, 0, 4)
+    assert plan_ex(300, 30, 12500, 0, 6, one_stream) == (0, 0, 4)
+    assert plan_ex(300, 30, 12500, 0, 6, one_launch) == (0, 0, 4)
+    assert plan_ex(300, 30, 1, 2, 6, one_launch) == (0, 0, 4)
+    assert plan_ex(260, 40, 20000, 0, 6, 0) == (16384, 4, 1)
+    assert plan_ex(300, 30, 100000, 0, 6, no_mfma) == (98304, 2, 3)
+    assert plan_ex(300, 30, 100000, 0, 6, force_pair) == (98304, 2, 3)
+    assert plan_ex(300, 30, 12500, 0, 6, no_mfma | one_launch) == (8192, 2, 1)
+    # the one-wave matrix-pipe form beside the one-problem-per-wave form (305..310 scans, more than 32 taps)
+    assert plan_ex(308, 40, 100000, 0, 6, 0) == (98304, 4, 3)
+    assert plan_ex(308, 40, 100000, 0, 6, one_launch) == (0, 0, 4)
+    # one problem per wave; the LDS kernel
+    assert plan_ex(2000, 30, 100, 0, 6, 0) == (0, 0, 3)
+    assert plan_ex(300, 30, 1000, 2, 5, 0) == (0, 0, 0)
+    assert lib.pb_fista_which_kernel(315, 30, 6000, 0, 2, 6) == 5
+    assert lib.pb_fista_which_kernel(260, 40, 20000, 0, 0, 6) == 4
+    assert lib.pb_fista_which_kernel(300, 30, 1, 0, 2, 6) == 3
+
 
 def test_argument_errors_do_not_reach_the_gpu(lib):
     from pybold_amd import _lib
