@@ -339,6 +339,31 @@ int pb_op_adjoint(const double* r_dev, int64_t ldr, double* out_dev, int64_t ldo
                   int V, int n_in, int n_out, const double* taps_dev, int K, void* stream);
 
 /*
+ * Spectral (padded-FFT) operators, pybold/convolution.py:9-102 with the
+ * zeros-mirror-zeros padding of pybold/padding.py:283-423, without an FFT.
+ * Each reference function pads a row of N samples to L, multiplies spectra and
+ * unpads; that is a length-L circular convolution of the padded row xp read at
+ * the N unpadded positions:
+ *
+ *   pb_spectral_conv   out[i] = sum_{m<T} filt[m] xp[(pad_left + i - m) mod L]
+ *   pb_spectral_corr   out[i] = sum_{m<T} filt[m] xp[(pad_left + i + m) mod L]
+ *
+ * xp[q] = x[map[q]] where 0 <= map[q] < N, else 0 (map_dev: int32 [L], -1 marks
+ * a padded zero; entries outside [0, N) read as zero).  The filter is prepared
+ * by the caller: spectral_convolve / spectral_retro_convolve use filt = k[:L]
+ * (T = min(K, L)); spectral_deconvolve / spectral_retro_deconvolve use
+ * filt = irfft(1 / rfft(k, L), L) (T = L).  float64 rows, one workgroup per row;
+ * requires 1 <= N <= L, 0 <= pad_left <= L - N, 1 <= T <= L and
+ * 2 * T + N - 1 <= 20000 (LDS), else PB_ERR_INVALID.
+ */
+int pb_spectral_conv(const double* x_dev, int64_t ldx, double* out_dev, int64_t ldo,
+                     int V, int N, const int32_t* map_dev, int L, int pad_left,
+                     const double* filt_dev, int T, void* stream);
+int pb_spectral_corr(const double* x_dev, int64_t ldx, double* out_dev, int64_t ldo,
+                     int V, int N, const int32_t* map_dev, int L, int pad_left,
+                     const double* filt_dev, int T, void* stream);
+
+/*
  * Per-voxel HRF fit error  cost[v] = 0.5 || y_v - taps * z_v ||^2
  * (hrf_fit_err, pybold/bold_signal.py:217-222) for n_hrf candidate HRFs at
  * once: taps_dev float64 [n_hrf][K], cost_dev float64 [n_hrf][V].  The caller

@@ -99,6 +99,10 @@ SIGNATURES = {
                                _c_int, _ptr, _c_int, _ptr]),
     "pb_op_adjoint": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int,
                                _c_int, _ptr, _c_int, _ptr]),
+    "pb_spectral_conv": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int,   # x, ldx, out, ldo, V, N
+                                  _ptr, _c_int, _c_int, _ptr, _c_int, _ptr]),   # map, L, pad_left, filt, T, stream
+    "pb_spectral_corr": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int,
+                                  _ptr, _c_int, _c_int, _ptr, _c_int, _ptr]),
     "pb_hrf_cost": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _ptr,
                              _c_int, _c_int, _ptr, _ptr]),
     "pb_spectral_radius": (_c_int, [_ptr, _c_int, _ptr, _c_int, _c_int, _c_dbl, _ptr, _ptr]),

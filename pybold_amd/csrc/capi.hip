@@ -451,6 +451,27 @@ int launch_op(const double* x, int64_t ldx, double* out, int64_t ldo, int V, int
   return check_launch(name);
 }
 
+template <bool CORR>
+int launch_spectral(const double* x, int64_t ldx, double* out, int64_t ldo, int V, int N, const int32_t* map,
+                    int L, int pad_left, const double* filt, int T, void* stream, const char* name) {
+  if (V < 0 || N < 1 || L < N || T < 1 || T > L)
+    return fail(PB_ERR_INVALID, "%s: bad size (V=%d N=%d L=%d T=%d; 1 <= N <= L and 1 <= T <= L required)", name,
+                V, N, L, T);
+  if (pad_left < 0 || pad_left > L - N)
+    return fail(PB_ERR_INVALID, "%s: pad_left=%d outside [0, L - N] (N=%d L=%d)", name, pad_left, N, L);
+  if (ldx < N || ldo < N) return fail(PB_ERR_INVALID, "%s: leading dimension too small", name);
+  const int64_t nd = (int64_t)N + 2 * (int64_t)T - 1;        // window e[N + T - 1] and filter c[T]
+  if (nd > LDS_DOUBLES_MAX)
+    return fail(PB_ERR_INVALID, "%s: N=%d with T=%d filter taps exceeds LDS (N + 2 T - 1 = %lld > %d doubles)", name,
+                N, T, (long long)nd, LDS_DOUBLES_MAX);
+  if ((int64_t)V * pb::GEN_THREADS > (int64_t)UINT32_MAX) return fail(PB_ERR_INVALID, "%s: V=%d rows per launch", name, V);
+  if (V == 0) return PB_OK;
+  if (!x || !out || !map || !filt) return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
+  hipLaunchKernelGGL((pb::spectral_kernel<CORR>), dim3(V), dim3(pb::GEN_THREADS), (size_t)nd * sizeof(double),
+                     (hipStream_t)stream, x, ldx, out, ldo, N, map, L, pad_left, filt, T);
+  return check_launch(name);
+}
+
 }  // namespace
 
 namespace {
@@ -1471,6 +1492,14 @@ int pb_op_forward(const double* x, int64_t ldx, double* out, int64_t ldo, int V,
 int pb_op_adjoint(const double* r, int64_t ldr, double* out, int64_t ldo, int V, int n_in, int n_out,
                   const double* taps, int K, void* st) {
   return launch_op<pb::OP_ADJ>(r, ldr, out, ldo, V, n_out, n_in, taps, K, st, "pb_op_adjoint");
+}
+int pb_spectral_conv(const double* x, int64_t ldx, double* out, int64_t ldo, int V, int N, const int32_t* map,
+                     int L, int pad_left, const double* filt, int T, void* st) {
+  return launch_spectral<false>(x, ldx, out, ldo, V, N, map, L, pad_left, filt, T, st, "pb_spectral_conv");
+}
+int pb_spectral_corr(const double* x, int64_t ldx, double* out, int64_t ldo, int V, int N, const int32_t* map,
+                     int L, int pad_left, const double* filt, int T, void* st) {
+  return launch_spectral<true>(x, ldx, out, ldo, V, N, map, L, pad_left, filt, T, st, "pb_spectral_corr");
 }
 
 int pb_hrf_cost(const double* z_dev, int64_t ldz, const float* y_dev, int64_t ldy, int V, int N,

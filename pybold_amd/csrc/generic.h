@@ -65,14 +65,15 @@ __device__ __forceinline__ void block_cumsum(const double* src, double* dst, int
   __syncthreads();
 }
 
-// out[i] = sum_m k[m] in[i-m], 0 <= i-m < n_in, i in [0, n_out)   (toeplitz @ in)
+// out[i] = sum_m k[m] in[i+off-m], 0 <= i+off-m < n_in, i in [0, n_out)   (toeplitz @ in;
+// off > 0 reads the output from lag off on, as the spectral kernel does)
 __device__ __forceinline__ void block_conv(const double* in, int n_in, double* out, int n_out,
-                                           const double* k, int K) {
+                                           const double* k, int K, int off = 0) {
   for (int i = threadIdx.x; i < n_out; i += GEN_THREADS) {
-    const int m0 = max(0, i - n_in + 1);
-    const int m1 = min(K - 1, i);
+    const int m0 = max(0, i + off - n_in + 1);
+    const int m1 = min(K - 1, i + off);
     double acc = 0.0;
-    for (int m = m0; m <= m1; ++m) acc = fma(k[m], in[i - m], acc);
+    for (int m = m0; m <= m1; ++m) acc = fma(k[m], in[i + off - m], acc);
     out[i] = acc;
   }
   __syncthreads();
@@ -126,6 +127,37 @@ __global__ __launch_bounds__(GEN_THREADS) void op_kernel(const double* x, int64_
     block_cumsum<true>(b, b, n_dst, red);
   }
   for (int i = threadIdx.x; i < n_dst; i += GEN_THREADS) orow[i] = res[i];
+}
+
+// Spectral operators (pybold/convolution.py:9-102): a length-L circular convolution (CORR = false) or
+// correlation (CORR = true) of the padded row xp with T filter taps, read at the N unpadded positions
+//   out[i] = sum_{m<T} c[m] xp[(pad_left + i -/+ m) mod L],   xp[q] = x[map[q]] if 0 <= map[q] < N, else 0.
+// The window e[j] = xp[(base + j) mod L], j < N + T - 1, holds every sample the N outputs read, so the
+// FIR loops run on it unmasked: base = pad_left - (T - 1) for the convolution (output offset T - 1),
+// pad_left for the correlation.  LDS: e[N + T - 1] c[T]; the outputs go straight to global memory.
+template <bool CORR>
+__global__ __launch_bounds__(GEN_THREADS) void spectral_kernel(const double* x, int64_t ldx, double* out,
+                                                               int64_t ldo, int N, const int32_t* map,
+                                                               int L, int pad_left, const double* filt,
+                                                               int T) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int W = N + T - 1;
+  double* e = reinterpret_cast<double*>(smem);
+  double* c = e + W;
+  const double* xr = x + (int64_t)blockIdx.x * ldx;
+  double* orow = out + (int64_t)blockIdx.x * ldo;
+  const int64_t b = CORR ? (int64_t)pad_left : (int64_t)pad_left - (T - 1);
+  const unsigned base = (unsigned)(((b % L) + L) % L);
+  for (int j = threadIdx.x; j < W; j += GEN_THREADS) {
+    unsigned q = base + (unsigned)j;           // < 3 L: N <= L and T <= L (checked by the launcher)
+    while (q >= (unsigned)L) q -= (unsigned)L;
+    const int s = map[q];
+    e[j] = (s >= 0 && s < N) ? xr[s] : 0.0;
+  }
+  for (int i = threadIdx.x; i < T; i += GEN_THREADS) c[i] = filt[i];
+  __syncthreads();
+  if constexpr (CORR) block_corr(e, W, orow, N, c, T);
+  else block_conv(e, W, orow, N, c, T, T - 1);
 }
 
 // z = cumsum(w), x = k * z

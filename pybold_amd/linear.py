@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import solver
-from .convolution import toeplitz_from_kernel
+from .convolution import spectral_convolve, spectral_retro_convolve, toeplitz_from_kernel
 
 
 def _to_dev(x):
@@ -49,8 +49,8 @@ class ConvAndLinear:
     def __init__(self, M, kernel, dim_in, dim_out=None, spectral_conv=False):
         if spectral_conv:
             raise NotImplementedError(
-                "spectral_conv=True (FFT path, pybold/linear.py:88-89,108-109) is out "
-                "of scope; the solvers never use it")
+                "ConvAndLinear(spectral_conv=True) is not provided; the same operator "
+                "(pybold/linear.py:88-89,108-109) is SpectralConvAndLinear(M, kernel, dim_in)")
         self.M = M
         self.k = np.asarray(kernel, dtype=np.float64)
         self.spectral_conv = spectral_conv
@@ -81,3 +81,25 @@ class ConvAndLinear:
         if isinstance(self.M, DiscretInteg):
             return back(solver.op_adjoint(t, self.k, self.dim_in))
         return self.M.adj(back(solver.corr(t, self.k, self.dim_in)))
+
+
+class SpectralConvAndLinear:
+    """The spectral form of the reference's ``ConvAndLinear(M, kernel, dim_in, dim_out,
+    spectral_conv=True)`` (pybold/linear.py:88-89,108-109):
+    ``op(x) = spectral_convolve(kernel, M.op(x))`` and
+    ``adj(r) = M.adj(spectral_retro_convolve(kernel, r))``, the circular convolution
+    over the zeros-mirror-zeros padded series (convolution.py).  As in the reference,
+    the output has the input's length and ``dim_in`` / ``dim_out`` are not used.
+
+    ``ConvAndLinear`` itself still rejects ``spectral_conv=True`` (NotImplementedError
+    naming this class): the reference's spectral branch is this separate operator."""
+
+    def __init__(self, M, kernel, dim_in=None, dim_out=None):
+        self.M = M
+        self.k = np.asarray(kernel, dtype=np.float64)
+
+    def op(self, x):
+        return spectral_convolve(self.k, self.M.op(x))
+
+    def adj(self, x):
+        return self.M.adj(spectral_retro_convolve(self.k, x))

@@ -619,6 +619,26 @@ def corr(R, taps, dim_in=None):
     return _apply("pb_corr", R, R.shape[1] if dim_in is None else dim_in, taps)
 
 
+def spectral(X, index_map, pad_left, filt, corr=False):
+    """Length-L circular convolution (``corr=False``) or correlation of each row padded
+    through ``index_map`` (int32 [L], -1 = zero), read at ``[pad_left, pad_left + N)``:
+    the product of the reference's padded-FFT functions (convolution.py:9-102) with the
+    filter ``filt`` prepared by the caller (include/pybold_hip.h, pb_spectral_conv)."""
+    lib = _lib.load()
+    X = _rows(X, torch.float64, "x")
+    dev = X.device
+    V, N = X.shape
+    m = torch.from_numpy(np.ascontiguousarray(index_map, dtype=np.int32).ravel()).to(dev)
+    c = torch.from_numpy(np.ascontiguousarray(filt, dtype=np.float64).ravel()).to(dev)
+    out = torch.empty((V, N), dtype=torch.float64, device=dev)
+    name = "pb_spectral_corr" if corr else "pb_spectral_conv"
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(X.data_ptr(), _ld(X), out.data_ptr(), _ld(out), V, N, m.data_ptr(), m.numel(),
+                                int(pad_left), c.data_ptr(), c.numel(), _stream_ptr(dev))
+    _lib.check(rc, name)
+    return out
+
+
 def op_forward(X, taps, dim_out=None):
     """``ConvAndLinear(DiscretInteg(), taps, n_in, dim_out).op`` (linear.py:73-93)."""
     return _apply("pb_op_forward", X, X.shape[1] if dim_out is None else dim_out, taps)
