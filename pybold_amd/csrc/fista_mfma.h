@@ -46,9 +46,7 @@
 //
 // Reference: pybold/bold_signal.py:62-72, pybold/linear.py:73-113, pybold/convolution.py:105-132.
 #pragma once
-#include "../../include/pybold_hip.h"
-#include "common.h"
-#include "fista_fast.h"
+#include "mfma_core.h"
 #ifndef PB_MFMA_CHECKS
 #define PB_MFMA_CHECKS 1
 #endif
@@ -75,90 +73,11 @@
 #ifndef PB_MFMA_FETCH_SLOT
 #define PB_MFMA_FETCH_SLOT 8
 #endif
-#ifndef PB_MFMA_CHECKS
-#define PB_MFMA_CHECKS 1
-#endif
 
 namespace pb {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-typedef unsigned u3 __attribute__((ext_vector_type(3)));
-
-constexpr float MFMA_RHO_MAX = 0.02f;
 constexpr int MFMA_SPAN = 31;       // samples per block of 32 slots; slot 31 (lane group 3, j = 7) is the block's sum slot
 constexpr int MFMA_SSHIFT = 9;      // the sums ride scaled by 2^-9: below the largest sample for up to 512 of them
-
-struct MfmaTaps {
-  float c[96];      // 2^a * cumsum(h)[m], m < 96 (constant from m = K-1 on; K <= 33 uses 64 of them)
-  double g_scale;   // 2^(-2a): the gradient comes out scaled by 2^(2a)
-  float y_scale;    // 2^a
-};
-
-inline MfmaTaps make_mfma_taps(const double* taps, int K) {
-  MfmaTaps t;
-  double c[96], run = 0.0, cmax = 0.0;
-  for (int m = 0; m < 96; ++m) {
-    if (m < K) run += (double)(float)taps[m];
-    c[m] = run;
-    cmax = fabs(run) > cmax ? fabs(run) : cmax;
-  }
-  int e = 0;
-  if (cmax > 0.0) frexp(cmax, &e);          // cmax = f 2^e, f in [0.5, 1)
-  const int a = 3 - e;                       // max |c| 2^a in [4, 8)
-  for (int m = 0; m < 96; ++m) t.c[m] = (float)ldexp(c[m], a);
-  t.g_scale = ldexp(1.0, -2 * a);
-  t.y_scale = (float)ldexp(1.0, a);
-  return t;
-}
-
-struct Frag {
-  h8 hi, lo;
-};
-
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-// two float32 -> packed float16, round to nearest even (v_cvt_pk_f16_f32).  The LOW parts are
-// rounded, not truncated: a truncated split shrinks every operand by ~2^-23 on average, a bias
-// that adds up coherently over samples and iterations (measured: 14x the error of float32
-// operators along a regularisation path, tools/r3_mfma_precision.py).
-__device__ __forceinline__ unsigned pk_rne(float x0, float x1) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f2v{x0, x1}, h2));
-}
-
-// (x0, x1) -> packed hi = RTZ(x) and packed lo = RNE(x - hi); x - hi is exact in float32.
-// (v_fma_mixlo_f16 + v_fma_mixhi_f16 would write the rounded differences straight into the two
-// halves -- one instruction less per pair, 96 fewer per iteration -- and measured 4.5 % SLOWER:
-// profiles/r3_mfma_split_mixlo_ab.txt; the partial-register writes serialise.)
-__device__ __forceinline__ void split_pair(float x0, float x1, unsigned& hi, unsigned& lo) {
-  hi = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x0, x1));
-  float l0, l1;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hi), "v"(x0));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hi), "v"(x1));
-  lo = pk_rne(l0, l1);
-}
-
-// eight float32 -> float16 hi / lo parts (hi = RTZ(x), lo = RNE(x - hi): 22 bits, unbiased)
-__device__ __forceinline__ Frag split8(const float (&x)[8]) {
-  u4 ph, pl;
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    unsigned h2, l2;
-    split_pair(x[2 * p], x[2 * p + 1], h2, l2);
-    ph[p] = h2;
-    pl[p] = l2;
-  }
-  return Frag{__builtin_bit_cast(h8, ph), __builtin_bit_cast(h8, pl)};
-}
-
-// acc += (Ahi + Alo) (Bhi + Blo) without the lo.lo term
-__device__ __forceinline__ f4 mma3(const Frag& A, const Frag& B, f4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(A.hi, B.hi, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(A.hi, B.lo, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(A.lo, B.hi, acc, 0, 0, 0);
-  return acc;
-}
 
 // NB blocks of 31 samples + one sum slot per series, 31 (NB - 1) < N <= 31 NB (only the last block can hold
 // padding), HRFs of up to 33 taps (NT = 2 near tiles) or 64 taps (NT = 3: one more near tile per block and
@@ -214,13 +133,10 @@ __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs
 #pragma unroll
     for (int q = 0; q < 7; ++q) lt[q * 256] = 0.0f;
   }
-  auto wave_sync = [] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
 
   // ---- cumulative taps c[m] = sum_{k <= min(m, K-1)} h[k], scaled by 2^a so that max |c| is in [4, 8) ----
+  // (This prologue and the series scale below are restated in the three kernels: as shared functions, in every shape
+  // tried, they change the register counts of some variant -- DESIGN 5.)
   double step = a.step, g_scale = tp.g_scale;
   float y_scale = tp.y_scale;
   if constexpr (TAPS_DEV) {
@@ -311,8 +227,7 @@ __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs
         ysn[q][j] = yv;
         m = fmaxf(m, fabsf(yv));
       }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    m = group_max(m);
     {                                            // (branch-free too)
       const bool okm = m > 0.0f && m < 3.0e38f;
       int e = 0;
@@ -373,10 +288,11 @@ __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs
   float jw2 = 0.0f, cvsq = 0.0f;                 // this lane's ||w||^2 part, its v^2
   bool cflag = false;
   int cert_it = -1;
-  constexpr float CP1 = 0.3133f, CP2 = 0.6467f, CP3 = 0.04f;
-  const float cert_t2 = ((float)a.tol * 1.001f) * ((float)a.tol * 1.001f);
-  const float cert_c0 = (float)th * (4.0f * 1.0001f) * __builtin_sqrtf(32.0f * NB) + 3.1e-10f * sigma;
-  const float cert_lim = cert_t2 * cert_c0 * cert_c0 * (1.0001f / CP3);
+  float cert_t2 = 0.0f, cert_lim = 0.0f;
+  if constexpr (CERT) {
+    cert_t2 = cert_tol2(a.tol);
+    cert_lim = cert_limit(cert_t2, th, sigma, NB);
+  }
 
   // Register placement: the operator tiles are read by matrix instructions only and -y'' once per
   // iteration: they live in the accumulator half of the register file (the asm constraints put
@@ -397,25 +313,7 @@ __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs
   // (data dependences keep the order; PB_MFMA_SB can pin it): every matrix instruction of block q is
   // followed by a slice of the vector work of its neighbours -- the float16 fragments of block
   // q+1, the residual (or the update) of the block before.
-  auto mfma_part = [](const Frag& A, const Frag& B, f4 acc, int part) __attribute__((always_inline)) -> f4 {
-    // the three products of a split pair, one per call: hi.hi, hi.lo, lo.hi
-#ifdef PB_MFMA_LOLO
-    if (part == 2) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(A.lo, B.lo, acc, 0, 0, 0);
-#endif
-    return part == 0   ? __builtin_amdgcn_mfma_f32_16x16x32_f16(A.hi, B.hi, acc, 0, 0, 0)
-           : part == 1 ? __builtin_amdgcn_mfma_f32_16x16x32_f16(A.hi, B.lo, acc, 0, 0, 0)
-                       : __builtin_amdgcn_mfma_f32_16x16x32_f16(A.lo, B.hi, acc, 0, 0, 0);
-  };
   Frag rlast;                                    // residual fragment of the last block, forward pass -> adjoint pass
-  // two float32 -> float16 hi / lo as split_pair, and what the split drops of x1: rem = x1 - hi - lo (exact)
-  auto split_pair_rem = [](float x0, float x1, unsigned& hi, unsigned& lo, float& rem) __attribute__((always_inline)) {
-    hi = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x0, x1));
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hi), "v"(x0));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hi), "v"(x1));
-    lo = pk_rne(l0, l1);
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rem) : "v"(lo), "v"(l1));
-  };
   // slot order of the 6 NT products of a block: row half r = 1 - (slot & 1) (the half that holds the sum row finishes
   // one slot before the end), tile o = NT-1 ... 0 (the block's own fragment last), the three split products in turn
   // ---- forward: r = T_c w - y, block by block (ascending); fragments of r go to LDS -------------
@@ -541,14 +439,8 @@ __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs
     };
     auto update = [&](auto qc, auto jc) {
       constexpr int q = decltype(qc)::value, j = decltype(jc)::value;
-      const double gj = (double)acc[q][j >> 2][j & 3];
-      const double u = fma(j == 7 ? nstep7 : nstep, gj, w[q][j]);
-      const double d = fmin(fmax(u, -th), th);
-      w[q][j] = fma(nb1, d, u);
-      if constexpr (LOOPS) {
-        if constexpr ((j & 1) == 0) { ldsq0 = fma(d, d, ldsq0); lwsq0 = fma(w[q][j], w[q][j], lwsq0); }
-        else { ldsq1 = fma(d, d, ldsq1); lwsq1 = fma(w[q][j], w[q][j], lwsq1); }
-      }
+      const double u = fista_update<LOOPS>(w[q][j], acc[q][j >> 2][j & 3], j == 7 ? nstep7 : nstep, th, nb1,
+                                           (j & 1) ? ldsq1 : ldsq0, (j & 1) ? lwsq1 : lwsq0);
       if constexpr (CERT && j == 3 && (q == CQ0 || q == CQ1 || q == CQ2 || q == CQ3)) {
         constexpr int gq = q == CQ0 ? 0 : (q == CQ1 ? 1 : (q == CQ2 ? 2 : 3));
         cu = (g == gq) ? u : cu;
@@ -590,46 +482,15 @@ __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs
       });
     });
     static_for<0, 8>([&](auto jc) { update(std::integral_constant<int, 0>{}, jc); });
-    if constexpr (CERT) {
-      // the window combination on this lane's tracked sample (see fista_pair_ffa.h): float32 from
-      // float64 differences; its rounding, and that of the stored increments, is below 2^-21 M
-      const float d1 = lt[((cert_it + 3) & 3) * 256], d2 = lt[((cert_it + 2) & 3) * 256], d3 = lt[((cert_it + 1) & 3) * 256];
-      const unsigned ulo = __builtin_bit_cast(unsigned, lt[4 * 256]), uhi = __builtin_bit_cast(unsigned, lt[5 * 256]);
-      const double up = __builtin_bit_cast(double, ((unsigned long long)uhi << 32) | ulo);
-      const float dk = (float)(cu - up), e = (float)(cw - cu);
-      const float v = fmaf(2.0f, d2, fmaf(3.0f, d1, fmaf(2.0f, dk, e))) + d3;
-      const float m = fmaf(2.0f, fabsf(d2), fmaf(3.0f, fabsf(d1), fmaf(2.0f, fabsf(dk), fabsf(e)))) + fabsf(d3);
-      const float vs = fmaxf(fmaf(-0x1p-21f, m, fabsf(v)), 0.0f);
-      cvsq = vs * vs;
-      lt[(cert_it & 3) * 256] = dk;
-      const unsigned long long ub = __builtin_bit_cast(unsigned long long, cu);
-      lt[4 * 256] = __builtin_bit_cast(float, (unsigned)ub);
-      lt[5 * 256] = __builtin_bit_cast(float, (unsigned)(ub >> 32));
-    }
+    if constexpr (CERT) cvsq = cert_window<256>(lt, cert_it, cu, cw);
   };
   // Range guard, every 8th iteration and after the last one: the largest |sigma w| (registers) and
   // the largest exponent among the hi halves of the residual fragments (LDS copy) -- a small block
   // of its own, so that the iteration body exists once.
   auto range_check = [&]() {
-    unsigned mb = 0;                              // largest |sigma w| by its float32 bits: NaN and inf rank highest
-#pragma unroll
-    for (int q = 0; q < NB; ++q)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) mb = max(mb, __builtin_bit_cast(unsigned, (float)w[q][j]) & 0x7fffffffu);
-    const float m = mb >= 0x7f800000u ? 65504.0f : __builtin_bit_cast(float, mb);
+    const float m = iterate_absmax<NB>(w);
     wlast = m;
-    unsigned e = 0;
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const u4 h = lrf[(2 * q) * 64];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        e = max(e, h[c] & 0x7fffu);
-        e = max(e, (h[c] >> 16) & 0x7fffu);
-      }
-    }
-    // float16 bits of |hi|: 0x7800 = 32768
-    guard = __builtin_fmaxf(guard, __builtin_fmaxf(m, e >= 0x7800u ? 65504.0f : 0.0f));
+    guard = __builtin_fmaxf(guard, __builtin_fmaxf(m, residual_guard<NB>(lrf)));
   };
 
   if constexpr (!WITH_J) {
@@ -640,20 +501,13 @@ __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs
       backward(beta);
       if constexpr (LOOPS) {
         double num = ldsq0 + ldsq1, den = lwsq0 + lwsq1;     // this lane's 8 NB slots -> the problem's 32 NB
-        num += __shfl_xor(num, 16, 64);
-        den += __shfl_xor(den, 16, 64);
-        num += __shfl_xor(num, 32, 64);
-        den += __shfl_xor(den, 32, 64);
+        group_sum2(num, den);
         // ||w' - u|| = (1 + beta) ||d||; everything lives at the scale sigma, and so does the reference's 1e-10 floor
         const bool fire = lactive && it >= 3 &&
                           (1.0 + beta) * sqrt(num) / (sqrt(den) + 1.0e-10 * (double)sigma) < a.tol;
         if (__builtin_amdgcn_ballot_w64(fire) != 0) {         // (rare: at most once per problem)
           range_check();                                      // this moment's operands, for the problems that finish now
-          float gq = guard, wq = wlast;
-          gq = fmaxf(gq, __shfl_xor(gq, 16, 64));
-          gq = fmaxf(gq, __shfl_xor(gq, 32, 64));
-          wq = fmaxf(wq, __shfl_xor(wq, 16, 64));
-          wq = fmaxf(wq, __shfl_xor(wq, 32, 64));
+          const float gq = group_max(guard), wq = group_max(wlast);
           const bool badq = !(gq < 60000.0f) || (a.rho_guard && wq > 0.0f && (float)th > MFMA_RHO_MAX * wq) || degenerate;
           if (fire) {
             lactive = false;
@@ -689,29 +543,20 @@ __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs
       backward(beta);
       forward();
       float sq = jsq, l1 = jl1;                   // this lane's 8 NB slots -> the problem's 32 NB
-      sq += __shfl_xor(sq, 16, 64);
-      l1 += __shfl_xor(l1, 16, 64);
-      sq += __shfl_xor(sq, 32, 64);
-      l1 += __shfl_xor(l1, 32, 64);
+      group_sum2(sq, l1);
       if (live && g == 0 && (!CERT || (a.J != nullptr && !cflag))) a.J[(int64_t)p * a.ldj + it] = fmaf(jq, sq, jl * l1);
       if constexpr (CERT) {
-        // close the certificate of iteration `it` (the rule is first tested at wind + 1 = 7):
-        // sum over the problem's four lanes of v^2 - tol^2 (||w_k||^2 / p1 + 4 ||w_{k+1}||^2 / p2)
-        float t = cvsq - cert_t2 * ((1.0001f / CP1) * lt[6 * 256] + (4.0001f / CP2) * jw2);
-        t += __shfl_xor(t, 16, 64);
-        t += __shfl_xor(t, 32, 64);
+        // close the certificate of iteration `it`: the sum over the problem's four lanes
+        const float t = cert_term<256>(lt, cvsq, cert_t2, jw2);
         cflag = cflag | ((it >= 7) & !(t >= cert_lim));      // NaN-safe: anything unclear is flagged
-        lt[6 * 256] = jw2;
       }
       if (PB_MFMA_CHECKS && (((it & 7) == 7) || (it == a.n_iter - 1) || (it == 0 && !a.cold))) range_check();
     }
   }
 
   // ---- store (unscaled); a problem that came near the float16 range is handed back ----------
-  guard = fmaxf(guard, __shfl_xor(guard, 16, 64));
-  guard = fmaxf(guard, __shfl_xor(guard, 32, 64));
-  wlast = fmaxf(wlast, __shfl_xor(wlast, 16, 64));
-  wlast = fmaxf(wlast, __shfl_xor(wlast, 32, 64));
+  guard = group_max(guard);
+  wlast = group_max(wlast);
   // Accuracy guard.  An error eps in the gradient moves an entry of the solution by ~eps th, so the
   // relative error of a solution grows like th / max|w| -- for every arithmetic; the 22-bit operands
   // here start 8x above float32 operators.  Measured along regularisation paths

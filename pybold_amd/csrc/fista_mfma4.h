@@ -78,18 +78,8 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
 #pragma unroll
     for (int q = 0; q < 7; ++q) lt[q * 256] = 0.0f;
   }
-  auto wave_sync = [] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  auto wg_sync = [] {                                // all waves: everything written to LDS before is visible after
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  };
 
-  // ---- cumulative taps (as fista_mfma.h) ------------------------------------------------------------------------------
+  // ---- cumulative taps (as fista_mfma.h; restated in the three kernels: DESIGN 5) ----
   double step = a.step, g_scale = tp.g_scale;
   float y_scale = tp.y_scale;
   if constexpr (TAPS_DEV) {
@@ -172,8 +162,7 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
         ysn[q][j] = yv;
         m = fmaxf(m, fabsf(yv));
       }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    m = group_max(m);
     xm[k * 64] = m;
     wg_sync();
     m = fmaxf(fmaxf(xm[0], xm[64]), fmaxf(xm[128], xm[192]));
@@ -225,10 +214,11 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
   float jw2 = 0.0f, cvsq = 0.0f;
   bool cflag = false;
   int cert_it = -1;
-  constexpr float CP1 = 0.3133f, CP2 = 0.6467f, CP3 = 0.04f;
-  const float cert_t2 = ((float)a.tol * 1.001f) * ((float)a.tol * 1.001f);
-  const float cert_c0 = (float)th * (4.0f * 1.0001f) * __builtin_sqrtf(32.0f * NBT) + 3.1e-10f * sigma;
-  const float cert_lim = cert_t2 * cert_c0 * cert_c0 * (1.0001f / CP3);
+  float cert_t2 = 0.0f, cert_lim = 0.0f;
+  if constexpr (CERT) {
+    cert_t2 = cert_tol2(a.tol);
+    cert_lim = cert_limit(cert_t2, th, sigma, NBT);
+  }
 
 #pragma unroll
   for (int r = 0; r < 2; ++r)
@@ -241,11 +231,6 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
 #pragma unroll
     for (int j = 0; j < 8; ++j) asm volatile("" : "+a"(ysn[q][j]));
 
-  auto mfma_part = [](const Frag& A, const Frag& B, f4 acc, int part) __attribute__((always_inline)) -> f4 {
-    return part == 0   ? __builtin_amdgcn_mfma_f32_16x16x32_f16(A.hi, B.hi, acc, 0, 0, 0)
-           : part == 1 ? __builtin_amdgcn_mfma_f32_16x16x32_f16(A.hi, B.lo, acc, 0, 0, 0)
-                       : __builtin_amdgcn_mfma_f32_16x16x32_f16(A.lo, B.hi, acc, 0, 0, 0);
-  };
   // what the right neighbour needs of the current iterate -- the fragments of this wave's last NX blocks (x = 0: the last) ...
   auto publish_block = [&](auto xc_) {
     constexpr int x = decltype(xc_)::value;
@@ -404,14 +389,8 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
     };
     auto update = [&](auto qc, auto jc) {
       constexpr int q = decltype(qc)::value, j = decltype(jc)::value;
-      const double gj = (double)acc[q][j >> 2][j & 3];
-      const double u = fma(nstep, gj, w[q][j]);
-      const double d = fmin(fmax(u, -th), th);
-      w[q][j] = fma(nb1, d, u);
-      if constexpr (LOOPS) {
-        if constexpr ((j & 1) == 0) { ldsq0 = fma(d, d, ldsq0); lwsq0 = fma(w[q][j], w[q][j], lwsq0); }
-        else { ldsq1 = fma(d, d, ldsq1); lwsq1 = fma(w[q][j], w[q][j], lwsq1); }
-      }
+      const double u = fista_update<LOOPS>(w[q][j], acc[q][j >> 2][j & 3], nstep, th, nb1, (j & 1) ? ldsq1 : ldsq0,
+                                           (j & 1) ? lwsq1 : lwsq0);
       if constexpr (HAS_R) {
         if constexpr (q >= NBW - NX) suml += w[q][j];
         else if constexpr ((j & 1) == 0) sum0 += w[q][j];
@@ -450,40 +429,12 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
     });
     static_for<0, 8>([&](auto jc) { update(std::integral_constant<int, 0>{}, jc); });
     if constexpr (HAS_R) publish_sums(sum0 + sum1, suml);
-    if constexpr (CERT) {                          // the window combination on this lane's tracked sample (fista_mfma.h)
-      const float d1 = lt[((cert_it + 3) & 3) * 256], d2 = lt[((cert_it + 2) & 3) * 256], d3 = lt[((cert_it + 1) & 3) * 256];
-      const unsigned ulo = __builtin_bit_cast(unsigned, lt[4 * 256]), uhi = __builtin_bit_cast(unsigned, lt[5 * 256]);
-      const double up = __builtin_bit_cast(double, ((unsigned long long)uhi << 32) | ulo);
-      const float dk = (float)(cu - up), e = (float)(cw - cu);
-      const float vv = fmaf(2.0f, d2, fmaf(3.0f, d1, fmaf(2.0f, dk, e))) + d3;
-      const float mm = fmaf(2.0f, fabsf(d2), fmaf(3.0f, fabsf(d1), fmaf(2.0f, fabsf(dk), fabsf(e)))) + fabsf(d3);
-      const float vs = fmaxf(fmaf(-0x1p-21f, mm, fabsf(vv)), 0.0f);
-      cvsq = vs * vs;
-      lt[(cert_it & 3) * 256] = dk;
-      const unsigned long long ub = __builtin_bit_cast(unsigned long long, cu);
-      lt[4 * 256] = __builtin_bit_cast(float, (unsigned)ub);
-      lt[5 * 256] = __builtin_bit_cast(float, (unsigned)(ub >> 32));
-    }
+    if constexpr (CERT) cvsq = cert_window<256>(lt, cert_it, cu, cw);
   };
   auto range_check = [&]() {
-    unsigned mb = 0;
-#pragma unroll
-    for (int q = 0; q < NBW; ++q)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) mb = max(mb, __builtin_bit_cast(unsigned, (float)w[q][j]) & 0x7fffffffu);
-    const float m = mb >= 0x7f800000u ? 65504.0f : __builtin_bit_cast(float, mb);
+    const float m = iterate_absmax<NBW>(w);
     wlast = m;
-    unsigned e = 0;
-#pragma unroll
-    for (int q = 0; q < NBW; ++q) {
-      const u4 h = lrf[(2 * q) * 64];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        e = max(e, h[c] & 0x7fffu);
-        e = max(e, (h[c] >> 16) & 0x7fffu);
-      }
-    }
-    guard = __builtin_fmaxf(guard, __builtin_fmaxf(m, e >= 0x7800u ? 65504.0f : 0.0f));
+    guard = __builtin_fmaxf(guard, __builtin_fmaxf(m, residual_guard<NBW>(lrf)));
   };
 
   // ---- iterations: both passes in all waves at once, one barrier per phase boundary -----------------------------------
@@ -509,7 +460,7 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
       if constexpr (LOOPS) { ldsq0 = ldsq1 = lwsq0 = lwsq1 = 0.0; }
       backward(beta);
       if constexpr (LOOPS) {                       // this wave's share of the rule's two norms (fista_mfma.h)
-        double num = ldsq0 + ldsq1, den = lwsq0 + lwsq1;
+        double num = ldsq0 + ldsq1, den = lwsq0 + lwsq1;     // (reductions spelled out: fista_mfma2.h says why)
         num += __shfl_xor(num, 16, 64);
         den += __shfl_xor(den, 16, 64);
         num += __shfl_xor(num, 32, 64);
@@ -523,10 +474,7 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
         // every wave adds the shares in the same order: the same verdict everywhere (the branches below are workgroup-uniform)
         const double num = (xl[0 * 64] + xl[2 * 64]) + (xl[4 * 64] + xl[6 * 64]);
         const double den = (xl[1 * 64] + xl[3 * 64]) + (xl[5 * 64] + xl[7 * 64]);
-        // (the criterion in EVERY lane, pinned: under `lactive &&` the compiler evaluated it in an exec-masked region and
-        // parked live registers in accumulator registers there -- the pattern tools/isa_spill_lint.py refuses)
-        double crit = (1.0 + beta) * sqrt(num) / (sqrt(den) + 1.0e-10 * (double)sigma);
-        asm volatile("" : "+v"(crit));
+        const double crit = loops_criterion(beta, num, den, sigma);
         const bool fire = lactive && it >= 3 && crit < a.tol;
         if (__builtin_amdgcn_ballot_w64(fire) != 0) {         // (rare: at most once per problem)
           range_check();                                      // this moment's operands, for the problems that finish now
@@ -578,17 +526,10 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
       wg_sync();
       forward();
       float sq = jsq, l1 = jl1;                     // this lane's samples -> this wave's share of the problem
-      sq += __shfl_xor(sq, 16, 64);
-      l1 += __shfl_xor(l1, 16, 64);
-      sq += __shfl_xor(sq, 32, 64);
-      l1 += __shfl_xor(l1, 32, 64);
+      group_sum2(sq, l1);
       float t = 0.0f;
       if constexpr (CERT) {
-        // this share's part of  sum v^2 - tol^2 (||w_k||^2 / p1 + 4 ||w_{k+1}||^2 / p2)
-        t = cvsq - cert_t2 * ((1.0001f / CP1) * lt[6 * 256] + (4.0001f / CP2) * jw2);
-        t += __shfl_xor(t, 16, 64);
-        t += __shfl_xor(t, 32, 64);
-        lt[6 * 256] = jw2;
+        t = cert_term<256>(lt, cvsq, cert_t2, jw2);
       }
       xj[(k * 3 + 0) * 64] = sq;
       xj[(k * 3 + 1) * 64] = l1;
@@ -607,10 +548,8 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
   }
 
   // ---- guards over the whole series, store ---------------------------------------------------------------------------
-  guard = fmaxf(guard, __shfl_xor(guard, 16, 64));
-  guard = fmaxf(guard, __shfl_xor(guard, 32, 64));
-  wlast = fmaxf(wlast, __shfl_xor(wlast, 16, 64));
-  wlast = fmaxf(wlast, __shfl_xor(wlast, 32, 64));
+  guard = group_max(guard);
+  wlast = group_max(wlast);
   xg[(k * 2 + 0) * 64] = guard;
   xg[(k * 2 + 1) * 64] = wlast;
   wg_sync();

@@ -33,34 +33,41 @@ def listing(path):
 
 
 SPAN = 300
-bad = 0
-for path in sys.argv[1:]:
-    kernel, stack, hits = None, [], {}
-    for n, line in enumerate(listing(path), 1):
-        s = line.strip()
-        m = re.match(r"^(?:[0-9a-f]+ <)?(_ZN2pb\w+)>?:", s)
-        if m:
-            kernel, stack = m.group(1), []
-            continue
-        if kernel is None:
-            continue
-        if s.startswith("s_endpgm"):
-            kernel = None
-            continue
-        if re.match(r"s_and_saveexec_b64", s):
-            stack.append(n)
-        elif re.match(r"s_or_saveexec_b64|s_andn2_saveexec_b64", s):   # the else-part of the region on top: same level
-            if stack:
-                stack[-1] = n
-            else:
+
+
+def main(paths):
+    bad = 0
+    for path in paths:
+        kernel, stack, hits = None, [], {}
+        for n, line in enumerate(listing(path), 1):
+            s = line.strip()
+            m = re.match(r"^(?:[0-9a-f]+ <)?(_ZN2pb\w+)>?:", s)
+            if m:
+                kernel, stack = m.group(1), []
+                continue
+            if kernel is None:
+                continue
+            if s.startswith("s_endpgm"):
+                kernel = None
+                continue
+            if re.match(r"s_and_saveexec_b64", s):
                 stack.append(n)
-        elif re.match(r"s_or_b64 exec, exec,", s) or re.match(r"s_mov_b64 exec,", s):
-            if stack:
-                stack.pop()
-        elif stack and n - stack[-1] < SPAN and s.startswith("v_accvgpr_write_b32"):
-            hits.setdefault(kernel, []).append(n)
-    for k, lines in hits.items():
-        bad += 1
-        print("%s: %s: %d accumulator-register writes inside an exec-masked region (lines %s ...)" % (path, k[:90], len(lines), lines[:4]))
-print("%d kernel(s) with accumulator-register writes under a partial exec mask" % bad)
-sys.exit(1 if bad else 0)
+            elif re.match(r"s_or_saveexec_b64|s_andn2_saveexec_b64", s):   # the else-part of the region on top: same level
+                if stack:
+                    stack[-1] = n
+                else:
+                    stack.append(n)
+            elif re.match(r"s_or_b64 exec, exec,", s) or re.match(r"s_mov_b64 exec,", s):
+                if stack:
+                    stack.pop()
+            elif stack and n - stack[-1] < SPAN and s.startswith("v_accvgpr_write_b32"):
+                hits.setdefault(kernel, []).append(n)
+        for k, lines in hits.items():
+            bad += 1
+            print("%s: %s: %d accumulator-register writes inside an exec-masked region (lines %s ...)" % (path, k[:90], len(lines), lines[:4]))
+    print("%d kernel(s) with accumulator-register writes under a partial exec mask" % bad)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
