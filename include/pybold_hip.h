@@ -178,6 +178,7 @@ int pb_fista_plan_ex(int N, int K, int P, int stop_mode, int wind, unsigned flag
  *   311 .. 640   34 .. 48  (b)                  (b) certificate          (b) in full           ... with three near tiles
  *   641 .. 1280  <= 33     (b)                  (b) certificate          (b) in full           fista_mfma4_kernel, four waves per 16 problems
  *   641 .. 1280  34 .. 48  (b)                  (b) certificate          (b) in full           ... with three near tiles
+ *   <= 640       <= 32     the noise-driven lambda search (deconv with lbda = None), wind 6, float64 end to end:        auto_lbda_kernel, one voxel per wave (pb_auto_lbda_d)
  *   longer series, longer HRFs, other windows, a cost trace beside the _loops_deconv rule: (a), one problem per wave up to
  *   2 432 scans, the LDS kernel beyond (and for the window rule beyond 1 280 scans, for 34+ taps beyond 1 280).  Per-problem HRFs (pb_fista_solve_pp, ldt != 0): (a).  A machine-filling batch that lands
  *   on (a) although (b) serves neighbouring shapes is 1.5 .. 4x below the matrix-pipe rate; the Python layer says so once.
@@ -487,6 +488,62 @@ int pb_lambda_max(const float* y_dev, int64_t ldy, int V, int N, const double* t
                   double* out_dev, void* stream);
 int pb_lambda_max_d(const double* y_dev, int64_t ldy, int V, int N, const double* taps_dev, int K,
                     double* out_dev, void* stream);
+
+/*
+ * The noise-driven lambda search of deconv (lbda = None: the reference's DEFAULT call, pybold/bold_signal.py:99-214)
+ * as one device-resident solve: one voxel per wave64 (auto_lbda_kernel, csrc/fista_auto.h), float64 end to end, no
+ * host round trip between outer iterations.  Per voxel, as oracle/pybold_oracle.py::deconv_auto_lbda states the branch:
+ *   alpha = 1, lbda = 1 / (2 alpha), mu = 1e-4                                                       (:104-106)
+ *   for i < nb_iter:  inner solve from w (momentum restarted, <= nb_sub_iter iterations of the recurrence of
+ *                     pb_fista_solve_d, threshold lbda * step, window rule wind = 6 when early_stopping)   (:114-138)
+ *                     r = ||h * cumsum(w) - y||^2, g = ||w||_1; alpha += mu (r - N sigma^2); lbda = 1 / (2 alpha);
+ *                     J_i = 0.5 r + lbda g -- products and sums rounded one by one, as NumPy's          (:141-157)
+ *                     early_stopping and i > wind: stop when the means of the older and the newer half of the last
+ *                     six alphas differ by less than tol, relative; the voxel keeps its iterate and lambda (:164-178)
+ *   one more inner solve with the last lambda                                                         (:181-209)
+ * lambda goes NEGATIVE in the reference's own runs: the prox and the suffix scan are those of pb_fista_solve_d.
+ *
+ * pb_auto_lbda_supported  1 if the search runs for (N scans, K taps, wind): N <= 640, K <= 32, wind = 6; else 0.
+ *                         Host-only query.
+ * pb_auto_lbda_work_len   float64 entries of work_dev for V voxels (the state of the search between launches).
+ * pb_auto_lbda_d
+ *   y_dev        float64 [V][ldy]         w_dev   float64 [V][ldw]: in = warm start unless cold != 0, out = diff_z
+ *   taps_host    float64 [K], host        step    1 / (0.9 rho) (:52-53)
+ *   betas_dev    float64 [nb_sub_iter]: the momentum factors of ONE inner solve (every inner solve restarts them)
+ *   sigma_dev    float64 [V]: noise level of every voxel (:103; pb_mad_daub_noise_est_d, or the caller's own)
+ *   R_dev, G_dev, J_dev   optional float64 [V][ldt], ldt >= nb_iter: r, g and J_i of every outer iteration a voxel
+ *                ran; entries from n_outer on are left untouched
+ *   alpha_dev, lbda_dev   float64 [V]: final alpha and lambda           n_outer_dev  int32 [V]: outer iterations run
+ *   n_inner_dev  int64 [V]: inner iterations run, the final solve included (any of the four may be NULL)
+ *   work_dev     float64 [work_len], work_len >= pb_auto_lbda_work_len(V); contents meaningless afterwards
+ * BOUNDED LAUNCHES.  A voxel may need nb_iter * nb_sub_iter inner iterations, so the call enqueues
+ * ceil(nb_iter / outer_chunk) launches of outer_chunk outer iterations each -- a wave whose voxel has left the search
+ * exits at once -- and one launch for the final solve, all on `stream`, no host synchronisation (capturable).
+ * outer_chunk = 0: the library chooses max(1, 65536 / (nb_sub_iter * ceil(V / 2048))), i.e. about 65536 inner
+ * iterations per wave slot and launch.  The chunking changes no bit of any output.
+ * Errors (nothing is launched): wind != 6, N > 640, K > 32, nb_iter < 1, NULL pointers, a workspace too small.
+ */
+int pb_auto_lbda_supported(int N, int K, int wind);
+int64_t pb_auto_lbda_work_len(int V);
+int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                   const double* taps_host, int K, double step, const double* betas_dev,
+                   const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter,
+                   int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldt,
+                   double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev,
+                   double* work_dev, int64_t work_len, void* stream);
+
+/*
+ * sigma[v] = MAD of the level-1 db3 detail band of row v, divided by c (mad_daub_noise_est, pybold/utils.py:10-25;
+ * c = 0.6744 there): cD[k] = sum_j g[j] xe[2k + 1 - j] on the row with half-sample symmetric extension,
+ * (N + 5) / 2 coefficients, then median(|cD - median(cD)|) / c, the median of an even count being the mean of the
+ * middle two.  Same operations in the same order as pybold_amd/utils.py::mad_daub_noise_est (the detail band is
+ * computed in the package, not by PyWavelets: that parity is unpinned).  5 <= N <= 8192; one workgroup per row.
+ * pb_mad_daub_noise_est reads float32 rows and widens them on load.
+ */
+int pb_mad_daub_noise_est(const float* y_dev, int64_t ldy, int V, int N, double c, double* sigma_dev,
+                          void* stream);
+int pb_mad_daub_noise_est_d(const double* y_dev, int64_t ldy, int V, int N, double c, double* sigma_dev,
+                            void* stream);
 
 /*
  * Row-wise inf-norm normalisation out = x / (max|x| + 1e-12) (inf_norm,

@@ -5,7 +5,7 @@ Importing the package does not touch the GPU; the HIP library is loaded on
 first use and its absence is an error (there is no CPU fallback).
 """
 from . import _lib  # noqa: F401
-from .bold_signal import _loops_deconv, bd, deconv, hrf_estim, hrf_fit_err  # noqa: F401
+from .bold_signal import _loops_deconv, bd, deconv, deconv_auto, hrf_estim, hrf_fit_err  # noqa: F401
 from .convolution import (kernel_from_toeplitz, simple_convolve, simple_retro_convolve,  # noqa: F401
                           spectral_convolve, spectral_deconvolve, spectral_matches_causal,
                           spectral_retro_convolve, spectral_retro_deconvolve, toeplitz_from_kernel)

@@ -136,6 +136,17 @@ SIGNATURES = {
                                   _c_int, _c_int, _ptr, _ptr]),
     "pb_lambda_max": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr]),
     "pb_lambda_max_d": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr]),
+    "pb_auto_lbda_supported": (_c_int, [_c_int, _c_int, _c_int]),
+    "pb_auto_lbda_work_len": (_c_i64, [_c_int]),
+    "pb_auto_lbda_d": (_c_int, [
+        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,     # y_dev, ldy, w_dev, ldw, cold, V, N
+        _ptr, _c_int, _c_dbl, _ptr, _ptr,                       # taps_host, K, step, betas_dev, sigma_dev
+        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,         # early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk
+        _ptr, _ptr, _ptr, _c_i64,                               # R_dev, G_dev, J_dev, ldt
+        _ptr, _ptr, _ptr, _ptr,                                 # alpha_dev, lbda_dev, n_outer_dev, n_inner_dev
+        _ptr, _c_i64, _ptr]),                                   # work_dev, work_len, stream
+    "pb_mad_daub_noise_est": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_dbl, _ptr, _ptr]),
+    "pb_mad_daub_noise_est_d": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_dbl, _ptr, _ptr]),
     "pb_inf_norm": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_i64, _ptr]),
     "pb_hrf_normal_eq_len": (_c_i64, [_c_int]),
     "pb_hrf_normal_eq": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int,

@@ -20,6 +20,8 @@ Deviations from the reference, all deliberate:
     else of the branch is pinned against the reference with the estimate injected,
     tests/golden/auto_lbda.npz); it computes in float64 end to end, batches included
     (see ``_deconv_auto_lbda``).
+Beyond the reference's surface: ``deconv_auto`` is that ``lbda=None`` call with the noise level as an argument and the
+whole search resident on the device (``engine``), see there.
 There is no CPU fallback: without the HIP library or a GPU these raise.
 """
 import os
@@ -79,6 +81,12 @@ def _host(t, shape):
 # (tests/test_torch_ops.py).  Initialised from the environment variable PYBOLD_AMD_DISPATCH.
 DISPATCH = os.environ.get("PYBOLD_AMD_DISPATCH", "ctypes")
 
+# Which engine a 2-D `deconv(lbda=None)` runs on: "host" (the default: `_deconv_auto_lbda`, one launch over all voxels per
+# outer iteration, the outer loop in NumPy) or "device" (`deconv_auto(engine="device")`: the whole search resident on
+# the device, one voxel per wave -- series of up to 640 scans, HRFs of up to 32 taps, wind = 6; other shapes keep the
+# host loop).  1-D calls always keep the host loop.  Initialised from the environment variable PYBOLD_AMD_AUTO_LBDA.
+AUTO_LBDA = os.environ.get("PYBOLD_AMD_AUTO_LBDA", "host")
+
 
 def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
            wind=6, nb_iter=1000, nb_sub_iter=1000, verbose=0):
@@ -92,6 +100,9 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
     ``(V, max iterations run)`` padded with NaN after a voxel's early stop.
     """
     if lbda is None:
+        if AUTO_LBDA == "device" and _n_dim(y) == 2 and solver.auto_lbda_supported(_n_scans(y), np.size(hrf), wind):
+            return deconv_auto(y, t_r, hrf, early_stopping=early_stopping, tol=tol, wind=wind, nb_iter=nb_iter,
+                               nb_sub_iter=nb_sub_iter, engine="device", verbose=verbose)[:6]
         return _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, verbose)
     Y, one_d = _y_to_device(y)
     n = Y.shape[1]
@@ -138,7 +149,90 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
     return _host(X, one_d), _host(Z, one_d), _host(W, one_d), J, None, None
 
 
-def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, verbose):
+def _n_dim(y):
+    return y.dim() if torch.is_tensor(y) else np.ndim(y)
+
+
+def _n_scans(y):
+    return int(y.shape[-1]) if torch.is_tensor(y) else int(np.shape(y)[-1])
+
+
+def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000,  # noqa
+                nb_sub_iter=1000, outer_chunk=None, engine="auto", verbose=0):
+    """``deconv(y, t_r, hrf)`` with ``lbda=None`` -- the reference's default call, its noise-driven lambda search
+    (pybold/bold_signal.py:99-214) -- with the engine and the noise level in the caller's hands.
+
+    sigma   noise level per voxel (scalar for a 1-D ``y``, ``(V,)`` array or tensor for a batch); ``None``: the db3
+            MAD estimate (``mad_daub_noise_est``), on the device for a CUDA ``y``, on the host otherwise
+    engine  "device": the whole search as one device-resident solve (``solver.auto_lbda_solve``: one voxel per
+            wave, no host round trip; series of up to 640 scans, HRFs of up to 32 taps, ``wind == 6`` --
+            ``ValueError`` otherwise); "host": the host-driven loop ``deconv(lbda=None)`` runs by default;
+            "auto": the device where it carries the call, else the host loop with one warning
+    outer_chunk  device engine: outer iterations per kernel launch (``None``: the library's choice); no effect on
+            the result
+
+    Returns ``(x, z, diff_z, J, R, G, info)``: the first six exactly as ``deconv(lbda=None)`` returns them for the
+    same input (lists for a 1-D ``y``; ``(n_outer, V)`` arrays padded with NaN for a batch, trimmed to the longest
+    row's outer iterations; CUDA in -> ``x, z, diff_z`` CUDA); ``info`` holds ``alpha``, ``lbda`` (final, per
+    voxel), ``n_outer``, ``n_inner`` (outer / summed inner iterations per voxel), ``sigma`` and ``engine``."""
+    if engine not in ("auto", "device", "host"):
+        raise ValueError("deconv_auto: engine must be 'auto', 'device' or 'host', got %r" % (engine,))
+    n, n_taps = _n_scans(y), int(np.size(hrf))
+    if engine != "host":
+        if solver.auto_lbda_supported(n, n_taps, wind):
+            engine = "device"
+        else:
+            limit = ("the device-resident lambda search carries series of up to 640 scans, HRFs of up to 32 taps and "
+                     "wind = 6; this call has %d scans, %d taps, wind = %d" % (n, n_taps, wind))
+            if engine == "device":
+                raise ValueError("deconv_auto(engine='device'): " + limit)
+            solver.warn_once(("auto-lambda-host", n, n_taps, wind), "deconv_auto: " + limit + ": running the host loop.")
+            engine = "host"
+    on_device = torch.is_tensor(y) and y.is_cuda
+    if sigma is None:
+        if on_device and 5 <= n <= solver.MAD_DAUB_NMAX and y.dtype in (torch.float32, torch.float64):
+            sigma = solver.mad_daub_noise_est(torch.atleast_2d(y))
+        else:
+            y_host = y.detach().cpu().numpy() if torch.is_tensor(y) else np.asarray(y, dtype=np.float64)
+            sigma = np.atleast_1d(mad_daub_noise_est(y_host))
+    if engine == "host":
+        info = {}
+        out = _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, verbose, sigma=sigma, info=info)
+        info["engine"] = "host"
+        return out + (info,)
+
+    one_d = _Shape(_n_dim(y) == 1, on_device)
+    if torch.is_tensor(y):
+        Y = torch.atleast_2d(y).to(device=solver.device(y.device if on_device else None), dtype=torch.float64)
+    else:
+        Y = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(np.asarray(y, dtype=np.float64)))).to(solver.device())
+    V = Y.shape[0]
+    if V == 0:
+        raise ValueError("deconv_auto: empty voxel batch")
+    hrf = np.asarray(hrf, dtype=np.float64)
+    H = ConvAndLinear(DiscretInteg(), hrf, dim_in=n, dim_out=n)
+    step = 1.0 / (0.9 * spectral_radius_est(H, (n,)))
+    W, res = solver.auto_lbda_solve(Y, hrf, step, sigma, early_stopping=early_stopping, tol=tol, wind=wind,
+                                    nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter),
+                                    outer_chunk=int(outer_chunk or 0))
+    X, Z = solver.fista_outputs(W, hrf)
+    n_outer = res["n_outer"].cpu().numpy()
+    n_max = int(n_outer.max())
+    J, R, G = (res[k][:, :n_max].t().cpu().numpy() for k in ("J", "R", "G"))       # (n_outer, V), NaN after a row's stop
+    info = {"alpha": res["alpha"].cpu().numpy(), "lbda": res["lbda"].cpu().numpy(), "n_outer": n_outer,
+            "n_inner": res["n_inner"].cpu().numpy(),
+            "sigma": sigma.cpu().numpy() if torch.is_tensor(sigma) else np.broadcast_to(np.asarray(sigma, dtype=np.float64), (V,)).copy(),
+            "engine": "device"}
+    if verbose > 0:
+        print("deconv_auto: {0} voxel(s), {1} outer iteration(s) at most, {2} inner iterations in all".format(
+            V, n_max, int(info["n_inner"].sum())))
+    if one_d:
+        return (_host(X, one_d), _host(Z, one_d), _host(W, one_d), [float(v) for v in J[:, 0]],
+                [float(v) for v in R[:, 0]], [float(v) for v in G[:, 0]], info)
+    return _host(X, one_d), _host(Z, one_d), _host(W, one_d), J, R, G, info
+
+
+def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, verbose, sigma=None, info=None):
     """``lbda=None`` branch of ``deconv`` (pybold/bold_signal.py:99-214), batched.
 
     Per voxel: ``sigma`` = db3 MAD noise level (:103); ``alpha_0 = 1``,
@@ -152,7 +246,10 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
     padded with NaN for a batch.
     """
     y_host = y.detach().cpu().numpy() if torch.is_tensor(y) else np.asarray(y, dtype=np.float64)
-    sigma = np.atleast_1d(mad_daub_noise_est(y_host))
+    if sigma is None:
+        sigma = np.atleast_1d(mad_daub_noise_est(y_host))
+    else:                                            # the caller's noise level (deconv_auto): scalar or one per voxel
+        sigma = np.atleast_1d(sigma.detach().cpu().numpy() if torch.is_tensor(sigma) else np.asarray(sigma, dtype=np.float64))
     Y, one_d = _y_to_device(y)
     if Y.dtype != torch.float64:
         if Y.shape[0] >= 1024:
@@ -188,9 +285,14 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
     l_alpha = []                                   # last `wind` alpha vectors
     J, R, G = [], [], []
     W = torch.zeros((V, n), dtype=torch.float64, device=dev)
+    n_inner = torch.zeros((V,), dtype=torch.int64, device=dev) if info is not None else None
+    n_outer = np.zeros(V, dtype=np.int32)
     for i in range(nb_iter):
-        W_new, _, _ = solver.fista_solve(Y, hrf, lbda, step, int(nb_sub_iter), W0=W, stop=stop,
-                                         tol=tol, wind=wind)
+        W_new, _, n_done = solver.fista_solve(Y, hrf, lbda, step, int(nb_sub_iter), W0=W, stop=stop,
+                                              tol=tol, wind=wind)
+        n_outer += active
+        if n_inner is not None:                      # (inner iterations of the voxels still searching: deconv_auto's info)
+            n_inner += torch.where(torch.from_numpy(active).to(dev), n_done.long(), torch.zeros_like(n_inner))
         if active.all():
             W = W_new
         else:
@@ -218,9 +320,12 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
             active &= ~(diff < tol)
             if not active.any():
                 break
-    W, _, _ = solver.fista_solve(Y, hrf, lbda, step, int(nb_sub_iter), W0=W, stop=stop, tol=tol,
-                                 wind=wind)
+    W, _, n_done = solver.fista_solve(Y, hrf, lbda, step, int(nb_sub_iter), W0=W, stop=stop, tol=tol,
+                                      wind=wind)
     X, Z = solver.fista_outputs(W, hrf)
+    if info is not None:
+        info.update(alpha=alpha.copy(), lbda=lbda.copy(), n_outer=n_outer, n_inner=(n_inner + n_done.long()).cpu().numpy(),
+                    sigma=np.broadcast_to(sigma, (V,)).copy())
     if one_d:
         keep = [k for k in range(len(J)) if not np.isnan(J[k][0])]
         return (_host(X, one_d), _host(Z, one_d), _host(W, one_d), [float(J[k][0]) for k in keep],

@@ -16,6 +16,7 @@
 #include "fista_pair.h"
 #include "fista_pair_ffa.h"
 #include "fista_exact.h"
+#include "fista_auto.h"
 #include "blind.h"
 #include "fista_mfma.h"
 #include "fista_mfma2.h"
@@ -195,6 +196,57 @@ const ExactEntry* pick_exact(int N, int K) {
     if (!best || (int64_t)e.S * e.KT < (int64_t)best->S * best->KT) best = &e;
   }
   return best;
+}
+
+}  // namespace
+namespace pb {
+#define PB_EXACT(S, KT) extern template int launch_auto<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);
+#include "exact_table.inc"
+#undef PB_EXACT
+}  // namespace pb
+namespace {
+// the device-resident lambda search (fista_auto.h): the (S, KT) pairs of the all-float64 form
+typedef int (*auto_launch_fn)(const pb::AutoArgs&, const double* taps, int K, bool early_stopping, hipStream_t);
+struct AutoEntry {
+  int S, KT;
+  auto_launch_fn fn;
+};
+#define PB_EXACT(S, KT) {S, KT, &pb::launch_auto<S, KT>},
+const AutoEntry kAuto[] = {
+#include "exact_table.inc"
+};
+#undef PB_EXACT
+const AutoEntry* pick_auto(int N, int K) {
+  const ExactEntry* e = (N >= 1 && K >= 1) ? pick_exact(N, K) : nullptr;
+  if (!e) return nullptr;
+  for (const AutoEntry& a : kAuto)
+    if (a.S == e->S && a.KT == e->KT) return &a;
+  return nullptr;
+}
+// outer iterations per launch when the caller leaves the choice to the library: about 65536 inner iterations per wave
+// slot and launch -- 65536 / nb_sub_iter for a batch the machine holds at once (2048 waves: 256 compute units, four
+// SIMDs, two waves of this kernel each), fewer in proportion for a larger one, whose launch runs its waves in rounds
+constexpr int AUTO_LAUNCH_ITERS = 65536, AUTO_RESIDENT_WAVES = 2048;
+inline int auto_outer_chunk(int V, int nb_sub_iter) {
+  const int64_t rounds = ((int64_t)V + AUTO_RESIDENT_WAVES - 1) / AUTO_RESIDENT_WAVES;
+  const int64_t per = (int64_t)(nb_sub_iter > 0 ? nb_sub_iter : 1) * (rounds > 0 ? rounds : 1);
+  const int64_t c = AUTO_LAUNCH_ITERS / per;
+  return (int)(c < 1 ? 1 : c);
+}
+
+constexpr int MAD_DAUB_NMAX = 8192;
+template <typename TY>
+int mad_daub_impl(const TY* y_dev, int64_t ldy, int V, int N, double c, double* sigma_dev, void* stream, const char* name) {
+  if (V < 0 || ldy < N) return fail(PB_ERR_INVALID, "%s: bad size", name);
+  if (N < 5 || N > MAD_DAUB_NMAX) return fail(PB_ERR_INVALID, "%s: N=%d outside 5..%d scans", name, N, MAD_DAUB_NMAX);
+  if (!(c > 0.0)) return fail(PB_ERR_INVALID, "%s: c must be positive", name);
+  if (V == 0) return PB_OK;
+  if (!y_dev || !sigma_dev) return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
+  int n2 = 1;
+  while (n2 < (N + 5) / 2) n2 <<= 1;
+  hipLaunchKernelGGL((pb::mad_daub_kernel<TY>), dim3(V), dim3(pb::GEN_THREADS), (size_t)n2 * sizeof(double), (hipStream_t)stream,
+                     y_dev, ldy, N, c, n2, sigma_dev);
+  return check_launch(name);
 }
 
 const WideEntry* pick_wide(int N, int K) {
@@ -1377,6 +1429,58 @@ int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
     hipLaunchKernelGGL((pb::fista_generic_kernel<false, true>), dim3(P), dim3(pb::GEN_THREADS), lds,
                        (hipStream_t)stream, a, taps_dev, K, wind);
   return check_launch("fista_generic_kernel(f64)");
+}
+
+int pb_auto_lbda_supported(int N, int K, int wind) { return (wind == pb::AUTO_WIND && pick_auto(N, K)) ? 1 : 0; }
+
+int64_t pb_auto_lbda_work_len(int V) { return (int64_t)pb::AUTO_STATE * (V > 0 ? V : 0); }
+
+int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                   const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
+                   int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
+                   double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
+                   int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
+  if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: bad size (V=%d N=%d K=%d)", V, N, K);
+  if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: wind=%d (the device-resident search carries wind = 6)", wind);
+  if (N > 640) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: N=%d exceeds 640 scans", N);
+  if (K > 32) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: K=%d exceeds 32 taps", K);
+  const AutoEntry* ae = pick_auto(N, K);
+  if (!ae) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: no specialisation for N=%d K=%d", N, K);
+  if (nb_iter < 1 || nb_sub_iter < 0 || outer_chunk < 0)
+    return fail(PB_ERR_INVALID, "pb_auto_lbda_d: nb_iter >= 1, nb_sub_iter >= 0 and outer_chunk >= 0 are required (%d, %d, %d)",
+                nb_iter, nb_sub_iter, outer_chunk);
+  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: leading dimension < N");
+  if ((R_dev || G_dev || J_dev) && ldt < nb_iter) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: ldt < nb_iter");
+  if (!(step > 0.0)) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: step must be positive");
+  if (work_len < pb_auto_lbda_work_len(V))
+    return fail(PB_ERR_INVALID, "pb_auto_lbda_d: workspace of %lld float64, %lld needed", (long long)work_len,
+                (long long)pb_auto_lbda_work_len(V));
+  if (V == 0) return PB_OK;
+  if (!y_dev || !w_dev || !taps_host || !sigma_dev || !work_dev || (nb_sub_iter > 0 && !betas_dev))
+    return fail(PB_ERR_INVALID, "pb_auto_lbda_d: NULL pointer");
+  if (V > (1 << 25)) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: more than 2^25 voxels per call");
+  pb::AutoArgs a;
+  a.y = y_dev; a.ldy = ldy; a.w = w_dev; a.ldw = ldw; a.V = V; a.N = N;
+  a.cold = cold ? 1 : 0; a.nb_sub_iter = nb_sub_iter; a.step = step; a.tol = tol;
+  a.betas = betas_dev; a.sigma = sigma_dev; a.R = R_dev; a.G = G_dev; a.J = J_dev; a.ldt = ldt;
+  a.alpha_out = alpha_dev; a.lbda_out = lbda_dev; a.n_outer = n_outer_dev; a.n_inner = n_inner_dev; a.work = work_dev;
+  const int chunk = outer_chunk > 0 ? outer_chunk : auto_outer_chunk(V, nb_sub_iter);
+  for (int i0 = 0; i0 < nb_iter; i0 += chunk) {        // outer iterations [i0, i1) of the voxels still searching
+    a.init = i0 == 0; a.i0 = i0; a.i1 = (nb_iter - i0 < chunk) ? nb_iter : i0 + chunk; a.final_solve = 0;
+    ae->fn(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
+    const int rc = check_launch("auto_lbda_kernel");
+    if (rc != PB_OK) return rc;
+  }
+  a.init = 0; a.i0 = a.i1 = nb_iter; a.final_solve = 1;   // the last inner solve of every voxel, then the outputs
+  ae->fn(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
+  return check_launch("auto_lbda_kernel(final solve)");
+}
+
+int pb_mad_daub_noise_est(const float* y_dev, int64_t ldy, int V, int N, double c, double* sigma_dev, void* stream) {
+  return mad_daub_impl<float>(y_dev, ldy, V, N, c, sigma_dev, stream, "pb_mad_daub_noise_est");
+}
+int pb_mad_daub_noise_est_d(const double* y_dev, int64_t ldy, int V, int N, double c, double* sigma_dev, void* stream) {
+  return mad_daub_impl<double>(y_dev, ldy, V, N, c, sigma_dev, stream, "pb_mad_daub_noise_est_d");
 }
 
 int pb_fista_solve_backtrack_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,

@@ -83,13 +83,160 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
   return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
 }
 
-template <int S, int KT, bool WITH_J, int STOP>
-__global__ __launch_bounds__(256) void fista_exact_kernel(FistaArgs a, TapsD<KT> taps) {
+// ---- the pass body, shared by fista_exact_kernel and auto_lbda_kernel (fista_auto.h) --------------------------------
+// Both kernels keep y, w, the mask and the window-rule state in VGPRs and call the two halves below, once per pass;
+// the cost trace of fista_exact_kernel and the residual statistics of auto_lbda_kernel sit between them (or after the
+// first alone), on the residual the forward half returns.
+
+// forward half: z = cumsum(w), x = h * z, r = (x - y) on the samples of the series (0 on the padding)
+template <int S, int KT>
+__device__ __forceinline__ void exact_forward(const double (&w)[S], const double (&y)[S], const double (&mk)[S],
+                                              const TapsD<KT>& taps, double (&r)[S]) {
   constexpr int H = KT - 1;
   constexpr int D = (H + S - 1) / S;        // neighbour lanes that contribute halo
-  constexpr int WIND = 6;
   static_assert(D <= 63, "halo spans more than the wave");
+  // ---- z = cumsum(w) ----------------------------------------------------
+  double z[S];
+  z[0] = w[0];
+#pragma unroll
+  for (int j = 1; j < S; ++j) z[j] = z[j - 1] + w[j];
+  {
+    const double off = dpp_f64<DPP_WAVE_SHR1>(wave_prefix_incl_f64(z[S - 1]));
+#pragma unroll
+    for (int j = 0; j < S; ++j) z[j] += off;
+  }
+  // ---- window of z: own samples at [H, H+S), halo below -------------------
+  double Z[H + S];
+  static_for<0, S>([&](auto jc) { Z[H + decltype(jc)::value] = z[decltype(jc)::value]; });
+  {
+    double sh[S];
+#pragma unroll
+    for (int j = 0; j < S; ++j) sh[j] = z[j];
+    static_for<1, D + 1>([&](auto dc) {
+      constexpr int d = decltype(dc)::value;
+#pragma unroll
+      for (int j = 0; j < S; ++j) sh[j] = dpp_f64<DPP_WAVE_SHR1>(sh[j]);      // lane - d
+      static_for<0, S>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        constexpr int e = H - d * S + j;
+        if constexpr (e >= 0) Z[e] = sh[j];
+      });
+    });
+  }
+  // ---- r = h * z - y -------------------------------------------------------
+  static_for<0, S>([&](auto jc) { r[decltype(jc)::value] = -y[decltype(jc)::value]; });
+  static_for<0, KT>([&](auto mc) {          // tap-major: S independent chains
+    constexpr int m = decltype(mc)::value;
+    static_for<0, S>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      r[j] = fma(taps.h[m], Z[H + j - m], r[j]);
+    });
+  });
+#pragma unroll
+  for (int j = 0; j < S; ++j) r[j] *= mk[j];
+}
 
+// backward half: g = revcumsum(K^T r), gradient step, prox, momentum; with a stop rule (STOP 1: _loops_deconv, 2: window,
+// wind = 6) the two wave-wide sums of its criterion come back in num / den (and the window state moves on one iteration)
+template <int S, int KT, int STOP>
+__device__ __forceinline__ void exact_backward(const double (&r)[S], double (&w)[S], const TapsD<KT>& taps, double nstep,
+                                               double th, const double* beta_k, double (&uprev)[STOP == 2 ? S : 1],
+                                               double (&d1)[STOP == 2 ? S : 1], double (&d2)[STOP == 2 ? S : 1],
+                                               double (&d3)[STOP == 2 ? S : 1], double& num, double& den) {
+  constexpr int H = KT - 1;
+  constexpr int D = (H + S - 1) / S;
+  // ---- window of r: own samples at [0, S), halo above ----------------------
+  double R[S + H];
+  static_for<0, S>([&](auto jc) { R[decltype(jc)::value] = r[decltype(jc)::value]; });
+  {
+    double sh[S];
+#pragma unroll
+    for (int j = 0; j < S; ++j) sh[j] = r[j];
+    static_for<1, D + 1>([&](auto dc) {
+      constexpr int d = decltype(dc)::value;
+#pragma unroll
+      for (int j = 0; j < S; ++j) sh[j] = dpp_f64<DPP_WAVE_SHL1>(sh[j]);      // lane + d
+      static_for<0, S>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        constexpr int e = d * S + j;
+        if constexpr (e < S + H) R[e] = sh[j];
+      });
+    });
+  }
+  // ---- g = revcumsum(K^T r) ---------------------------------------------------
+  double g[S];
+#pragma unroll
+  for (int j = 0; j < S; ++j) g[j] = 0.0;
+  static_for<0, KT>([&](auto mc) {
+    constexpr int m = decltype(mc)::value;
+    static_for<0, S>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      g[j] = fma(taps.h[m], R[j + m], g[j]);
+    });
+  });
+#pragma unroll
+  for (int j = S - 2; j >= 0; --j) g[j] += g[j + 1];
+  {
+    const double off = wave_suffix_excl_f64(g[0]);         // sum of the lanes above, exactly 0 above the last sample
+#pragma unroll
+    for (int j = 0; j < S; ++j) g[j] += off;
+  }
+
+  // ---- gradient step, prox, momentum; stop rules ------------------------------
+  const double beta = *beta_k;                // (read here, after the scans: the taps fill the scalar registers)
+  const double nb1 = -(1.0 + beta);
+  if constexpr (STOP == 0) {
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+      const double u = fma(nstep, g[j], w[j]);
+      const double d = prox_excess_ref(u, th);
+      w[j] = fma(nb1, d, u);
+    }
+  } else {
+    num = 0.0;
+    den = 0.0;
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+      const double u = fma(nstep, g[j], w[j]);
+      const double d = prox_excess_ref(u, th);
+      const double wn = fma(nb1, d, u);
+      if constexpr (STOP == 1) {            // _loops_deconv rule (pybold/bold_signal.py:267-273)
+        const double diff = wn - u;
+        num = fma(diff, diff, num);
+        den = fma(wn, wn, den);
+      } else {
+        // deconv window rule, wind = 6 (:82-95), on [u_{k-4} .. u_k, w_{k+1}]:
+        //   3 (new - old) = delta_{k-3} + 2 delta_{k-2} + 3 delta_{k-1} + 2 delta_k + e
+        //   3 new         = 3 u_k - delta_k + e          (see fista_fast.h)
+        const double dk = u - uprev[j];
+        const double e = wn - u;
+        const double diff = fma(2.0, dk, fma(3.0, d1[j], fma(2.0, d2[j], d3[j]))) + e;
+        const double sn = fma(3.0, u, e - dk);
+        num = fma(diff, diff, num);
+        den = fma(sn, sn, den);
+        d3[j] = d2[j];
+        d2[j] = d1[j];
+        d1[j] = dk;
+        uprev[j] = u;
+      }
+      w[j] = wn;
+    }
+    num = seg_allsum_f64<64>(num);
+    den = seg_allsum_f64<64>(den);
+  }
+}
+
+// the criterion of either stop rule on those sums: first test after 3 (_loops_deconv) / wind + 1 = 7 (window rule)
+// iterations, floor 1e-10 / 3e-10 (the window rule's sums carry a factor 3)
+template <int STOP>
+__device__ __forceinline__ bool exact_stop_fires(int it, double num, double den, double tol) {
+  constexpr int first_test = (STOP == 1) ? 3 : 6 + 1;
+  constexpr double floor_eps = (STOP == 2) ? 3.0e-10 : 1.0e-10;
+  return it >= first_test && sqrt(num) / (sqrt(den) + floor_eps) < tol;
+}
+
+template <int S, int KT, bool WITH_J, int STOP>
+__global__ __launch_bounds__(256) void fista_exact_kernel(FistaArgs a, TapsD<KT> taps) {
   const int lane = threadIdx.x & 63;
   // slots of this launch's list (fista_fast.h: launch_slots; the batch itself without a device-side list).  Round 5: the
   // ill-conditioned series of a partitioned float32 call run here (y float32 in HBM, a.y64 == nullptr; cost trace to a.J)
@@ -132,46 +279,8 @@ __global__ __launch_bounds__(256) void fista_exact_kernel(FistaArgs a, TapsD<KT>
   int n_stop = a.n_iter;
   for (int it = 0;; ++it) {
     if (!WITH_J && it >= n_stop) break;
-    // ---- z = cumsum(w) ----------------------------------------------------
-    double z[S];
-    z[0] = w[0];
-#pragma unroll
-    for (int j = 1; j < S; ++j) z[j] = z[j - 1] + w[j];
-    {
-      const double off = dpp_f64<DPP_WAVE_SHR1>(wave_prefix_incl_f64(z[S - 1]));
-#pragma unroll
-      for (int j = 0; j < S; ++j) z[j] += off;
-    }
-    // ---- window of z: own samples at [H, H+S), halo below -------------------
-    double Z[H + S];
-    static_for<0, S>([&](auto jc) { Z[H + decltype(jc)::value] = z[decltype(jc)::value]; });
-    {
-      double sh[S];
-#pragma unroll
-      for (int j = 0; j < S; ++j) sh[j] = z[j];
-      static_for<1, D + 1>([&](auto dc) {
-        constexpr int d = decltype(dc)::value;
-#pragma unroll
-        for (int j = 0; j < S; ++j) sh[j] = dpp_f64<DPP_WAVE_SHR1>(sh[j]);      // lane - d
-        static_for<0, S>([&](auto jc) {
-          constexpr int j = decltype(jc)::value;
-          constexpr int e = H - d * S + j;
-          if constexpr (e >= 0) Z[e] = sh[j];
-        });
-      });
-    }
-    // ---- r = h * z - y -------------------------------------------------------
     double r[S];
-    static_for<0, S>([&](auto jc) { r[decltype(jc)::value] = -y[decltype(jc)::value]; });
-    static_for<0, KT>([&](auto mc) {          // tap-major: S independent chains
-      constexpr int m = decltype(mc)::value;
-      static_for<0, S>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        r[j] = fma(taps.h[m], Z[H + j - m], r[j]);
-      });
-    });
-#pragma unroll
-    for (int j = 0; j < S; ++j) r[j] *= mk[j];
+    exact_forward<S, KT>(w, y, mk, taps, r);
 
     // ---- cost of the iterate this pass started from -------------------------
     if constexpr (WITH_J) {
@@ -191,88 +300,12 @@ __global__ __launch_bounds__(256) void fista_exact_kernel(FistaArgs a, TapsD<KT>
       if (it >= n_stop) break;
     }
 
-    // ---- window of r: own samples at [0, S), halo above ----------------------
-    double R[S + H];
-    static_for<0, S>([&](auto jc) { R[decltype(jc)::value] = r[decltype(jc)::value]; });
-    {
-      double sh[S];
-#pragma unroll
-      for (int j = 0; j < S; ++j) sh[j] = r[j];
-      static_for<1, D + 1>([&](auto dc) {
-        constexpr int d = decltype(dc)::value;
-#pragma unroll
-        for (int j = 0; j < S; ++j) sh[j] = dpp_f64<DPP_WAVE_SHL1>(sh[j]);      // lane + d
-        static_for<0, S>([&](auto jc) {
-          constexpr int j = decltype(jc)::value;
-          constexpr int e = d * S + j;
-          if constexpr (e < S + H) R[e] = sh[j];
-        });
-      });
-    }
-    // ---- g = revcumsum(K^T r) ---------------------------------------------------
-    double g[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) g[j] = 0.0;
-    static_for<0, KT>([&](auto mc) {
-      constexpr int m = decltype(mc)::value;
-      static_for<0, S>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        g[j] = fma(taps.h[m], R[j + m], g[j]);
-      });
-    });
-#pragma unroll
-    for (int j = S - 2; j >= 0; --j) g[j] += g[j + 1];
-    {
-      const double off = wave_suffix_excl_f64(g[0]);         // sum of the lanes above, exactly 0 above the last sample
-#pragma unroll
-      for (int j = 0; j < S; ++j) g[j] += off;
-    }
-
-    // ---- gradient step, prox, momentum; stop rules ------------------------------
-    const double beta = a.betas[it];
-    const double nb1 = -(1.0 + beta);
-    if constexpr (STOP == 0) {
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-        const double u = fma(nstep, g[j], w[j]);
-        const double d = prox_excess_ref(u, th);
-        w[j] = fma(nb1, d, u);
-      }
-    } else {
-      double num = 0.0, den = 0.0, floor_eps = 1.0e-10;
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-        const double u = fma(nstep, g[j], w[j]);
-        const double d = prox_excess_ref(u, th);
-        const double wn = fma(nb1, d, u);
-        if constexpr (STOP == 1) {            // _loops_deconv rule (pybold/bold_signal.py:267-273)
-          const double diff = wn - u;
-          num = fma(diff, diff, num);
-          den = fma(wn, wn, den);
-        } else {
-          // deconv window rule, wind = 6 (:82-95), on [u_{k-4} .. u_k, w_{k+1}]:
-          //   3 (new - old) = delta_{k-3} + 2 delta_{k-2} + 3 delta_{k-1} + 2 delta_k + e
-          //   3 new         = 3 u_k - delta_k + e          (see fista_fast.h)
-          const double dk = u - uprev[j];
-          const double e = wn - u;
-          const double diff = fma(2.0, dk, fma(3.0, d1[j], fma(2.0, d2[j], d3[j]))) + e;
-          const double sn = fma(3.0, u, e - dk);
-          num = fma(diff, diff, num);
-          den = fma(sn, sn, den);
-          d3[j] = d2[j];
-          d2[j] = d1[j];
-          d1[j] = dk;
-          uprev[j] = u;
-        }
-        w[j] = wn;
-      }
-      if constexpr (STOP == 2) floor_eps = 3.0e-10;
-      num = seg_allsum_f64<64>(num);
-      den = seg_allsum_f64<64>(den);
+    double num = 0.0, den = 0.0;
+    exact_backward<S, KT, STOP>(r, w, taps, nstep, th, a.betas + it, uprev, d1, d2, d3, num, den);
+    if constexpr (STOP != 0) {
       if (active) {
         done = it + 1;
-        constexpr int first_test = (STOP == 1) ? 3 : WIND + 1;
-        if (it >= first_test && sqrt(num) / (sqrt(den) + floor_eps) < a.tol) {
+        if (exact_stop_fires<STOP>(it, num, den, a.tol)) {
           active = false;                     // wave-uniform: one problem per wave
           n_stop = it + 1;
         }

@@ -448,6 +448,68 @@ __global__ __launch_bounds__(GEN_THREADS) void lambda_max_kernel(const TY* y, in
   if (threadIdx.x == 0) out[blockIdx.x] = m;
 }
 
+// ---- noise level of every row: MAD of the level-1 db3 detail band / c (mad_daub_noise_est, pybold/utils.py:10-25) ----
+// ascending bitonic sort of s[0, n2) in LDS (n2 a power of two; the caller pads with +inf), all threads of the workgroup
+__device__ __forceinline__ void block_bitonic_sort(double* s, int n2) {
+  for (int k = 2; k <= n2; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int t = threadIdx.x; t < (n2 >> 1); t += GEN_THREADS) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));      // lower index of the pair (bit j clear)
+        const int l = i | j;
+        const double a = s[i], b = s[l];
+        const bool up = (i & k) == 0;
+        if ((a > b) == up) {
+          s[i] = b;
+          s[l] = a;
+        }
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// median of the n smallest entries of the sorted s: the middle one, or (a + b) / 2 of the middle two (np.median)
+__device__ __forceinline__ double sorted_median(const double* s, int n) {
+  return (n & 1) ? s[n >> 1] : (s[(n >> 1) - 1] + s[n >> 1]) / 2.0;
+}
+
+// sigma[v] = median(|cD - median(cD)|) / c with cD[k] = sum_j g[j] xe[2k + 1 - j], k < (N + 5) / 2, xe = the row with
+// half-sample symmetric extension (5 samples mirrored at either end) and g = db3's decomposition high-pass: the sums
+// with j ascending, multiply then add, NOT contracted -- the NumPy statement's own roundings.  One row per workgroup;
+// LDS: n2 doubles, n2 = the power of two >= (N + 5) / 2.  5 <= N <= 8192.
+template <typename TY>
+__global__ __launch_bounds__(GEN_THREADS) void mad_daub_kernel(const TY* y, int64_t ldy, int N, double c, int n2,
+                                                               double* sigma) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double* s = reinterpret_cast<double*>(smem);
+  constexpr double g[6] = {-0.3326705529509569, 0.8068915093133388, -0.4598775021193313,
+                           -0.13501102001039084, 0.08544127388224149, 0.035226291882100656};
+  const TY* yr = y + (int64_t)blockIdx.x * ldy;
+  const int n_out = (N + 5) / 2;
+  const double inf = __builtin_inf();
+  for (int k = threadIdx.x; k < n2; k += GEN_THREADS) {
+    double acc = inf;
+    if (k < n_out) {
+      acc = 0.0;
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const int e = 2 * k + 1 - j;                                // index into the extended row, -5 <= e <= N + 4
+        const int i = e < 0 ? -1 - e : (e < N ? e : 2 * N - 1 - e);
+        acc = acc + g[j] * (double)yr[i];
+      }
+    }
+    s[k] = acc;
+  }
+  block_bitonic_sort(s, n2);
+  const double med = sorted_median(s, n_out);
+  __syncthreads();
+  for (int k = threadIdx.x; k < n_out; k += GEN_THREADS) s[k] = fabs(s[k] - med);
+  block_bitonic_sort(s, n2);
+  if (threadIdx.x == 0) sigma[blockIdx.x] = sorted_median(s, n_out) / c;
+}
+
 // out = x / (max|x| + 1e-12) per row (inf_norm, pybold/utils.py:112-138); rows of any length
 // (two passes over global memory, nothing staged)
 __global__ __launch_bounds__(GEN_THREADS) void inf_norm_kernel(const double* x, int64_t ldx,

@@ -5,6 +5,8 @@
 //   deconv / _loops_deconv loops   pybold/bold_signal.py:62-72, :259-276   -> fista_solve
 //   outputs z, x                   pybold/bold_signal.py:74-75, :97        -> fista_outputs
 //   H.op / H.adj                   pybold/linear.py:73-113                 -> op_forward / op_adjoint
+//   deconv, lbda=None (noise-driven search)   pybold/bold_signal.py:99-214    -> auto_lbda_solve
+//   mad_daub_noise_est             pybold/utils.py:10-25                   -> mad_daub_noise_est
 //   hrf_fit_err as normal equations + its 1-D fit   pybold/bold_signal.py:217-222, :329-333
 //                                                                          -> hrf_normal_eq, theta_fit
 // Host-only translation unit (no device code): built by `make torch_ops` with the C++ compiler.
@@ -143,9 +145,70 @@ std::tuple<Tensor, Tensor, Tensor> theta_fit(const Tensor& ne, const Tensor& t, 
   return {theta, cost, taps};
 }
 
+// sigma (V,) float64 of the rows of Y (float32 or float64)
+Tensor mad_daub_noise_est(const Tensor& Y, double c) {
+  TORCH_CHECK(Y.scalar_type() == at::kFloat || Y.scalar_type() == at::kDouble, "Y must be float32 or float64");
+  rows(Y, Y.scalar_type(), "Y");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Y.device());
+  Tensor sigma = at::empty({Y.size(0)}, Y.options().dtype(at::kDouble));
+  if (Y.scalar_type() == at::kDouble)
+    check(pb_mad_daub_noise_est_d(Y.data_ptr<double>(), ld(Y), (int)Y.size(0), (int)Y.size(1), c, sigma.data_ptr<double>(),
+                                  stream_of(Y)), "pb_mad_daub_noise_est_d");
+  else
+    check(pb_mad_daub_noise_est(Y.data_ptr<float>(), ld(Y), (int)Y.size(0), (int)Y.size(1), c, sigma.data_ptr<double>(),
+                                stream_of(Y)), "pb_mad_daub_noise_est");
+  return sigma;
+}
+
+// The noise-driven lambda search, device-resident.  W (in: warm start unless cold, out: diff_z) and the traces R, G, J
+// (V, >= nb_iter; or undefined) are written in place; returns (alpha, lbda, n_outer int32, n_inner int64).
+std::tuple<Tensor, Tensor, Tensor, Tensor> auto_lbda_solve(const Tensor& Y, Tensor W, bool cold, const Tensor& taps_host,
+                                                           double step, const Tensor& betas, const Tensor& sigma,
+                                                           bool early_stopping, double tol, int64_t wind, int64_t nb_iter,
+                                                           int64_t nb_sub_iter, int64_t outer_chunk, c10::optional<Tensor> R,
+                                                           c10::optional<Tensor> G, c10::optional<Tensor> J) {
+  rows(Y, at::kDouble, "Y");
+  rows(W, at::kDouble, "W");
+  same_device(W, Y, "W");
+  TORCH_CHECK(W.size(0) == Y.size(0) && W.size(1) == Y.size(1), "W must have the shape of Y");
+  TORCH_CHECK(!taps_host.is_cuda() && taps_host.scalar_type() == at::kDouble && taps_host.is_contiguous(),
+              "taps_host must be a contiguous float64 CPU tensor");
+  TORCH_CHECK(nb_iter >= 1 && nb_sub_iter >= 0 && outer_chunk >= 0, "nb_iter >= 1, nb_sub_iter >= 0, outer_chunk >= 0");
+  TORCH_CHECK(betas.is_cuda() && betas.scalar_type() == at::kDouble && betas.numel() >= nb_sub_iter, "betas: float64 CUDA, nb_sub_iter entries");
+  same_device(betas, Y, "betas");
+  dev_vec(sigma, Y, "sigma");
+  TORCH_CHECK(sigma.numel() == Y.size(0), "sigma must hold one value per row of Y");
+  int64_t ldt = 0;
+  for (const c10::optional<Tensor>* t : {&R, &G, &J}) {
+    if (!*t) continue;
+    rows(**t, at::kDouble, "R / G / J");
+    same_device(**t, Y, "R / G / J");
+    TORCH_CHECK((*t)->size(0) == Y.size(0) && (*t)->size(1) >= nb_iter, "R, G, J must be (V, >= nb_iter)");
+    TORCH_CHECK(ldt == 0 || ldt == ld(**t), "R, G, J must share one leading dimension");
+    ldt = ld(**t);
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Y.device());
+  const int V = (int)Y.size(0);
+  Tensor alpha = at::empty({V}, Y.options()), lbda = at::empty({V}, Y.options());
+  Tensor n_outer = at::empty({V}, Y.options().dtype(at::kInt)), n_inner = at::empty({V}, Y.options().dtype(at::kLong));
+  Tensor work = at::empty({pb_auto_lbda_work_len(V)}, Y.options());
+  check(pb_auto_lbda_d(Y.data_ptr<double>(), ld(Y), W.data_ptr<double>(), ld(W), cold ? 1 : 0, V, (int)Y.size(1),
+                       taps_host.data_ptr<double>(), (int)taps_host.numel(), step, betas.data_ptr<double>(),
+                       sigma.data_ptr<double>(), early_stopping ? 1 : 0, tol, (int)wind, (int)nb_iter, (int)nb_sub_iter,
+                       (int)outer_chunk, R ? R->data_ptr<double>() : nullptr, G ? G->data_ptr<double>() : nullptr,
+                       J ? J->data_ptr<double>() : nullptr, ldt, alpha.data_ptr<double>(), lbda.data_ptr<double>(),
+                       n_outer.data_ptr<int32_t>(), n_inner.data_ptr<int64_t>(), work.data_ptr<double>(), work.numel(),
+                       stream_of(Y)), "pb_auto_lbda_d");
+  return {alpha, lbda, n_outer, n_inner};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(pybold_hip, m) {
+  m.def("auto_lbda_solve(Tensor Y, Tensor(a!) W, bool cold, Tensor taps_host, float step, Tensor betas, Tensor sigma, "
+        "bool early_stopping, float tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk, Tensor(b!)? R, "
+        "Tensor(c!)? G, Tensor(d!)? J) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("mad_daub_noise_est(Tensor Y, float c) -> Tensor");
   m.def("fista_solve(Tensor Y, Tensor(a!) W, Tensor taps_host, Tensor? taps_dev, float step, float lbda, Tensor? lbda_vec, "
         "Tensor betas, int n_iter, Tensor(b!)? J, int stop_mode, float tol, int wind, Tensor(c!) n_done, int y_rep, int flags) -> ()");
   m.def("fista_outputs(Tensor W, Tensor taps_dev) -> (Tensor, Tensor)");
@@ -158,6 +221,8 @@ TORCH_LIBRARY(pybold_hip, m) {
 
 TORCH_LIBRARY_IMPL(pybold_hip, CUDA, m) {
   m.impl("fista_solve", &fista_solve);
+  m.impl("auto_lbda_solve", &auto_lbda_solve);
+  m.impl("mad_daub_noise_est", &mad_daub_noise_est);
   m.impl("fista_outputs", &fista_outputs);
   m.impl("op_forward", &op_forward);
   m.impl("op_adjoint", &op_adjoint);

@@ -813,6 +813,84 @@ def lambda_max(Y, hrf):
     return out
 
 
+MAD_DAUB_NMAX = 8192         # pb_mad_daub_noise_est: longest row (include/pybold_hip.h)
+
+
+def mad_daub_noise_est(Y, c=0.6744):
+    """Noise level of every row of a float32 or float64 CUDA ``(V, N)`` tensor (float64 ``(V,)``): the MAD of the
+    level-1 db3 detail band / ``c`` (pybold/utils.py:10-25), the operations of ``utils.mad_daub_noise_est`` in the
+    same order on the device.  ``5 <= N <= 8192``; the library refuses other lengths (``PyboldHipError``)."""
+    lib = _lib.load()
+    Y, fn = _y_rows(Y, lib.pb_mad_daub_noise_est, lib.pb_mad_daub_noise_est_d)
+    dev = Y.device
+    V, N = Y.shape
+    out = torch.empty((V,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = fn(Y.data_ptr(), _ld(Y), V, N, float(c), out.data_ptr(), _stream_ptr(dev))
+    _lib.check(rc, "pb_mad_daub_noise_est")
+    return out
+
+
+def auto_lbda_supported(n_scans, n_taps, wind=6):
+    """Whether :func:`auto_lbda_solve` carries this shape (``N <= 640``, ``K <= 32``, ``wind == 6``)."""
+    return bool(_lib.load().pb_auto_lbda_supported(int(n_scans), int(n_taps), int(wind)))
+
+
+def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                    outer_chunk=0, W0=None, want_trace=True):
+    """The noise-driven lambda search of ``deconv(lbda=None)`` (pybold/bold_signal.py:99-214) for every row of ``Y``
+    as one device-resident solve (``pb_auto_lbda_d``: one voxel per wave, no host round trip, no synchronisation).
+
+    Y      float64 CUDA ``(V, N)``, ``N <= 640``;  hrf  1-D array of ``K <= 32`` taps (host);  step  ``1 / L``
+    sigma  float64 ``(V,)`` noise levels (CUDA tensor, array or scalar)
+    W0     optional float64 CUDA ``(V, N)`` warm start (not modified)
+    outer_chunk  outer iterations per launch (0: the library's choice); changes no bit of the result
+    Returns ``(W, info)``: the final iterate and a dict of CUDA tensors ``alpha``, ``lbda`` (float64 ``(V,)``),
+    ``n_outer`` (int32), ``n_inner`` (int64, inner iterations summed) and, with ``want_trace``, ``R``, ``G``, ``J``
+    (float64 ``(V, nb_iter)``, NaN from a voxel's ``n_outer`` on)."""
+    lib = _lib.load()
+    Y = _rows(Y, torch.float64, "Y")
+    dev = Y.device
+    V, N = Y.shape
+    taps = _as_taps(hrf)
+    nb_iter, nb_sub_iter = int(nb_iter), int(nb_sub_iter)
+    if W0 is None:
+        W = torch.empty((V, N), dtype=torch.float64, device=dev)
+    else:
+        W = _rows(W0, torch.float64, "W0").clone()
+        if W.shape != (V, N):
+            raise ValueError("W0 must be %s, got %s" % ((V, N), tuple(W.shape)))
+    if torch.is_tensor(sigma):
+        sig = sigma.to(device=dev, dtype=torch.float64).reshape(-1)
+    else:
+        sig = torch.from_numpy(np.ascontiguousarray(np.atleast_1d(np.asarray(sigma, dtype=np.float64)).ravel())).to(dev)
+    if sig.numel() == 1 and V != 1:
+        sig = sig.expand(V)
+    sig = sig.contiguous()
+    if sig.numel() != V:
+        raise ValueError("sigma must have one entry per row of Y (%d)" % V)
+    betas = _betas_on(dev, nb_sub_iter)
+    trace = [torch.full((V, max(nb_iter, 1)), float("nan"), dtype=torch.float64, device=dev) if want_trace else None
+             for _ in range(3)]
+    alpha = torch.empty((V,), dtype=torch.float64, device=dev)
+    lbda = torch.empty((V,), dtype=torch.float64, device=dev)
+    n_outer = torch.empty((V,), dtype=torch.int32, device=dev)
+    n_inner = torch.empty((V,), dtype=torch.int64, device=dev)
+    work = torch.empty((int(lib.pb_auto_lbda_work_len(V)),), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.pb_auto_lbda_d(
+            Y.data_ptr(), _ld(Y), W.data_ptr(), _ld(W), int(W0 is None), V, N,
+            taps.ctypes.data, taps.size, float(step), betas.data_ptr(), sig.data_ptr(),
+            int(bool(early_stopping)), float(tol), int(wind), nb_iter, nb_sub_iter, int(outer_chunk),
+            trace[0].data_ptr() if want_trace else None, trace[1].data_ptr() if want_trace else None,
+            trace[2].data_ptr() if want_trace else None, _ld(trace[0]) if want_trace else 0,
+            alpha.data_ptr(), lbda.data_ptr(), n_outer.data_ptr(), n_inner.data_ptr(),
+            work.data_ptr(), work.numel(), _stream_ptr(dev))
+    _lib.check(rc, "pb_auto_lbda_d")
+    return W, {"alpha": alpha, "lbda": lbda, "n_outer": n_outer, "n_inner": n_inner,
+               "R": trace[0], "G": trace[1], "J": trace[2]}
+
+
 def inf_norm_rows(X):
     """``x / (max|x| + 1e-12)`` for every row of a float64 CUDA ``(V, n)`` tensor
     (pybold/utils.py:112-115 applied row-wise)."""

@@ -45,3 +45,26 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop_mode=0, 
                     solver._betas_on(dev, int(n_iter)), int(n_iter), J, int(stop_mode), float(tol), int(wind), n_done,
                     int(y_rep), int(flags))
     return W, J, n_done
+
+
+def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                    outer_chunk=0, W0=None, want_trace=True):
+    """The same contract as :func:`pybold_amd.solver.auto_lbda_solve` through ``torch.ops.pybold_hip.auto_lbda_solve``."""
+    import numpy as np
+    from . import solver
+    ops = load()
+    dev = Y.device
+    taps = torch.from_numpy(np.ascontiguousarray(np.asarray(hrf, dtype=np.float64).ravel()))
+    W = torch.empty_like(Y) if W0 is None else W0.clone()
+    R, G, J = (torch.full((Y.shape[0], int(nb_iter)), float("nan"), dtype=torch.float64, device=dev)
+               for _ in range(3)) if want_trace else (None, None, None)
+    alpha, lbda, n_outer, n_inner = ops.auto_lbda_solve(
+        Y, W, W0 is None, taps, float(step), solver._betas_on(dev, int(nb_sub_iter)),
+        torch.as_tensor(sigma, dtype=torch.float64).to(dev).contiguous().ravel(), bool(early_stopping), float(tol),
+        int(wind), int(nb_iter), int(nb_sub_iter), int(outer_chunk), R, G, J)
+    return W, {"alpha": alpha, "lbda": lbda, "n_outer": n_outer, "n_inner": n_inner, "R": R, "G": G, "J": J}
+
+
+def mad_daub_noise_est(Y, c=0.6744):
+    """``torch.ops.pybold_hip.mad_daub_noise_est``: the noise level of every row of a CUDA ``(V, N)`` tensor."""
+    return load().mad_daub_noise_est(Y, float(c))
