@@ -438,11 +438,20 @@ int pb_spm_hrf(const double* deltas_dev, int M, const double* t_dev, int K,
  *                     noise-driven search (pybold/bold_signal.py:141-145) drives alpha, hence
  *                     lambda = 1 / (2 alpha), below zero, and `sign(u) max(|u| - th, 0)` (:66) then
  *                     GROWS every non-zero entry by |th|; these kernels restate that expression,
- *                     the float32-y kernels clamp (pb_fista_solve rejects a negative scalar lbda).  Register-resident kernel (one problem per wave,
- *                     fista_exact_kernel) for series of up to 640 scans with HRFs of up to
- *                     32 taps when taps_host is given (window rule: wind = 6); otherwise, or
- *                     with PB_FLAG_FORCE_GENERIC, the any-size LDS kernel, which reads the taps
- *                     from taps_dev.  Either taps pointer may be NULL if the other kernel runs.
+ *                     the float32-y kernels clamp (pb_fista_solve rejects a negative scalar lbda).  Register-resident kernels
+ *                     when taps_host is given, for HRFs of up to 32 taps (window rule: wind = 6):
+ *                       scans N       form                                                     pb_fista_which_kernel_d
+ *                       <= 640        fista_exact_kernel, one problem per wave                 7
+ *                       641 .. 1280   fista_exact_split_kernel, one problem per workgroup of   8
+ *                                     four waves (csrc/fista_exact_split.h)
+ *                       otherwise (longer series or HRFs, other windows), or with
+ *                       PB_FLAG_FORCE_GENERIC: the any-size LDS kernel, which reads the taps    0
+ *                       from taps_dev (-1: the shape exceeds LDS as well, the call fails)
+ *                     Either taps pointer may be NULL if the other kind of kernel runs.  PB_FLAG_FORCE_FAST means what it
+ *                     meant before the four-wave form: fista_exact_kernel or an error (it fails beyond 640 scans); the
+ *                     four-wave form is chosen by the dispatch, never forced.
+ * pb_fista_which_kernel_d  which of them pb_fista_solve_d (no flags, taps_host given) runs for a call shape: the codes
+ *                     above.  Host-only query.
  * pb_fista_stats_d, pb_hrf_cost_d, pb_hrf_cost_pv_d   as their float32-y namesakes.
  */
 int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw,
@@ -450,6 +459,7 @@ int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
                      double step, double lbda, const double* lbda_dev, const double* betas_dev,
                      int n_iter, double* J_dev, int64_t ldj, int stop_mode, double tol, int wind,
                      int32_t* n_done_dev, unsigned flags, void* stream);
+int pb_fista_which_kernel_d(int N, int K, int with_cost_trace, int stop_mode, int wind);
 /*
  * OPT-IN EXTRA, never part of a parity run: the recurrence of pb_fista_solve_d with a BACKTRACKED step.  The reference
  * has a constant step only (pybold/bold_signal.py:52-53 / :253-254: 1 / (0.9 rho) or 1 / ||A^T A||_F); this is

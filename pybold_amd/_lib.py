@@ -128,6 +128,7 @@ SIGNATURES = {
         _ptr, _c_i64,                    # J_dev (float64), ldj
         _c_int, _c_dbl, _c_int, _ptr,    # stop_mode, tol, wind, n_done_dev
         ctypes.c_uint, _ptr]),           # flags, stream
+    "pb_fista_which_kernel_d": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "pb_fista_stats_d": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int, _ptr,
                                   _c_int, _ptr, _ptr, _ptr]),
     "pb_hrf_cost_d": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _ptr,

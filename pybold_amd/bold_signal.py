@@ -254,8 +254,9 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
     if Y.dtype != torch.float64:
         if Y.shape[0] >= 1024:
             solver.warn_once("auto-lambda-f64",
-                             "deconv(lbda=None) on %d voxels runs on the all-float64 kernel (one problem per wave, ~3x "
-                             "slower than the float32-FIR batch kernels; the LDS kernel beyond 640 scans / 32 taps): "
+                             "deconv(lbda=None) on %d voxels runs on the all-float64 kernels (one problem per wave, ~3x "
+                             "slower than the float32-FIR batch kernels; one problem per workgroup of four waves for "
+                             "641..1280 scans; the LDS kernel beyond 1280 scans / 32 taps): "
                              "the decisions of this branch sit on rounding knife edges." % Y.shape[0])
         # Two knife edges (both pinned against the reference: tests/golden/auto_lbda.npz).  (1) The inner window rule
         # compares iterates with gradient points (the aliasing of :65/:72), so its criterion tends to a CONSTANT

@@ -16,6 +16,7 @@
 #include "fista_pair.h"
 #include "fista_pair_ffa.h"
 #include "fista_exact.h"
+#include "fista_exact_split.h"
 #include "fista_auto.h"
 #include "blind.h"
 #include "fista_mfma.h"
@@ -181,6 +182,20 @@ const ExactEntry kExact[] = {
 #include "exact_table.inc"
 };
 #undef PB_EXACT
+}  // namespace
+namespace pb {
+#define PB_EXACT_SPLIT(S, KT) \
+  extern template int launch_exact_split<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t);
+#include "exact_split_table.inc"
+#undef PB_EXACT_SPLIT
+}  // namespace pb
+namespace {
+// the same form with one series over the four waves of a workgroup (fista_exact_split.h): S samples per lane of each wave
+#define PB_EXACT_SPLIT(S, KT) {S, KT, &pb::launch_exact_split<S, KT>},
+const ExactEntry kExactSplit[] = {
+#include "exact_split_table.inc"
+};
+#undef PB_EXACT_SPLIT
 
 // window lengths the register-resident forms carry (increment ring of wind - 2 slots in LDS)
 inline bool ring_wind(int wind) { return wind == 4 || wind == 6 || wind == 8; }
@@ -196,6 +211,24 @@ const ExactEntry* pick_exact(int N, int K) {
     if (!best || (int64_t)e.S * e.KT < (int64_t)best->S * best->KT) best = &e;
   }
   return best;
+}
+// four waves per series: the shapes beyond the one-wave entries (641 .. 1 280 scans), cheapest entry that holds (N, K)
+const ExactEntry* pick_exact_split(int N, int K) {
+  if (pick_exact(N, K)) return nullptr;
+  const ExactEntry* best = nullptr;
+  const int s_need = (N + 64 * pb::SPLIT_WAVES - 1) / (64 * pb::SPLIT_WAVES);
+  for (const ExactEntry& e : kExactSplit) {
+    if (e.S < s_need || e.KT < K) continue;
+    if (!best || (int64_t)e.S * e.KT < (int64_t)best->S * best->KT) best = &e;
+  }
+  return best;
+}
+// the float64 register form that carries a call: one wave per series, else four; the window rule of both is wind = 6
+const ExactEntry* pick_exact_any(int N, int K, int stop_mode, int wind, bool* split) {
+  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
+  const ExactEntry* e = pick_exact(N, K);
+  if (split) *split = !e;
+  return e ? e : pick_exact_split(N, K);
 }
 
 }  // namespace
@@ -1030,11 +1063,9 @@ static int solve_impl(const float* y_dev, int64_t ldy, int y_rep, double* w_dev,
   //   (list 0: the call's one list -- matrix-pipe forms for its dense head, vector forms for the rest --, 1 / 2: the
   //   measurement aids "matrix-pipe candidates only" / "vector candidates only", 3: handed-back problems);
   //   bound(cand) = grid bound of a candidate in slots
-  // (the ill-conditioned class: register-resident float64 kernel where the shape has an entry; its window rule is wind = 6)
-  auto ill_exact = [&]() -> const ExactEntry* {
-    const ExactEntry* e = pick_exact(N, K);
-    return (e && stop_mode == PB_STOP_WINDOW && wind != 6) ? nullptr : e;
-  };
+  // (the ill-conditioned class: register-resident float64 kernel, one or four waves per series, where the shape has an
+  // entry; its window rule is wind = 6)
+  auto ill_exact = [&]() -> const ExactEntry* { return pick_exact_any(N, K, stop_mode, wind, nullptr); };
   const int64_t nd_g = gen_lds_doubles(N, K, stop_mode, wind);
   auto run_partition = [&](const pb::PlanSpec& dense, const pb::PlanSpec& sparse, const pb::PlanSpec& flagged, bool no_dense_class,
                            auto&& launch_form, auto&& has_form, auto&& bound) -> int {
@@ -1126,7 +1157,7 @@ static int solve_impl(const float* y_dev, int64_t ldy, int y_rep, double* w_dev,
         b.grid_slots = P;
         if (ee->fn(b, taps_host, K, wj, stop_mode, user) != 0)
           return fail(PB_ERR_INVALID, "pb_fista_solve: float64 kernel rejected the launch (ill-conditioned series)");
-        rc = check_launch("fista_exact_kernel(ill-conditioned series)");
+        rc = check_launch("fista_exact_kernel / fista_exact_split_kernel(ill-conditioned series)");
         if (rc != PB_OK) return rc;
       } else if (taps_dev && nd_g <= LDS_DOUBLES_MAX) {
         const int wgs = P < 2048 ? P : 2048;
@@ -1402,10 +1433,13 @@ int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
     return fail(PB_ERR_INVALID, "pb_fista_solve_d: wind must be >= 2");
   // register-resident float64 form (one problem per wave) when the shape has an entry and
   // the host copy of the taps is given; the window rule there is the reference default wind = 6
-  const ExactEntry* ee = (taps_host && !(flags & PB_FLAG_FORCE_GENERIC)) ? pick_exact(N, K) : nullptr;
-  if (ee && stop_mode == PB_STOP_WINDOW && wind != 6) ee = nullptr;
-  if (!ee && (flags & PB_FLAG_FORCE_FAST))
-    return fail(PB_ERR_INVALID, "pb_fista_solve_d: no register-resident float64 kernel for N=%d K=%d", N, K);
+  // (one problem per wave up to 640 scans, one per workgroup of four waves up to 1 280: fista_exact_split.h)
+  bool split = false;
+  const ExactEntry* ee = (taps_host && !(flags & PB_FLAG_FORCE_GENERIC)) ? pick_exact_any(N, K, stop_mode, wind, &split) : nullptr;
+  // PB_FLAG_FORCE_FAST keeps the meaning it had before the four-wave form existed: the one-problem-per-wave form or an
+  // error (callers and tests pin that it fails beyond 640 scans); the four-wave form is reached by the dispatch only
+  if ((!ee || split) && (flags & PB_FLAG_FORCE_FAST))
+    return fail(PB_ERR_INVALID, "pb_fista_solve_d: no register-resident float64 kernel with one problem per wave for N=%d K=%d", N, K);
   const int64_t nd = gen_lds_doubles(N, K, stop_mode, wind);
   if (!ee && nd > LDS_DOUBLES_MAX)
     return fail(PB_ERR_INVALID, "pb_fista_solve_d: N=%d K=%d wind=%d exceeds LDS", N, K, wind);
@@ -1419,7 +1453,7 @@ int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
   if (ee) {
     if (ee->fn(a, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
       return fail(PB_ERR_INVALID, "pb_fista_solve_d: launch rejected");
-    return check_launch("fista_exact_kernel");
+    return check_launch(split ? "fista_exact_split_kernel" : "fista_exact_kernel");
   }
   const size_t lds = (size_t)nd * sizeof(double);
   if (J_dev)
@@ -1429,6 +1463,14 @@ int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
     hipLaunchKernelGGL((pb::fista_generic_kernel<false, true>), dim3(P), dim3(pb::GEN_THREADS), lds,
                        (hipStream_t)stream, a, taps_dev, K, wind);
   return check_launch("fista_generic_kernel(f64)");
+}
+
+int pb_fista_which_kernel_d(int N, int K, int with_cost_trace, int stop_mode, int wind) {
+  (void)with_cost_trace;                                // (every float64 form writes the cost trace)
+  if (N < 1 || K < 1) return 0;
+  bool split = false;
+  if (pick_exact_any(N, K, stop_mode, wind, &split)) return split ? 8 : 7;
+  return gen_lds_doubles(N, K, stop_mode, wind) <= LDS_DOUBLES_MAX ? 0 : -1;
 }
 
 int pb_auto_lbda_supported(int N, int K, int wind) { return (wind == pb::AUTO_WIND && pick_auto(N, K)) ? 1 : 0; }

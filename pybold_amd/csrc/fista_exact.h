@@ -83,30 +83,14 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
   return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
 }
 
-// ---- the pass body, shared by fista_exact_kernel and auto_lbda_kernel (fista_auto.h) --------------------------------
-// Both kernels keep y, w, the mask and the window-rule state in VGPRs and call the two halves below, once per pass;
-// the cost trace of fista_exact_kernel and the residual statistics of auto_lbda_kernel sit between them (or after the
-// first alone), on the residual the forward half returns.
-
-// forward half: z = cumsum(w), x = h * z, r = (x - y) on the samples of the series (0 on the padding)
+// ---- the per-lane pieces of the pass, shared with the four-wave form (fista_exact_split.h) -------------------------------
+// window of z for the FIR: own samples at [H, H+S), below them the last H samples of the lanes below (0 before lane 0)
 template <int S, int KT>
-__device__ __forceinline__ void exact_forward(const double (&w)[S], const double (&y)[S], const double (&mk)[S],
-                                              const TapsD<KT>& taps, double (&r)[S]) {
+__device__ __forceinline__ void exact_window_below(const double (&z)[S], double (&Z)[KT - 1 + S]) {
   constexpr int H = KT - 1;
   constexpr int D = (H + S - 1) / S;        // neighbour lanes that contribute halo
   static_assert(D <= 63, "halo spans more than the wave");
-  // ---- z = cumsum(w) ----------------------------------------------------
-  double z[S];
-  z[0] = w[0];
-#pragma unroll
-  for (int j = 1; j < S; ++j) z[j] = z[j - 1] + w[j];
-  {
-    const double off = dpp_f64<DPP_WAVE_SHR1>(wave_prefix_incl_f64(z[S - 1]));
-#pragma unroll
-    for (int j = 0; j < S; ++j) z[j] += off;
-  }
   // ---- window of z: own samples at [H, H+S), halo below -------------------
-  double Z[H + S];
   static_for<0, S>([&](auto jc) { Z[H + decltype(jc)::value] = z[decltype(jc)::value]; });
   {
     double sh[S];
@@ -123,30 +107,14 @@ __device__ __forceinline__ void exact_forward(const double (&w)[S], const double
       });
     });
   }
-  // ---- r = h * z - y -------------------------------------------------------
-  static_for<0, S>([&](auto jc) { r[decltype(jc)::value] = -y[decltype(jc)::value]; });
-  static_for<0, KT>([&](auto mc) {          // tap-major: S independent chains
-    constexpr int m = decltype(mc)::value;
-    static_for<0, S>([&](auto jc) {
-      constexpr int j = decltype(jc)::value;
-      r[j] = fma(taps.h[m], Z[H + j - m], r[j]);
-    });
-  });
-#pragma unroll
-  for (int j = 0; j < S; ++j) r[j] *= mk[j];
 }
 
-// backward half: g = revcumsum(K^T r), gradient step, prox, momentum; with a stop rule (STOP 1: _loops_deconv, 2: window,
-// wind = 6) the two wave-wide sums of its criterion come back in num / den (and the window state moves on one iteration)
-template <int S, int KT, int STOP>
-__device__ __forceinline__ void exact_backward(const double (&r)[S], double (&w)[S], const TapsD<KT>& taps, double nstep,
-                                               double th, const double* beta_k, double (&uprev)[STOP == 2 ? S : 1],
-                                               double (&d1)[STOP == 2 ? S : 1], double (&d2)[STOP == 2 ? S : 1],
-                                               double (&d3)[STOP == 2 ? S : 1], double& num, double& den) {
+// window of r for the correlation: own samples at [0, S), above them the first H samples of the lanes above (0 past lane 63)
+template <int S, int KT>
+__device__ __forceinline__ void exact_window_above(const double (&r)[S], double (&R)[S + KT - 1]) {
   constexpr int H = KT - 1;
   constexpr int D = (H + S - 1) / S;
   // ---- window of r: own samples at [0, S), halo above ----------------------
-  double R[S + H];
   static_for<0, S>([&](auto jc) { R[decltype(jc)::value] = r[decltype(jc)::value]; });
   {
     double sh[S];
@@ -163,8 +131,29 @@ __device__ __forceinline__ void exact_backward(const double (&r)[S], double (&w)
       });
     });
   }
-  // ---- g = revcumsum(K^T r) ---------------------------------------------------
-  double g[S];
+}
+
+// r = (h * z - y) on the samples of the series from the window Z of z: own samples at [H, H+S), halo below them
+template <int S, int KT>
+__device__ __forceinline__ void exact_fir_residual(const double (&Z)[KT - 1 + S], const double (&y)[S], const double (&mk)[S],
+                                                   const TapsD<KT>& taps, double (&r)[S]) {
+  constexpr int H = KT - 1;
+  // ---- r = h * z - y -------------------------------------------------------
+  static_for<0, S>([&](auto jc) { r[decltype(jc)::value] = -y[decltype(jc)::value]; });
+  static_for<0, KT>([&](auto mc) {          // tap-major: S independent chains
+    constexpr int m = decltype(mc)::value;
+    static_for<0, S>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      r[j] = fma(taps.h[m], Z[H + j - m], r[j]);
+    });
+  });
+#pragma unroll
+  for (int j = 0; j < S; ++j) r[j] *= mk[j];
+}
+
+// g = K^T r from the window R of r (own samples at [0, S), halo above them), summed from the lane's last sample down
+template <int S, int KT>
+__device__ __forceinline__ void exact_corr_suffix(const double (&R)[S + KT - 1], const TapsD<KT>& taps, double (&g)[S]) {
 #pragma unroll
   for (int j = 0; j < S; ++j) g[j] = 0.0;
   static_for<0, KT>([&](auto mc) {
@@ -176,12 +165,15 @@ __device__ __forceinline__ void exact_backward(const double (&r)[S], double (&w)
   });
 #pragma unroll
   for (int j = S - 2; j >= 0; --j) g[j] += g[j + 1];
-  {
-    const double off = wave_suffix_excl_f64(g[0]);         // sum of the lanes above, exactly 0 above the last sample
-#pragma unroll
-    for (int j = 0; j < S; ++j) g[j] += off;
-  }
+}
 
+// gradient step, prox, momentum on the lane's samples; with a stop rule the LANE's share of the two sums of its criterion
+// comes back in num / den (and the window state moves on one iteration)
+template <int S, int STOP>
+__device__ __forceinline__ void exact_update(const double (&g)[S], double (&w)[S], double nstep, double th, const double* beta_k,
+                                             double (&uprev)[STOP == 2 ? S : 1], double (&d1)[STOP == 2 ? S : 1],
+                                             double (&d2)[STOP == 2 ? S : 1], double (&d3)[STOP == 2 ? S : 1], double& num,
+                                             double& den) {
   // ---- gradient step, prox, momentum; stop rules ------------------------------
   const double beta = *beta_k;                // (read here, after the scans: the taps fill the scalar registers)
   const double nb1 = -(1.0 + beta);
@@ -221,6 +213,55 @@ __device__ __forceinline__ void exact_backward(const double (&r)[S], double (&w)
       }
       w[j] = wn;
     }
+  }
+}
+
+// ---- the pass body, shared by fista_exact_kernel and auto_lbda_kernel (fista_auto.h) --------------------------------
+// Both kernels keep y, w, the mask and the window-rule state in VGPRs and call the two halves below, once per pass;
+// the cost trace of fista_exact_kernel and the residual statistics of auto_lbda_kernel sit between them (or after the
+// first alone), on the residual the forward half returns.
+
+// forward half: z = cumsum(w), x = h * z, r = (x - y) on the samples of the series (0 on the padding)
+template <int S, int KT>
+__device__ __forceinline__ void exact_forward(const double (&w)[S], const double (&y)[S], const double (&mk)[S],
+                                              const TapsD<KT>& taps, double (&r)[S]) {
+  constexpr int H = KT - 1;
+  // ---- z = cumsum(w) ----------------------------------------------------
+  double z[S];
+  z[0] = w[0];
+#pragma unroll
+  for (int j = 1; j < S; ++j) z[j] = z[j - 1] + w[j];
+  {
+    const double off = dpp_f64<DPP_WAVE_SHR1>(wave_prefix_incl_f64(z[S - 1]));
+#pragma unroll
+    for (int j = 0; j < S; ++j) z[j] += off;
+  }
+  double Z[H + S];
+  exact_window_below<S, KT>(z, Z);
+  exact_fir_residual<S, KT>(Z, y, mk, taps, r);
+}
+
+// backward half: g = revcumsum(K^T r), gradient step, prox, momentum; with a stop rule (STOP 1: _loops_deconv, 2: window,
+// wind = 6) the two wave-wide sums of its criterion come back in num / den (and the window state moves on one iteration)
+template <int S, int KT, int STOP>
+__device__ __forceinline__ void exact_backward(const double (&r)[S], double (&w)[S], const TapsD<KT>& taps, double nstep,
+                                               double th, const double* beta_k, double (&uprev)[STOP == 2 ? S : 1],
+                                               double (&d1)[STOP == 2 ? S : 1], double (&d2)[STOP == 2 ? S : 1],
+                                               double (&d3)[STOP == 2 ? S : 1], double& num, double& den) {
+  constexpr int H = KT - 1;
+  double R[S + H];
+  exact_window_above<S, KT>(r, R);
+  // ---- g = revcumsum(K^T r) ---------------------------------------------------
+  double g[S];
+  exact_corr_suffix<S, KT>(R, taps, g);
+  {
+    const double off = wave_suffix_excl_f64(g[0]);         // sum of the lanes above, exactly 0 above the last sample
+#pragma unroll
+    for (int j = 0; j < S; ++j) g[j] += off;
+  }
+
+  exact_update<S, STOP>(g, w, nstep, th, beta_k, uprev, d1, d2, d3, num, den);
+  if constexpr (STOP != 0) {
     num = seg_allsum_f64<64>(num);
     den = seg_allsum_f64<64>(den);
   }

@@ -198,13 +198,25 @@ KERNEL_NAMES = {0: "fista_generic_kernel (LDS)", 1: "fista_fast_kernel (register
                 5: "fista_mfma2_kernel (register-resident, 16 problems per two waves -- every series split over two "
                    "SIMDs --, both operators on the matrix pipe)",
                 6: "fista_mfma4_kernel (register-resident, 16 problems per workgroup of four waves -- every series split over "
-                   "the four SIMDs of a compute unit --, both operators on the matrix pipe)"}
+                   "the four SIMDs of a compute unit --, both operators on the matrix pipe)",
+                7: "fista_exact_kernel (register-resident, float64 end to end, one problem per wave)",
+                8: "fista_exact_split_kernel (register-resident, float64 end to end, one problem per workgroup of four "
+                   "waves)"}
 
 
 def which_kernel(n_scans, n_taps, n_problems, want_J=False, stop=None, wind=6):
     """Name of the kernel :func:`fista_solve` dispatches to for this call shape."""
     return KERNEL_NAMES[_lib.load().pb_fista_which_kernel(
         int(n_scans), int(n_taps), int(n_problems), int(bool(want_J)), _STOP[stop], int(wind))]
+
+
+def which_kernel_f64(n_scans, n_taps, want_J=False, stop=None, wind=6):
+    """Name of the kernel :func:`fista_solve` dispatches to for a float64 ``Y`` of this shape (``pb_fista_solve_d``: the
+    1-D calls of the API, ``deconv(lbda=None)``); raises ``ValueError`` where not even the LDS kernel holds the shape."""
+    form = _lib.load().pb_fista_which_kernel_d(int(n_scans), int(n_taps), int(bool(want_J)), _STOP[stop], int(wind))
+    if form < 0:
+        raise ValueError("no float64 kernel for %d scans, %d taps, wind=%d: the series exceeds LDS" % (n_scans, n_taps, wind))
+    return KERNEL_NAMES[form]
 
 
 def launch_plan(n_scans, n_taps, n_problems, stop=None, wind=6, force=None):
@@ -225,7 +237,8 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
 
     Y     float32 CUDA ``(V, N)`` (the batch layout; register-resident kernels), or
           float64 CUDA ``(V, N)``: float64 end to end (``pb_fista_solve_d``: register-resident
-          one-problem-per-wave kernel for N <= 640, K <= 32, else the LDS kernel), the
+          kernels for K <= 32 -- one problem per wave for N <= 640, one per workgroup of four
+          waves for N <= 1280 --, else the LDS kernel; :func:`which_kernel_f64`), the
           reference's arithmetic -- what the 1-D calls of the API use
     hrf   1-D array of K taps (host)
     lbda  scalar, or array/tensor of ``V * y_rep`` per-problem values
@@ -275,7 +288,7 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
     if f64:
         if force not in (None, "generic", "fast"):
             raise ValueError("float64 y: force must be None, 'fast' (register-resident float64 "
-                             "kernel) or 'generic' (LDS kernel)")
+                             "kernel, one problem per wave) or 'generic' (LDS kernel)")
         with torch.cuda.device(dev):
             rc = lib.pb_fista_solve_d(
                 Y.data_ptr(), _ld(Y), int(y_rep), W.data_ptr(), _ld(W), P, N,

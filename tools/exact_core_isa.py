@@ -1,5 +1,6 @@
-"""Instruction-count comparison of fista_exact_kernel between two builds, from the ISA listings `make build/exact_5_32.s
-build/exact_10_32.s` leaves in pybold_amd/csrc/build (hipcc for gfx950, no GPU needed):
+"""Instruction-count comparison of fista_exact_kernel (and, where both builds have its listings, auto_lbda_kernel) between two
+builds, from the ISA listings `make build/exact_5_32.s build/exact_10_32.s [build/auto_5_32.s build/auto_10_32.s]` leaves in
+pybold_amd/csrc/build (hipcc for gfx950, no GPU needed):
 
     python tools/exact_core_isa.py <dir with the parent's exact_*.s / .res> <dir with this tree's> > profiles/exact_core_isa.txt
 
@@ -46,7 +47,9 @@ def main():
     old, new = sys.argv[1], sys.argv[2]
     print("tools/exact_core_isa.py: fista_exact_kernel of this tree (pass body in exact_forward / exact_backward, shared with")
     print("auto_lbda_kernel) against a build of the parent commit.  hipcc for gfx950, no GPU.\n")
-    for name in ("exact_5_32", "exact_10_32"):
+    for name in ("exact_5_32", "exact_10_32", "auto_5_32", "auto_10_32"):
+        if name.startswith("auto") and not all(os.path.exists(os.path.join(d, name + ".s")) for d in (old, new)):
+            continue
         ko, kn = kernels(os.path.join(old, name + ".s")), kernels(os.path.join(new, name + ".s"))
         ro, rn = resources(os.path.join(old, name + ".res")), resources(os.path.join(new, name + ".res"))
         assert sorted(ko) == sorted(kn), "symbols differ"
