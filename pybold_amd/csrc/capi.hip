@@ -23,6 +23,7 @@
 #include "fista_mfma2.h"
 #include "fista_mfma4.h"
 #include "path.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -49,213 +50,6 @@ inline int64_t gen_lds_doubles(int N, int K, int stop_mode, int wind) {
   return 3 * (int64_t)N + K + 2 * pb::GEN_WAVES + (stop_mode == PB_STOP_WINDOW ? (int64_t)wind * N : 0);
 }
 
-// ---- register-resident specialisations --------------------------------------
-typedef int (*fast_launch_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j,
-                              int stop, hipStream_t);
-typedef int (*fast_launch_pp_fn)(const pb::FistaArgs&, int stop, hipStream_t);
-// the pair form and the three matrix-pipe forms
-typedef int (*launch_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j, hipStream_t);
-typedef int (*pair_cert_fn)(const pb::FistaArgs&, const double* taps, int K, hipStream_t);
-typedef int (*pair_split_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j, bool cert, hipStream_t);
-
-struct FastEntry {
-  int S, KT;
-  fast_launch_fn fn;
-  fast_launch_pp_fn fn_pp;
-  launch_fn fn_pair;          // two-problems-per-row kernel (S <= 20, KT <= 32 only), else nullptr
-  launch_fn fn_pair_ffa;      // the same with 2-parallel fast FIRs (fista_pair_ffa.h)
-  int (*fn_pair_dev)(const pb::FistaArgs&, hipStream_t);   // ... reading ONE shared HRF from device memory
-  pair_cert_fn fn_pair_cert;  // ... carrying the window rule (wind = 6) as a no-fire certificate
-  pair_split_fn fn_pair_split; // ... ONE series of 16 S < N <= 32 S scans per row (its halves in the two slots)
-};
-
-}  // namespace
-
-// instantiated in fast_inst.hip, one translation unit per table entry
-namespace pb {
-#define PB_FAST(S, KT)                                                                              \
-  extern template int launch_fast<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t); \
-  extern template int launch_fast_pp<S, KT>(const FistaArgs&, int, hipStream_t);            \
-  extern template int launch_pair<S, KT>(const FistaArgs&, const double*, int, bool, hipStream_t); \
-  extern template int launch_pair_ffa<S, KT>(const FistaArgs&, const double*, int, bool, hipStream_t); \
-  extern template int launch_pair_ffa_dev<S, KT>(const FistaArgs&, hipStream_t);                  \
-  extern template int launch_pair_ffa_cert<S, KT>(const FistaArgs&, const double*, int, hipStream_t); \
-  extern template int launch_pair_ffa_split<S, KT>(const FistaArgs&, const double*, int, bool, bool, hipStream_t);
-#include "fast_table.inc"
-#undef PB_FAST
-}  // namespace pb
-
-namespace pb {
-#define PB_MFMA(NB) extern template int launch_mfma<NB>(const FistaArgs&, const double*, int, bool, hipStream_t);
-PB_MFMA(5) PB_MFMA(6) PB_MFMA(7) PB_MFMA(8) PB_MFMA(9) PB_MFMA(10)
-#undef PB_MFMA
-}
-namespace pb {
-#define PB_MFMA2(A, B) extern template int launch_mfma2<A, B>(const FistaArgs&, const double*, int, bool, hipStream_t);
-PB_MFMA2(2, 3) PB_MFMA2(3, 3) PB_MFMA2(3, 4) PB_MFMA2(4, 4) PB_MFMA2(4, 5) PB_MFMA2(5, 5) PB_MFMA2(5, 6) PB_MFMA2(6, 6)
-PB_MFMA2(6, 7) PB_MFMA2(7, 7) PB_MFMA2(7, 8) PB_MFMA2(8, 8) PB_MFMA2(8, 9) PB_MFMA2(9, 9) PB_MFMA2(9, 10) PB_MFMA2(10, 10)
-#undef PB_MFMA2
-#define PB_MFMA4(A) extern template int launch_mfma4<A>(const FistaArgs&, const double*, int, bool, hipStream_t);
-PB_MFMA4(6) PB_MFMA4(7) PB_MFMA4(8) PB_MFMA4(9) PB_MFMA4(10)
-#undef PB_MFMA4
-}
-namespace {
-// the matrix-pipe form with one series split over the two waves of a workgroup (fista_mfma2.h): nb = ceil(N / 32)
-// blocks of 32 samples (it keeps the carry tile: its waves are bound by the vector work of the exchange, not by
-// their matrix instructions -- the sum-slot form of fista_mfma.h measured 4 % slower there), 5 <= nb <= 20
-// (129 .. 640 scans), floor(nb / 2) of them in the left wave; K <= 33; plain solves, the cost
-// trace and the window rule (wind = 6) as a no-fire certificate; the shared-HRF z-step plain only
-// (34 <= K <= 65: three near tiles -- series of 225+ scans (four blocks per wave; the one-wave form carries shorter ones, and
-// everything up to 310 scans but the certificate), plain solves, the cost trace, the certificate and the _loops_deconv rule;
-// `two_tiles_only`: K <= 33)
-launch_fn pick_mfma2(int N, int K, bool two_tiles_only) {
-  static const launch_fn tab[] = {
-      &pb::launch_mfma2<2, 3>, &pb::launch_mfma2<3, 3>, &pb::launch_mfma2<3, 4>, &pb::launch_mfma2<4, 4>,
-      &pb::launch_mfma2<4, 5>, &pb::launch_mfma2<5, 5>, &pb::launch_mfma2<5, 6>, &pb::launch_mfma2<6, 6>,
-      &pb::launch_mfma2<6, 7>, &pb::launch_mfma2<7, 7>, &pb::launch_mfma2<7, 8>, &pb::launch_mfma2<8, 8>,
-      &pb::launch_mfma2<8, 9>, &pb::launch_mfma2<9, 9>, &pb::launch_mfma2<9, 10>, &pb::launch_mfma2<10, 10>};
-  const int nb = (N + 31) / 32;
-  if (K < 1 || K > 65 || nb < 5 || nb > 20) return nullptr;
-  if (K > 33 && (two_tiles_only || N <= 224)) return nullptr;   // (three near tiles: four blocks at least per wave)
-  return tab[nb - 5];
-}
-// the same with one series split over the FOUR waves of a workgroup (fista_mfma4.h): 641 .. 1 280 scans, A = ceil(N / 128)
-// blocks per wave (6 .. 10); K <= 33 with two near tiles: the call shapes of the two-wave form; 34 <= K <= 65 with three: plain
-// solves, the cost trace, the certificate and the _loops_deconv rule (`two_tiles_only`: K <= 33)
-launch_fn pick_mfma4(int N, int K, bool two_tiles_only) {
-  static const launch_fn tab[] = {&pb::launch_mfma4<6>, &pb::launch_mfma4<7>, &pb::launch_mfma4<8>, &pb::launch_mfma4<9>,
-                                  &pb::launch_mfma4<10>};
-  if (K < 1 || K > 65 || (K > 33 && two_tiles_only) || N <= 640 || N > 1280) return nullptr;
-  return tab[(N + 127) / 128 - 6];
-}
-// the matrix-pipe form (fista_mfma.h): NB = ceil(N / 31) blocks of 31 samples + one sum slot, 129 <= N <= 310; K <= 33
-// with two near tiles (every variant), 34 <= K <= 64 with three (plain solves and the cost trace only: `stop_rule` = the
-// window-rule certificate or the _loops_deconv rule rides the kernel)
-constexpr int MFMA_K2 = 33, MFMA_K3 = 64;
-constexpr int MFMA1_NMAX = 10 * pb::MFMA_SPAN;   // longer series (up to 640 scans) run on the split form (fista_mfma2.h)
-launch_fn pick_mfma(int N, int K, bool stop_rule) {
-  static const launch_fn tab[] = {&pb::launch_mfma<5>, &pb::launch_mfma<6>, &pb::launch_mfma<7>,
-                                  &pb::launch_mfma<8>, &pb::launch_mfma<9>, &pb::launch_mfma<10>};
-  const int nb = (N + pb::MFMA_SPAN - 1) / pb::MFMA_SPAN;
-  if (K < 1 || K > MFMA_K3 || (K > MFMA_K2 && stop_rule) || N <= 128 || nb > 10) return nullptr;   // (129 .. 310 scans: 5 .. 10 blocks)
-  return tab[nb - 5];
-}
-}  // namespace
-namespace pb {
-#define PB_WIDE(S, KT)                                                                            \
-  extern template int launch_wide<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t); \
-  extern template int launch_wide_pp<S, KT>(const FistaArgs&, int, hipStream_t);
-#include "wide_table.inc"
-#undef PB_WIDE
-}  // namespace pb
-namespace {
-
-typedef int (*wide_launch_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j, int stop,
-                              hipStream_t);
-struct WideEntry {
-  int S, KT;
-  wide_launch_fn fn;
-  fast_launch_pp_fn fn_pp;
-};
-#define PB_WIDE(S, KT) {S, KT, &pb::launch_wide<S, KT>, &pb::launch_wide_pp<S, KT>},
-const WideEntry kWide[] = {
-#include "wide_table.inc"
-};
-#undef PB_WIDE
-
-typedef int (*exact_launch_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j, int stop,
-                               hipStream_t);
-struct ExactEntry {
-  int S, KT;
-  exact_launch_fn fn;
-};
-}  // namespace
-namespace pb {
-#define PB_EXACT(S, KT) \
-  extern template int launch_exact<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t);
-#include "exact_table.inc"
-#undef PB_EXACT
-}  // namespace pb
-namespace {
-#define PB_EXACT(S, KT) {S, KT, &pb::launch_exact<S, KT>},
-const ExactEntry kExact[] = {
-#include "exact_table.inc"
-};
-#undef PB_EXACT
-}  // namespace
-namespace pb {
-#define PB_EXACT_SPLIT(S, KT) \
-  extern template int launch_exact_split<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t);
-#include "exact_split_table.inc"
-#undef PB_EXACT_SPLIT
-}  // namespace pb
-namespace {
-// the same form with one series over the four waves of a workgroup (fista_exact_split.h): S samples per lane of each wave
-#define PB_EXACT_SPLIT(S, KT) {S, KT, &pb::launch_exact_split<S, KT>},
-const ExactEntry kExactSplit[] = {
-#include "exact_split_table.inc"
-};
-#undef PB_EXACT_SPLIT
-
-// window lengths the register-resident forms carry (increment ring of wind - 2 slots in LDS)
-inline bool ring_wind(int wind) { return wind == 4 || wind == 6 || wind == 8; }
-// an entry of S samples per lane carries the call's stop rule: the window rule needs its increment ring (S <= 20)
-inline bool ring_fits(int S, int stop_mode, int wind) { return stop_mode != PB_STOP_WINDOW || (ring_wind(wind) && S <= 20); }
-
-// all-float64 register-resident form (one problem per wave): cheapest entry that holds (N, K)
-const ExactEntry* pick_exact(int N, int K) {
-  const ExactEntry* best = nullptr;
-  const int s_need = (N + 63) / 64;
-  for (const ExactEntry& e : kExact) {
-    if (e.S < s_need || e.KT < K) continue;
-    if (!best || (int64_t)e.S * e.KT < (int64_t)best->S * best->KT) best = &e;
-  }
-  return best;
-}
-// four waves per series: the shapes beyond the one-wave entries (641 .. 1 280 scans), cheapest entry that holds (N, K)
-const ExactEntry* pick_exact_split(int N, int K) {
-  if (pick_exact(N, K)) return nullptr;
-  const ExactEntry* best = nullptr;
-  const int s_need = (N + 64 * pb::SPLIT_WAVES - 1) / (64 * pb::SPLIT_WAVES);
-  for (const ExactEntry& e : kExactSplit) {
-    if (e.S < s_need || e.KT < K) continue;
-    if (!best || (int64_t)e.S * e.KT < (int64_t)best->S * best->KT) best = &e;
-  }
-  return best;
-}
-// the float64 register form that carries a call: one wave per series, else four; the window rule of both is wind = 6
-const ExactEntry* pick_exact_any(int N, int K, int stop_mode, int wind, bool* split) {
-  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
-  const ExactEntry* e = pick_exact(N, K);
-  if (split) *split = !e;
-  return e ? e : pick_exact_split(N, K);
-}
-
-}  // namespace
-namespace pb {
-#define PB_EXACT(S, KT) extern template int launch_auto<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);
-#include "exact_table.inc"
-#undef PB_EXACT
-}  // namespace pb
-namespace {
-// the device-resident lambda search (fista_auto.h): the (S, KT) pairs of the all-float64 form
-typedef int (*auto_launch_fn)(const pb::AutoArgs&, const double* taps, int K, bool early_stopping, hipStream_t);
-struct AutoEntry {
-  int S, KT;
-  auto_launch_fn fn;
-};
-#define PB_EXACT(S, KT) {S, KT, &pb::launch_auto<S, KT>},
-const AutoEntry kAuto[] = {
-#include "exact_table.inc"
-};
-#undef PB_EXACT
-const AutoEntry* pick_auto(int N, int K) {
-  const ExactEntry* e = (N >= 1 && K >= 1) ? pick_exact(N, K) : nullptr;
-  if (!e) return nullptr;
-  for (const AutoEntry& a : kAuto)
-    if (a.S == e->S && a.KT == e->KT) return &a;
-  return nullptr;
-}
 // outer iterations per launch when the caller leaves the choice to the library: about 65536 inner iterations per wave
 // slot and launch -- 65536 / nb_sub_iter for a batch the machine holds at once (2048 waves: 256 compute units, four
 // SIMDs, two waves of this kernel each), fewer in proportion for a larger one, whose launch runs its waves in rounds
@@ -281,104 +75,6 @@ int mad_daub_impl(const TY* y_dev, int64_t ldy, int V, int N, double c, double* 
                      y_dev, ldy, N, c, n2, sigma_dev);
   return check_launch(name);
 }
-
-const WideEntry* pick_wide(int N, int K) {
-  const WideEntry* best = nullptr;
-  const int s_need = (N + 63) / 64;
-  for (const WideEntry& e : kWide) {
-    if (e.S < s_need || e.KT < K) continue;
-    if (!best || (int64_t)e.S * e.KT < (int64_t)best->S * best->KT) best = &e;
-  }
-  return best;
-}
-
-template <int S, int KT>
-constexpr launch_fn pair_or_null() {
-  if constexpr (S <= 20 && KT <= 32) return &pb::launch_pair<S, KT>; else return nullptr;
-}
-template <int S, int KT>
-constexpr launch_fn pair_ffa_or_null() {
-  if constexpr (S <= 20 && KT <= 32) return &pb::launch_pair_ffa<S, KT>; else return nullptr;
-}
-template <int S, int KT>
-constexpr int (*pair_dev_or_null())(const pb::FistaArgs&, hipStream_t) {
-  if constexpr (S <= 20 && KT <= 32) return &pb::launch_pair_ffa_dev<S, KT>; else return nullptr;
-}
-template <int S, int KT>
-constexpr pair_cert_fn pair_cert_or_null() {
-  if constexpr (S <= 20 && KT <= 32) return &pb::launch_pair_ffa_cert<S, KT>; else return nullptr;
-}
-template <int S, int KT>
-constexpr pair_split_fn pair_split_or_null() {
-  if constexpr (S <= 20 && KT <= 32) return &pb::launch_pair_ffa_split<S, KT>; else return nullptr;
-}
-#define PB_FAST(S, KT)                                                                             \
-  {S, KT, &pb::launch_fast<S, KT>, &pb::launch_fast_pp<S, KT>, pair_or_null<S, KT>(),             \
-   pair_ffa_or_null<S, KT>(), pair_dev_or_null<S, KT>(), pair_cert_or_null<S, KT>(),              \
-   pair_split_or_null<S, KT>()},
-const FastEntry kFast[] = {
-#include "fast_table.inc"
-};
-#undef PB_FAST
-
-const FastEntry* pick_fast(int N, int K) {
-  const FastEntry* best = nullptr;
-  const int s_need = (N + 15) / 16;
-  for (const FastEntry& e : kFast) {
-    if (e.S < s_need || e.KT < K) continue;
-    if (!best || (int64_t)e.S * e.KT < (int64_t)best->S * best->KT) best = &e;
-  }
-  return best;
-}
-
-// series of 16 S < N <= 32 S scans: the pair form with the series' two halves in the slots of a row
-const FastEntry* pick_split(int N, int K) {
-  const FastEntry* best = nullptr;
-  const FastEntry* whole = pick_fast(N, K);
-  if (whole && whole->fn_pair_ffa) return nullptr;      // the series fits a slot: two PROBLEMS per row
-  for (const FastEntry& e : kFast) {
-    if (!e.fn_pair_split || e.KT < K || N <= 16 * e.S || N > 32 * e.S) continue;
-    if (!best || (int64_t)e.S * e.KT < (int64_t)best->S * best->KT) best = &e;
-  }
-  return best;
-}
-// below this many series the one-problem-per-wave / single-row forms finish first (latency-bound)
-constexpr int SPLIT_MIN_P = 1024;
-
-// Plain solves (no stop rule) of a shape the matrix-pipe form serves AND some vector form can back up
-// (remainders, re-solves of what its guards hand back): they go to the matrix pipe before the split-pair form
-// is considered -- 305..310 scans fit ten blocks of 31 samples but have no single-slot pair entry, and one
-// matrix-pipe wave beats the pair form over two slots.
-bool mfma_serves_plain(int N, int K) {
-  return pick_mfma(N, K, false) != nullptr && (pick_fast(N, K) != nullptr || pick_wide(N, K) != nullptr);
-}
-// without a single-row entry (305..310 scans and more than 32 taps) the remainder of the whole rounds goes to the
-// one-problem-per-wave form when it is small, else everything runs on the matrix pipe (a partial last pass)
-double wave_slots();
-int mfma_wide_base(int P, bool one_launch) {
-  const int round = (int)wave_slots() * 8;
-  const int base = (P / round) * round;
-  return (one_launch || P - base > round / 4) ? P : base;
-}
-
-// ---- launch plans: plan.h (host + device); here the host-side wrappers with this device's wave slots --------
-using pb::Piece; using pb::Plan;
-using pb::FORM_GENERIC; using pb::FORM_FAST1; using pb::FORM_PAIR; using pb::FORM_WIDE; using pb::FORM_MFMA; using pb::FORM_MFMA2;
-using pb::MFMA2_MIN_R; using pb::MFMA2_BESIDE_CHUNKS;
-
-double wave_slots() {
-  static const double slots = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-      return 2048.0;
-    return (double)prop.multiProcessorCount * 4.0 * 2.0;
-  }();
-  return slots;
-}
-int best_form(int P, bool has_pair, bool has_wide, double* cost = nullptr) { return pb::best_form(P, has_pair, has_wide, wave_slots(), cost); }
-Plan plan_plain(int P, bool has_pair, bool has_wide, bool one_launch) { return pb::plan_plain(P, has_pair, has_wide, one_launch, wave_slots()); }
-
 // ---- a side stream per device for remainders that fit BESIDE the main launch -----------
 // When a plain solve has between one and two half rounds of pair waves (8 192 < P < 16 384
 // problems on MI355X), a single launch leaves some SIMDs with two 8-problem waves and the
@@ -426,48 +122,6 @@ bool stream_is_capturing(hipStream_t st) {
   }
   return cs != hipStreamCaptureStatusNone;
 }
-
-int plan_pieces(int P, bool has_pair, bool has_wide, bool one_launch, bool one_stream, Piece* out) {
-  return pb::plan_pieces(P, has_pair, has_wide, one_launch, one_stream, wave_slots(), out);
-}
-// ... for series of ten blocks; shorter series take one chunk at most: a pass of the one-wave form is cheaper for them
-// relative to a chunk (round 4, sum-slot kernel: N = 240, 10 000 problems 1.36 ms as split pass + two chunks against
-// 1.21 ms as one pass of the one-wave form; N = 300: 1.52 against 1.59 -- profiles/r4_split_form_passes.txt)
-inline int beside_chunks_for(int N) { return N > 9 * pb::MFMA_SPAN ? MFMA2_BESIDE_CHUNKS : 1; }
-// Series of 311 .. 640 scans (10 .. 20 blocks) run on the split form from this many problems on (below, the
-// pair form over two slots or the latency-bound one-problem-per-wave form finish first: N = 600, 4 096 problems
-// 1.58 ms against 1.93, 8 192 2.87 against 1.97 -- profiles/r4_split_form_passes.txt); whole passes of 8 192
-// problems, a remainder above 5/16 of a pass too, a smaller one on the one-problem-per-wave form.
-constexpr int MFMA2_LONG_MIN_P = 5120;
-// (HRFs of 34+ taps have no pair form to compete with, and the one-problem-per-wave form pays for every tap: N = 600, K = 42,
-// 4 096 problems 2.31 ms on the split form against 4.61 -- profiles/r5_long_series_42_taps.txt)
-inline int mfma2_long_min_p(int K) { return K > 33 ? 2048 : MFMA2_LONG_MIN_P; }
-bool mfma2_serves_long(int N, int K) { return N > MFMA1_NMAX && pick_mfma2(N, K, false) != nullptr && pick_wide(N, K) != nullptr; }
-// 225 .. 310 scans with 34+ taps and the window rule: the one-wave form has no certificate beside three near tiles (its state does
-// not fit), the split form has -- it takes such calls like a long series
-bool mfma2_takes_short_cert(int N, int K, int stop_mode, int wind) {     // (... and the _loops_deconv rule, which the one-wave form lacks there too)
-  return K > 33 && ((stop_mode == PB_STOP_WINDOW && wind == 6) || stop_mode == PB_STOP_LOOPS) && N > 224 && N <= MFMA1_NMAX &&
-         pick_mfma2(N, K, false) != nullptr && pick_wide(N, K) != nullptr;
-}
-int mfma2_long_base(int P, bool one_launch) {
-  const int pass = (int)wave_slots() * 4;            // 16 problems x (slots / 2 SIMDs / 2 waves)
-  const int base = (P / pass) * pass;
-  return (one_launch || P - base > pass * 5 / 16) ? P : base;
-}
-// Series of 641 .. 1 280 scans on the four-wave form: a pass is 16 problems per compute unit (4 096 on 256 of them) whatever
-// the batch; whole passes, a remainder above MFMA4_MIN_R of a pass too, a smaller one -- and batches below it -- on the
-// one-problem-per-wave form
-constexpr int MFMA4_MIN_R_NUM = 10, MFMA4_MIN_R_DEN = 16;   // (N = 1 200: 2 048 problems 1.89 ms against 2.31, 3 072 2.59 against 2.30 -- profiles/r5_long_series_1200_scans.txt)
-bool mfma4_serves(int N, int K) { return pick_mfma4(N, K, false) != nullptr && pick_wide(N, K) != nullptr; }
-int mfma4_base(int P, bool one_launch) {
-  const int pass = (int)wave_slots() * 2;            // 16 problems x (slots / 2 per SIMD / 4 SIMDs per workgroup)
-  const int base = (P / pass) * pass;
-  return (one_launch || (int64_t)(P - base) * MFMA4_MIN_R_DEN > (int64_t)pass * MFMA4_MIN_R_NUM) ? P : base;
-}
-int plan_pieces_mfma(int P, bool has_pair, bool has_wide, bool one_launch, bool one_stream, bool has_mfma2, int beside_chunks, Piece* out) {
-  return pb::plan_pieces_mfma(P, has_pair, has_wide, one_launch, one_stream, has_mfma2, beside_chunks, wave_slots(), out);
-}
-
 // ---- workspace of a partitioned solve (int32 units) -----------------------------------------------------------
 //   [0, P) the lists   [P] length of the front list   [P+1, P+1+nblk) block counts   ranges of the three lists'
 //   candidate launches   lambda_max of every series (float64, when the caller has none)
@@ -480,22 +134,6 @@ WorkLayout work_layout(int P, int V) {
   w.total = w.lmax + 2 * (int64_t)V + 8;
   return w;
 }
-// coherence bounds of the conditioning guard (path.h: path_class; calibrated on 5 120 series per length,
-// profiles/r5_gamma_calibration_*.txt: above them the matrix-pipe form holds 3.3e-6 and the float32 vector forms 3e-6)
-constexpr double PART_GAMMA_F64 = 1.0e-2, PART_GAMMA_MATRIX_PIPE = 7.0e-2;
-// The bound below which a series stays off the matrix pipe, by shape: the error of the matrix-pipe forms at a given coherence falls
-// with the length of the series (profiles/r5_gamma_calibration_*.txt, worst over the adversarial families per bin of gamma_2:
-// 300 scans 4.8e-6 in [5e-2, 7e-2) and 6.7e-6 below; 600 scans 3.7e-6 in [3e-2, 5e-2), 4.9e-6 in [2e-2, 3e-2); 1 200 scans 5.4e-6 in
-// [2e-2, 3e-2), 4.5e-6 in [1e-2, 2e-2); with 34+ taps 8.2e-6 in [5e-2, 7e-2) at 300 scans) -- and white noise, whose own error is
-// 2e-6 at most, has a median gamma_2 of 6e-2 / 4e-2 / 3e-2 at 300 / 600 / 1 200 scans: one bound for every length kept nearly
-// every noise-like series of 1 200 scans on the vector forms.
-inline double part_gamma_matrix_pipe(int N, int K) {
-  if (K > 33 || N <= 310) return PART_GAMMA_MATRIX_PIPE;
-  return N <= 640 ? 3.0e-2 : 2.0e-2;
-}
-// below this many problems a call is latency-bound and keeps the host-side plan (a partition costs ~8 small launches)
-constexpr int PART_MIN_P = 4096;
-
 // pb_fista_solve without a caller's workspace: one buffer per (device, stream), grown on demand, never freed
 int32_t* own_workspace(void* stream, int64_t need, int64_t* len) {
   static std::mutex mu;
@@ -675,276 +313,337 @@ int normal_eq_impl(const double* z_dev, int64_t ldz, const TY* y_dev, int64_t ld
 }
 }  // namespace
 
+
 namespace {
-// the one-problem-per-wave entry worth using for SHORT series (the cheapest-per-problem tail
-// form): only entries whose strips are at most 8 samples
-const WideEntry* pick_wide_small(int N, int K) {
-  const WideEntry* we = pick_wide(N, K);
-  return (we && we->S <= 8) ? we : nullptr;
-}
-
-// Flag masks of the dispatch.  The forms split over waves, and the one-wave matrix-pipe form beside them, stay off under
-// a pinned vector form or PB_FLAG_NO_MFMA
-constexpr unsigned FLAGS_VECTOR_ONLY = PB_FLAG_FORCE_GENERIC | PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_FORCE_WIDE |
-                                       PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA;
-// ... the one-wave matrix-pipe form as a piece of a single-row entry's plan (whose entry PB_FLAG_FORCE_GENERIC / _FORCE_WIDE
-// have already ruled out); plan_ex reads these flags as "the plan without the matrix pipe"
-constexpr unsigned FLAGS_PAIR_PIN_OR_NO_MFMA = PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA;
-// the split pair form (one series over the two slots of a row)
-constexpr unsigned FLAGS_NO_SPLIT_PAIR = PB_FLAG_FORCE_GENERIC | PB_FLAG_NO_PAIR | PB_FLAG_FORCE_WIDE | PB_FLAG_DIRECT_FIR;
-// the partition on the device
-constexpr unsigned FLAGS_NO_PARTITION = PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_PAIR | PB_FLAG_FORCE_WIDE | PB_FLAG_NO_PAIR |
-                                        PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA | PB_FLAG_ONE_LAUNCH | PB_FLAG_FORCE_MFMA2 |
-                                        PB_FLAG_CERT_NO_RESOLVE | PB_FLAG_NO_PARTITION;
-
-// The window rule at the reference's wind = 6 as a per-iteration no-fire certificate (fista_pair_ffa.h, the matrix-pipe
-// forms), then an exact re-solve of the problems it could not clear (n_done = -1).  Worth it when the rule is not expected
-// to fire: the criterion decays like ~0.9/k on this problem class, so it cannot pass below tol before k ~ 0.9/tol --
-// tol * n_iter < CERT_TN_VECTOR.  The matrix-pipe forms' bound rests on four tracked samples per problem instead of
-// sixteen: only where the rule is far from firing, tol * n_iter < CERT_TN_MATRIX_PIPE; closer calls stay on the pair form.
-constexpr double CERT_TN_VECTOR = 0.5, CERT_TN_MATRIX_PIPE = 0.02;
-
-// ---- the dispatch of a float32 call: pb_fista_solve runs its route, the queries report it -------------------------------
-struct Call {
-  int N, K, P, stop_mode, wind;
-  unsigned flags;
-  bool cost_trace;     // J_dev given
-  bool lbda_vec;       // one lambda per problem
-  bool n_done;         // n_done_dev given
-  double tol_iters;    // tol * n_iter
-  bool taps_dev;       // the taps in device memory too
-  bool workspace;      // a partition workspace can be used
-  bool reported;       // a query: the cells where the queries have always answered otherwise than the solve runs (below)
+// ---- running a route --------------------------------------------------------------------------------------------------
+// launch_form(form, args, stream, exact_rule) -> 0 / 1 (rejected): the kernel launcher the route holds for a form of the
+// plan (plan.h); exact_rule = the window rule in full, not as a certificate (re-solves of handed-back problems).  One
+// mapping per call kind, built once per call from its Route; the executors below take either.
+struct HostTapsForms {            // pb_fista_solve, _ex, _path: the taps on the host
+  const Route& r;
+  const char* name;               // the entry point, for error texts
+  const double* taps;
+  int K, stop_mode;
+  bool wj, direct_fir;
+  int operator()(int form, const pb::FistaArgs& b, hipStream_t st, bool exact_rule) const {
+    const bool cert = r.cert && !exact_rule;
+    switch (form) {
+      case FORM_MFMA: return r.mfma ? r.mfma(b, taps, K, wj, st) : 1;
+      case FORM_MFMA2: return r.split ? r.split(b, taps, K, wj, st) : 1;      // (over four waves beyond 640 scans)
+      case FORM_PAIR:
+        if (r.path == PATH_PART_LONG || r.path == PATH_SPLIT_PAIR) return r.se->fn_pair_split(b, taps, K, wj, cert, st);
+        if (cert) return r.fe->fn_pair_cert(b, taps, K, st);
+        return ((r.fe->fn_pair_ffa && !direct_fir) ? r.fe->fn_pair_ffa : r.fe->fn_pair)(b, taps, K, wj, st);
+      case FORM_WIDE: return r.we ? r.we->fn(b, taps, K, wj, stop_mode, st) : 1;
+      default: return r.fe->fn(b, taps, K, wj, stop_mode, st);
+    }
+  }
+};
+struct DeviceTapsForms {          // pb_fista_solve_pp: taps and steps in device memory (FistaArgs::taps_pp, step_vec)
+  const Route& r;
+  const char* name;
+  int K, stop_mode;
+  int operator()(int form, const pb::FistaArgs& b, hipStream_t st, bool) const {
+    switch (form) {
+      case FORM_MFMA: return r.mfma ? r.mfma(b, nullptr, K, false, st) : 1;
+      case FORM_MFMA2: return r.split ? r.split(b, nullptr, K, false, st) : 1;
+      case FORM_PAIR: return r.fe->fn_pair_dev(b, st);
+      case FORM_WIDE: return r.we ? r.we->fn_pp(b, stop_mode, st) : 1;
+      default: return r.fe->fn_pp(b, stop_mode, st);
+    }
+  }
 };
 
-enum Path {
-  PATH_PART_LONG,      // 311 .. 1 280 scans partitioned on the device: a split matrix-pipe form, the split pair form, the backup form
-  PATH_SPLIT_LONG,     // whole passes of a split matrix-pipe form, the remainder and the re-solve on the backup form
-  PATH_SPLIT_PAIR,     // the pair form with the two halves of ONE series in the slots of a row
-  PATH_PART_SHORT,     // a single-row entry's shape partitioned on the device: the one-wave matrix-pipe form and vector forms
-  PATH_PIECES,         // the host-side plan of a single-row entry's shape (plan.h), or one pinned form
-  PATH_MFMA_WIDE,      // the one-wave matrix-pipe form beside the one-problem-per-wave form
-  PATH_WIDE,           // one problem per wave
-  PATH_GENERIC         // the any-size LDS kernel
+template <class LF>
+int launch(const LF& lf, int form, const pb::FistaArgs& b, hipStream_t st, bool exact_rule = false) {
+  static const char* const kernel[] = {"fista_generic_kernel", "fista_fast_kernel", "fista_pair_ffa_kernel", "fista_fast_kernel(wide)",
+                                       "fista_mfma_kernel", "fista_mfma2_kernel / fista_mfma4_kernel"};
+  if (lf(form, b, st, exact_rule) != 0) return fail(PB_ERR_INVALID, "%s: the kernel of form %d rejected its launch", lf.name, form);
+  return check_launch(kernel[form]);
+}
+
+// The device's side stream in the hands of one call: taken under the lock, forked from the caller's stream once, joined back
+// into it if it was forked
+struct Side {
+  std::unique_lock<std::mutex> lock{g_side_mutex, std::defer_lock};
+  SideStream* ss = nullptr;
+  bool forked = false;
+  void take() {
+    lock.lock();
+    ss = side_stream_locked();
+  }
+  int fork(hipStream_t user, const char* name) {
+    if (forked) return PB_OK;
+    if (hipEventRecord(ss->fork, user) != hipSuccess || hipStreamWaitEvent(ss->stream, ss->fork, 0) != hipSuccess)
+      return fail(PB_ERR_HIP, "%s: fork to the side stream failed", name);
+    forked = true;
+    return PB_OK;
+  }
+  int join(hipStream_t user, const char* name) {
+    if (!forked) return PB_OK;
+    forked = false;
+    if (hipEventRecord(ss->join, ss->stream) != hipSuccess || hipStreamWaitEvent(user, ss->join, 0) != hipSuccess)
+      return fail(PB_ERR_HIP, "%s: join of the side stream failed", name);
+    return PB_OK;
+  }
 };
 
-struct Route {
-  Path path;
-  const FastEntry* fe;   // single-row entry: PIECES, PART_SHORT; the backup form of SPLIT_LONG / PART_LONG unless backup_wide
-  const WideEntry* we;   // one-problem-per-wave entry: WIDE, MFMA_WIDE, SPLIT_PAIR's re-solve, the backup form when backup_wide
-  const FastEntry* se;   // split pair entry: SPLIT_PAIR, PART_LONG
-  launch_fn mfma;        // one-wave matrix-pipe form: PIECES, PART_SHORT, MFMA_WIDE (PART_SHORT without it: no dense class)
-  launch_fn split;       // the form split over two waves (over four beyond 640 scans)
-  bool backup_wide;
-  bool cert;             // the window rule as a certificate on the pair form (SPLIT_PAIR, PART_LONG: the split pair form)
-  bool mfma_cert;        // ... on the one-wave matrix-pipe form too
-  bool has_pair, has_wide, has_mfma2;   // the forms a plan may use (PART_LONG: has_pair = the split pair form)
-  int one_form;          // PIECES: this form over every problem in one launch (0: the plan)
-  int base;              // SPLIT_LONG, MFMA_WIDE: problems [0, base) on the matrix-pipe form
-};
-
-Route route(const Call& c) {
-  const int N = c.N, K = c.K, P = c.P, stop = c.stop_mode;
-  const unsigned fl = c.flags;
-  const bool plain = stop == PB_STOP_NONE, window6 = stop == PB_STOP_WINDOW && c.wind == 6;
-  Route r{};
-  const bool part_ws = c.workspace && c.n_done && P >= PART_MIN_P && K <= pb::LMAX_KT && N <= 1280 && !(fl & FLAGS_NO_PARTITION);
-  // the window rule as a certificate on a form with this limit of tol * n_iter
-  auto cert_clears = [&](double limit) { return !(fl & PB_FLAG_NO_CERT) && ((fl & PB_FLAG_FORCE_CERT) || c.tol_iters < limit); };
-  // the split matrix-pipe forms: plain solves, the certificate, the _loops_deconv rule in full inside the kernel (no cost
-  // trace); one lambda per problem only when asked for
-  const bool split_cert = window6 && c.n_done && cert_clears(CERT_TN_MATRIX_PIPE);
-  const bool split_rule = plain || split_cert || (stop == PB_STOP_LOOPS && !c.cost_trace);
-  const bool split_shape = split_rule && c.n_done && !(fl & FLAGS_VECTOR_ONLY) &&
-                           (!c.lbda_vec || (fl & (PB_FLAG_FORCE_MFMA | PB_FLAG_FORCE_MFMA2)));
-  const launch_fn mfma2 = split_shape ? pick_mfma2(N, K, false) : nullptr;
-  const launch_fn mfma4 = (split_shape && mfma4_serves(N, K)) ? pick_mfma4(N, K, false) : nullptr;
-  const bool four = N > 640;
-  const bool long_shape = mfma2_serves_long(N, K) || mfma2_takes_short_cert(N, K, stop, c.wind);
-  const bool long_call = long_shape && P >= mfma2_long_min_p(K);
-  // the exact vector form behind a split form (remainder, re-solve): single row, else one per wave -- with the window rule it
-  // must hold the rule's increment ring (the queries check the one-problem-per-wave entry's: 311..320 scans)
-  const FastEntry* fe1 = pick_fast(N, K);
-  const WideEntry* we1 = pick_wide(N, K);
-  r.backup_wide = we1 && (!fe1 || N > 320);
-  const bool backup_ok = (fe1 || we1) && ring_fits((r.backup_wide || (c.reported && we1)) ? we1->S : fe1->S, stop, c.wind);
-  // series of 16 S < N <= 32 S scans (the reference's 600-scan demo): the pair form with the two halves of ONE series in the
-  // slots of a row; the window rule as a certificate, re-solved on the one-problem-per-wave form
-  r.se = pick_split(N, K);
-  const bool split_pair_cert = r.se && window6 && c.n_done && we1 && ring_fits(we1->S, stop, c.wind) && cert_clears(CERT_TN_VECTOR);
-
-  // 311 .. 1 280 scans partitioned on the device: the dense class on whole passes of the split form, the sparse class on the
-  // pair form over two slots (or the backup form), handed-back problems compacted
-  if (part_ws && split_rule && (four ? mfma4_serves(N, K) : long_call) && backup_ok) {
-    r.path = PATH_PART_LONG;
-    r.split = four ? pick_mfma4(N, K, false) : pick_mfma2(N, K, false);
-    r.fe = fe1;
-    r.we = we1;
-    r.cert = split_pair_cert;
-    r.has_pair = r.se && (plain || split_pair_cert);
-    return r;
-  }
-  // Series of 311 .. 640 scans on the two-wave split form from mfma2_long_min_p problems on, 641 .. 1 280 on the four-wave
-  // form: whole passes (and a large remainder), the rest and whatever its guards hand back on the backup form.  Shorter
-  // series meet the two-wave form as a piece of the plan below (small batches, remainders) or through PB_FLAG_FORCE_MFMA2.
-  // (PB_FLAG_FORCE_MFMA2 as the queries report it: the long shapes, and plain solves or the certificate with up to 33 taps
-  // whatever the backup form)
-  const bool forced = (fl & PB_FLAG_FORCE_MFMA2) != 0;
-  const bool forced_short = c.reported && forced && (plain || window6) && pick_mfma2(N, K, true);
-  const launch_fn split = mfma4 ? mfma4 : ((mfma2 && ((forced && (!c.reported || long_shape || forced_short)) || long_call)) ? mfma2 : nullptr);
-  if (split && (backup_ok || forced_short)) {
-    r.path = PATH_SPLIT_LONG;
-    r.split = split;
-    r.fe = fe1;
-    r.we = we1;
-    const bool one_launch = (fl & PB_FLAG_ONE_LAUNCH) != 0;
-    r.base = (fl & PB_FLAG_FORCE_MFMA2) ? P : (mfma4 ? mfma4_base(P, one_launch) : mfma2_long_base(P, one_launch));
-    return r;
-  }
-  const bool mfma_plain = plain && c.n_done && (!c.lbda_vec || (fl & PB_FLAG_FORCE_MFMA)) && !(fl & FLAGS_VECTOR_ONLY) &&
-                          mfma_serves_plain(N, K);
-  if (!mfma_plain && !(fl & FLAGS_NO_SPLIT_PAIR) && r.se && (P >= SPLIT_MIN_P || (fl & PB_FLAG_FORCE_PAIR)) &&
-      (plain || split_pair_cert)) {
-    r.path = PATH_SPLIT_PAIR;
-    r.we = we1;
-    r.cert = split_pair_cert;
-    return r;
-  }
-  // the register-resident window rule keeps wind-1 iterates: wind = 4, 6 or 8 on entries small enough to hold them
-  const FastEntry* fe = (fl & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_WIDE)) ? nullptr : fe1;
-  if (fe && !ring_fits(fe->S, stop, c.wind)) fe = nullptr;
-  if (fe) {
-    r.fe = fe;
-    // (the queries report the certificate for a single problem too)
-    r.cert = window6 && fe->fn_pair_cert && c.n_done && (P >= 2 || c.reported) && !(fl & (PB_FLAG_NO_PAIR | PB_FLAG_DIRECT_FIR)) &&
-             cert_clears(CERT_TN_VECTOR);
-    // Plain solves (cost trace or not) of 129..310 scans, HRFs up to 33 taps (34..65: plain solves only): both operators on
-    // the matrix pipe (fista_mfma.h).  Needs n_done_dev: a problem whose scaled operands left the float16 range comes back
-    // with n_done = -1 and is re-solved on the single-row form.  Not with one lambda per problem, unless asked for
-    // (PB_FLAG_FORCE_MFMA): along a regularisation path a third of the problems (lambda near lambda_max) fail that
-    // kernel's accuracy guard and would be solved twice.  The window rule rides it as the certificate; the _loops_deconv
-    // rule is evaluated exactly inside it (no cost trace, K <= 33).
-    r.mfma_cert = r.cert && ((fl & PB_FLAG_FORCE_MFMA) || c.tol_iters < CERT_TN_MATRIX_PIPE);
-    const bool mfma_rule = plain || r.mfma_cert || (stop == PB_STOP_LOOPS && !c.cost_trace && K <= MFMA_K2);
-    const launch_fn mfma_shape = mfma_rule ? pick_mfma(N, K, !plain) : nullptr;
-    const launch_fn mfma = (mfma_shape && c.n_done && (!c.lbda_vec || (fl & PB_FLAG_FORCE_MFMA)) && !(fl & FLAGS_PAIR_PIN_OR_NO_MFMA))
-                               ? mfma_shape : nullptr;
-    r.has_pair = (fe->fn_pair && plain) || r.cert;
-    r.has_wide = pick_wide_small(N, K) != nullptr;
-    r.path = PATH_PIECES;
-    if (fl & PB_FLAG_NO_PAIR) {
-      r.one_form = FORM_FAST1;
-      return r;
-    }
-    // A call no matrix-pipe form carries -- another window, a cost trace beside the _loops_deconv rule, a long HRF -- is
-    // partitioned all the same, with an empty dense class: the conditioning guard is the partition's, and float32 vector
-    // forms need it too (ill-conditioned series: 3e-5 .. 5e-3 without it)
-    const bool part_mfma = mfma || (c.lbda_vec && mfma_shape);
-    if (part_ws && (part_mfma || !(fl & PB_FLAG_NO_ILL_GUARD))) {
-      r.path = PATH_PART_SHORT;
-      r.mfma = part_mfma ? mfma_shape : nullptr;
-      r.split = !part_mfma ? nullptr
-                : (mfma2 || !c.lbda_vec) ? mfma2
-                : ((plain || split_cert) && K <= MFMA_K2) ? pick_mfma2(N, K, false) : nullptr;
-      r.has_mfma2 = r.split && (plain || r.mfma_cert);
-      return r;
-    }
-    r.mfma = mfma;
-    r.split = mfma2;
-    // (the queries plan the two-wave form with up to 33 taps)
-    r.has_mfma2 = c.reported ? (plain || window6) && pick_mfma2(N, K, true) : mfma2 && (plain || r.mfma_cert);
-    if (fl & PB_FLAG_FORCE_PAIR) r.one_form = (r.cert || (fe->fn_pair && P >= 2 && plain)) ? FORM_PAIR : FORM_FAST1;
-    return r;
-  }
-  // 305..310 scans with more than 32 taps: no single-row entry, but ten blocks of 31 samples fit the matrix-pipe form --
-  // whole rounds (or everything) on it, a small remainder and the problems its guards hand back on the one-problem-per-wave form
-  const launch_fn mf = mfma_plain ? pick_mfma(N, K, false) : nullptr;
-  if (mf && we1) {
-    r.path = PATH_MFMA_WIDE;
-    r.mfma = mf;
-    r.we = we1;
-    r.base = mfma_wide_base(P, (fl & PB_FLAG_ONE_LAUNCH) != 0);
-    return r;
-  }
-  // long series: one problem per wave
-  if (!(fl & PB_FLAG_FORCE_GENERIC) && we1 && ring_fits(we1->S, stop, c.wind)) {
-    r.path = PATH_WIDE;
-    r.we = we1;
-    return r;
-  }
-  r.path = PATH_GENERIC;
-  return r;
-}
-
-// PATH_PIECES: the pinned form over every problem, else the plan of its forms (plan.h)
-int route_pieces(const Route& r, int N, int P, bool one_launch, bool one_stream, Piece* pc) {
-  if (r.one_form) {
-    pc[0] = Piece{r.one_form, 0, P, false, false};
-    return 1;
-  }
-  if (r.mfma) return plan_pieces_mfma(P, r.has_pair, r.has_wide, one_launch, one_stream, r.has_mfma2, beside_chunks_for(N), pc);
-  return plan_pieces(P, r.has_pair, r.has_wide, one_launch, one_stream, pc);
-}
-
-// What the queries report of a route: problems [0, n_main) on main_form, the rest (mostly) on tail_form.  Of pieces, the
-// leading ones of one form are the "main" part, the first other form the tail (of several: the one that carries most
-// of the remaining problems).  A partitioned call reports its host-side plan: the queries describe calls without a workspace.
-void report(const Route& r, int N, int P, bool one_launch, bool one_stream, int* nm, int* mf, int* tf) {
-  auto passes = [&](int base, int form, int rest) {
-    if (base > 0 && base < P) { *nm = base; *mf = form; *tf = rest; }
-    else *tf = base > 0 ? form : rest;
-  };
-  *nm = *mf = *tf = 0;
-  switch (r.path) {
-    case PATH_SPLIT_LONG: passes(r.base, N > 640 ? pb::FORM_MFMA4 : FORM_MFMA2, r.backup_wide ? FORM_WIDE : FORM_FAST1); return;
-    case PATH_MFMA_WIDE: passes(r.base, FORM_MFMA, FORM_WIDE); return;
-    case PATH_SPLIT_PAIR: *tf = FORM_PAIR; return;
-    case PATH_WIDE: *tf = FORM_WIDE; return;
-    case PATH_PIECES: {
-      Piece pc[pb::MAX_PIECES];
-      const int npc = route_pieces(r, N, P, one_launch, one_stream, pc);
-      int i = 1;
-      while (i < npc && pc[i].form == pc[0].form) ++i;
-      if (i == npc) { *tf = pc[0].form; return; }
-      *nm = pc[i - 1].p1;
-      *mf = pc[0].form;
-      int big = i;
-      for (int k = i + 1; k < npc; ++k)
-        if (pc[k].p1 - pc[k].p0 > pc[big].p1 - pc[big].p0) big = k;
-      *tf = pc[big].form;
-      return;
-    }
-    default: *tf = FORM_GENERIC; return;
-  }
-}
-
-int launched(int rejected, const char* why, const char* name) {
-  return rejected ? fail(PB_ERR_INVALID, "%s", why) : check_launch(name);
-}
-
-// Whole passes [0, base) on a matrix-pipe form (`main`), the remainder [base, P) on a vector form (`rest`), then `rest`
-// again over [0, base) for the problems the matrix-pipe form's guards handed back (only_flagged: n_done = -1)
-template <class Main, class Rest>
-int run_passes(const pb::FistaArgs& a, int base, bool resolve, hipStream_t st, Main&& main, Rest&& rest) {
+// Whole passes [0, base) on a matrix-pipe form (`main_form`), the remainder [base, P) on a vector form (`rest_form`), then
+// `rest_form` again over [0, base) for the problems the main form's guards handed back (only_flagged: n_done = -1)
+template <class LF>
+int run_passes(const pb::FistaArgs& a, int base, int main_form, int rest_form, bool resolve, const LF& lf, hipStream_t st) {
   pb::FistaArgs b = a;
   if (base > 0) {
     b.P = base;
-    const int rc = main(b, st);
+    const int rc = launch(lf, main_form, b, st);
     if (rc != PB_OK) return rc;
   }
   if (base < a.P) {
     b = a;
     b.p0 = base;
-    const int rc = rest(b, st);
+    const int rc = launch(lf, rest_form, b, st);
     if (rc != PB_OK) return rc;
   }
   if (base > 0 && resolve) {
     b = a;
     b.P = base;
     b.only_flagged = 1;
-    return rest(b, st);
+    return launch(lf, rest_form, b, st, true);
   }
   return PB_OK;
+}
+
+// The host-side plan of a single-row entry's shape: whole rounds on the densest form, the remainder on the cheapest (the pair
+// form has no stop rules; the one-problem-per-wave form has them all); a remainder that fits beside half a round of pair
+// waves runs on the side stream.  Then the flagged problems of the pieces that may leave n_done = -1: the exact rule on the
+// single-row form, on the caller's stream (after the join)
+template <class LF>
+int run_pieces(const Route& r, const pb::FistaArgs& a, const LF& lf, hipStream_t user, unsigned flags) {
+  Piece pc[pb::MAX_PIECES];
+  const bool one_stream = r.one_stream || r.one_form || (flags & PB_FLAG_ONE_STREAM) != 0 || stream_is_capturing(user);
+  const int npc = route_pieces(r, a.P, (flags & PB_FLAG_ONE_LAUNCH) != 0, one_stream, pc);
+  bool any_side = false;
+  int q0 = a.P, q1 = 0;                          // range of the pieces that may leave n_done = -1 (contiguous)
+  for (int i = 0; i < npc; ++i) {
+    any_side |= pc[i].side;
+    if ((pc[i].form == FORM_PAIR && r.cert) || pc[i].form == FORM_MFMA || pc[i].form == FORM_MFMA2) {
+      q0 = pc[i].p0 < q0 ? pc[i].p0 : q0;
+      q1 = pc[i].p1 > q1 ? pc[i].p1 : q1;
+    }
+  }
+  Side side;
+  if (any_side) side.take();                     // (no side stream: the same pieces, one after the other)
+  pb::FistaArgs b = a;
+  int rc = PB_OK;
+  for (int i = 0; i < npc && rc == PB_OK; ++i) {
+    if (pc[i].group && side.ss) rc = side.fork(user, lf.name);   // whole rounds are in the queue: the group starts here
+    if (rc != PB_OK) break;
+    b.p0 = pc[i].p0;
+    b.P = pc[i].p1;
+    rc = launch(lf, pc[i].form, b, (pc[i].side && side.ss) ? side.ss->stream : user);
+  }
+  // join even after an error so that the caller's stream never runs ahead of the side stream
+  const int rj = side.join(user, lf.name);
+  if (rj != PB_OK) return rj;
+  if (rc != PB_OK || q1 <= q0 || (flags & PB_FLAG_CERT_NO_RESOLVE)) return rc;
+  b.p0 = q0;
+  b.P = q1;
+  b.only_flagged = 1;
+  return launch(lf, FORM_FAST1, b, user, true);
+}
+
+// a route that solves the problems where they lie (no partition): every call of pb_fista_solve_pp, and of pb_fista_solve below
+// PART_MIN_P problems, without a workspace or under a pin
+template <class LF>
+int run_in_place(const Route& r, const pb::FistaArgs& a, const LF& lf, hipStream_t user, unsigned flags) {
+  const bool resolve = !(flags & PB_FLAG_CERT_NO_RESOLVE);
+  switch (r.path) {
+    case PATH_SPLIT_LONG: return run_passes(a, r.base, FORM_MFMA2, r.backup_wide ? FORM_WIDE : FORM_FAST1, resolve, lf, user);
+    case PATH_MFMA_WIDE: return run_passes(a, r.base, FORM_MFMA, FORM_WIDE, resolve, lf, user);
+    // (every series on the split pair form, the certificate's re-solve one problem per wave)
+    case PATH_SPLIT_PAIR: return run_passes(a, a.P, FORM_PAIR, FORM_WIDE, r.cert && resolve, lf, user);
+    case PATH_PIECES: return run_pieces(r, a, lf, user, flags);
+    case PATH_WIDE: return launch(lf, FORM_WIDE, a, user);
+    default: return fail(PB_ERR_INVALID, "%s: this route is not solved in place", lf.name);
+  }
+}
+
+// ---- the partition BEFORE solving (dense class -> matrix pipe, sparse class -> float32 vector forms) and a compacted
+// re-solve of what a guard or certificate hands back; list lengths and launch plans live on the device (path.h, plan.h).
+// Without it a batch whose lambda lies near lambda_max was solved twice -- matrix pipe, then one handed-back problem per
+// wave (profiles/r4_path_partition.txt: 2.05 against 3.20e9).
+struct PartitionSpecs { pb::PlanSpec dense, sparse, flagged; };
+PartitionSpecs partition_specs(const Route& r, int N, bool one_stream) {
+  const double slots = wave_slots();
+  const int pair = r.has_pair ? 1 : 0, wide = r.has_wide ? 1 : 0, os = one_stream ? 1 : 0;
+  if (r.path == PATH_PART_SHORT)
+    return {{1, pair, wide, 0, os, r.has_mfma2 ? 1 : 0, r.beside_chunks, slots}, {2, pair, wide, 0, os, 0, 0, slots}, {2, 0, wide, 0, 1, 0, 0, slots}};
+  PartitionSpecs s{{3, 0, 0, 0, 1, 1, 0, slots}, {4, pair, 0, 0, 1, 0, 0, slots}, {4, 0, 0, 0, 1, 0, 0, slots}};
+  if (N > 640) {                                 // 641 .. 1 280 scans: the form split over four waves (fista_mfma4.h)
+    s.dense.pass_mult = 2;
+    s.dense.rem_num16 = MFMA4_MIN_R_NUM;
+  }
+  s.dense.backup_form = s.sparse.backup_form = s.flagged.backup_form = r.backup_wide ? FORM_WIDE : FORM_FAST1;
+  s.sparse.min_pair = SPLIT_MIN_P;
+  return s;
+}
+// which candidate launches of a list exist (list 0: the call's one list -- matrix-pipe forms for its dense head, vector forms
+// for the rest --, 1 / 2: the measurement aids "matrix-pipe candidates only" / "vector candidates only", 3: handed-back problems)
+bool list_has_form(const Route& r, int form, int list) {
+  const bool lng = r.path == PATH_PART_LONG;
+  if (form == FORM_MFMA) return list <= 1 && r.mfma != nullptr;
+  if (form == FORM_MFMA2) return list <= 1 && (lng || r.has_mfma2);
+  if (list == 1) return false;
+  if (form == FORM_PAIR) return list != 3 && r.has_pair;
+  if (form == FORM_WIDE) return lng ? r.backup_wide : r.has_wide;
+  return !lng || !r.backup_wide;
+}
+// grid bound of a candidate in slots
+int cand_bound(const Route& r, int c, int P) {
+  if (r.path == PATH_PART_SHORT) return pb::cand_max_slots(c, P, wave_slots());
+  return (c == pb::CAND_MFMA2 || c == pb::CAND_PAIR0 || c == pb::CAND_FAST0 || c == pb::CAND_WIDE) ? P : 0;
+}
+
+// a whole list: its candidates in their static order, the side-stream ones forked after the whole rounds
+template <class LF>
+int solve_list(const Route& r, const pb::FistaArgs& a, const LF& lf, hipStream_t user, Side& side, const int32_t* work_dev,
+               const int32_t* ranges, int list, bool exact_rule) {
+  pb::FistaArgs b = a;
+  b.perm = work_dev;
+  b.n_dense = work_dev + a.P;
+  b.perm_side = list == 3 ? 3 : 1;
+  int rc = PB_OK;
+  for (int c = 0; c < pb::CAND_COUNT && rc == PB_OK; ++c) {
+    const int form = pb::cand_form(c);
+    if (!list_has_form(r, form, list) || (pb::cand_side(c) && !side.ss)) continue;
+    // (a plan on one stream has no groups, and a second piece of a form continues the first: plan_to_candidates merges them)
+    if ((c == pb::CAND_PAIR1 || c == pb::CAND_FAST1) && !side.ss) continue;
+    b.grid_slots = cand_bound(r, c, a.P);
+    if (b.grid_slots <= 0) continue;
+    if (c >= pb::CAND_FIRST_AFTER_FORK && side.ss) rc = side.fork(user, lf.name);
+    if (rc != PB_OK) break;
+    b.range = ranges + 2 * c;
+    rc = launch(lf, form, b, (pb::cand_side(c) && side.ss) ? side.ss->stream : user, exact_rule);
+  }
+  const int rj = side.join(user, lf.name);
+  return rj != PB_OK ? rj : rc;
+}
+
+// lambda_max of every series, with max|y| and the marks of the ill-conditioned ones -- float32, ~55 us per 100 k series
+// (gamma_f64, gamma_vec: the coherence bounds below which a series is marked for the float64 kernel / kept off the matrix pipe; 0: none)
+void launch_lmax_pass(const pb::FistaArgs& a, int V_series, const double* taps_host, double* lm, double gamma_f64, double gamma_vec,
+                      hipStream_t st) {
+  const int N = a.N, K = a.K;
+  pb::LmaxTaps lt;
+  double run = 0.0, csum = 0.0;                   // sum|c| over the N lags of the operator's step response c = cumsum(h)
+  for (int k = 0; k < pb::LMAX_KT; ++k) lt.h[k] = k < K ? (float)taps_host[k] : 0.0f;
+  for (int t = 0; t < N; ++t) { if (t < K) run += taps_host[t]; csum += std::fabs(run); }
+  const double unit = csum / std::sqrt((double)N);
+  const float f64_bound = gamma_f64 > 0.0 ? (float)(gamma_f64 * unit) : 0.0f, vec_bound = gamma_vec > 0.0 ? (float)(gamma_vec * unit) : 0.0f;
+  const dim3 grid((unsigned)((V_series + 3) / 4)), block(256);
+  if (N <= 320) hipLaunchKernelGGL((pb::lmax_wave_kernel<5>), grid, block, 4 * (64 * 5 + pb::LMAX_KT) * sizeof(float), st, a.y, a.ldy, V_series, N, lt, K, lm, f64_bound, vec_bound);
+  else if (N <= 640) hipLaunchKernelGGL((pb::lmax_wave_kernel<10>), grid, block, 4 * (64 * 10 + pb::LMAX_KT) * sizeof(float), st, a.y, a.ldy, V_series, N, lt, K, lm, f64_bound, vec_bound);
+  else hipLaunchKernelGGL((pb::lmax_wave_kernel<21>), grid, block, 4 * (64 * 21 + pb::LMAX_KT) * sizeof(float), st, a.y, a.ldy, V_series, N, lt, K, lm, f64_bound, vec_bound);   // (odd strips: conflict-free)
+}
+
+// count, scan (which also plans the lists: plan_kernel's work on thread 0) and scatter of one class predicate
+int launch_partition(const pb::ClassPred& cp, int P, int32_t* work_dev, const pb::PlanSpec& front, const pb::PlanSpec& back,
+                     int32_t* rg_front, int32_t* rg_back, int32_t* rg_ill, const char* what, hipStream_t st) {
+  const int nblk = (P + pb::PATH_PER_BLOCK - 1) / pb::PATH_PER_BLOCK;
+  hipLaunchKernelGGL(pb::path_count_kernel, dim3(nblk), dim3(pb::PATH_THREADS), 0, st, cp, P, work_dev);
+  hipLaunchKernelGGL(pb::path_scan_kernel, dim3(1), dim3(pb::PATH_THREADS), 0, st, P, nblk, work_dev, front, back, rg_front, rg_back, rg_ill);
+  hipLaunchKernelGGL(pb::path_scatter_kernel, dim3(nblk), dim3(pb::PATH_THREADS), 0, st, cp, P, work_dev);
+  return check_launch(what);
+}
+
+// the any-size LDS kernel (generic.h), one workgroup per problem (fewer: they stride over a device-side list)
+void launch_generic(const pb::FistaArgs& a, const double* taps_dev, int K, int wind, bool with_j, bool f64, int grid, hipStream_t st) {
+  void (*const kernel)(pb::FistaArgs, const double*, int, int) =
+      !f64 ? (with_j ? pb::fista_generic_kernel<true> : pb::fista_generic_kernel<false>)
+           : (with_j ? pb::fista_generic_kernel<true, true> : pb::fista_generic_kernel<false, true>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(pb::GEN_THREADS), (size_t)gen_lds_doubles(a.N, K, a.stop_mode, wind) * sizeof(double), st,
+                     a, taps_dev, K, wind);
+}
+
+template <class LF>
+int run_partition(const Route& r, const pb::FistaArgs& a, const LF& lf, hipStream_t user, const double* taps_host,
+                  const double* taps_dev, unsigned flags, double dense_ratio, int32_t* work_dev) {
+  const int P = a.P, N = a.N, K = a.K, V_series = (P + a.y_rep - 1) / a.y_rep;
+  const bool one_stream = r.path == PATH_PART_LONG || (flags & PB_FLAG_ONE_STREAM) != 0 || stream_is_capturing(user);
+  const PartitionSpecs sp = partition_specs(r, N, one_stream);
+  const WorkLayout wl = work_layout(P, V_series);
+  // The ill-conditioned class (marked by the lambda_max pass, the tail of the list array) goes to a float64 kernel, any stop
+  // rule: the register-resident one, one or four waves per series, where the shape has an entry (its window rule is
+  // wind = 6; 1.0e9 voxel-iterations/s against 0.17e9), else the LDS one, which needs the taps in device memory and the row
+  // in LDS; with neither, or without the guard, no series is marked
+  const ExactEntry* ill_exact = pick_exact_any(N, K, a.stop_mode, a.wind, nullptr);
+  const bool ill_generic = !ill_exact && taps_dev && gen_lds_doubles(N, K, a.stop_mode, a.wind) <= LDS_DOUBLES_MAX;
+  const bool guard = !(flags & PB_FLAG_NO_ILL_GUARD);
+  // (the caller's lmax_dev is not needed: the pass also sees max|y| and marks the ill-conditioned series, which the caller's
+  // numbers do not tell)
+  double* lmax = reinterpret_cast<double*>(work_dev + wl.lmax);
+  launch_lmax_pass(a, V_series, taps_host, lmax, (guard && (ill_exact || ill_generic)) ? PART_GAMMA_F64 : 0.0,
+                   guard ? part_gamma_matrix_pipe(N, K) : 0.0, user);
+  int32_t* rg_dense = work_dev + wl.ranges;
+  int32_t* rg_sparse = rg_dense + 2 * pb::CAND_COUNT;
+  int32_t* rg_flag = rg_sparse + 2 * pb::CAND_COUNT;
+  int32_t* rg_ill = rg_flag + 2 * pb::CAND_COUNT;
+  const double ratio = (r.path == PATH_PART_SHORT && !r.mfma) ? 0.0                    // (no matrix-pipe form: no dense class)
+                       : dense_ratio > 0.0 ? dense_ratio
+                       : N > 640 ? PB_PATH_DENSE_RATIO_LONGER : (N > MFMA1_NMAX ? PB_PATH_DENSE_RATIO_LONG : PB_PATH_DENSE_RATIO);
+  pb::PlanSpec front = sp.dense;
+  front.merged = 1;
+  int rc = launch_partition(pb::ClassPred{a.lbda_vec, a.lbda, lmax, a.y_rep, ratio, nullptr}, P, work_dev, front, sp.sparse, rg_dense,
+                            rg_sparse, rg_ill, "partition", user);
+  if (rc != PB_OK) return rc;
+  Side side;
+  if (!one_stream) side.take();
+  // ONE list for the call: positions [0, P) of the list array (dense problems first), one plan (plan.h: plan_partitioned)
+  const bool only_dense = (flags & PB_FLAG_ONLY_DENSE) != 0, only_sparse = (flags & PB_FLAG_ONLY_SPARSE) != 0;   // (measurement aids)
+  rc = solve_list(r, a, lf, user, side, work_dev, rg_dense, only_dense ? 1 : (only_sparse ? 2 : 0), false);
+  if (rc != PB_OK || only_dense || only_sparse) return rc;
+  if (ill_exact || ill_generic) {                // (its workgroups stride over the list, which is empty for ordinary data)
+    pb::FistaArgs b = a;
+    b.perm = work_dev;
+    b.perm_side = 1;
+    b.range = rg_ill;
+    if (ill_exact) {
+      b.grid_slots = P;
+      if (ill_exact->fn(b, taps_host, K, a.J != nullptr, a.stop_mode, user) != 0)
+        return fail(PB_ERR_INVALID, "%s: float64 kernel rejected the launch (ill-conditioned series)", lf.name);
+    } else {
+      launch_generic(b, taps_dev, K, a.wind, a.J != nullptr, false, P < 2048 ? P : 2048, user);
+    }
+    rc = check_launch("float64 kernel (ill-conditioned series)");
+    if (rc != PB_OK) return rc;
+  }
+  // what the guards / certificates handed back (n_done = -1): compacted, then the exact vector forms at full occupancy
+  const pb::PlanSpec none{0, 0, 0, 0, 1, 0, 0, sp.dense.slots};
+  rc = launch_partition(pb::ClassPred{nullptr, 0.0, nullptr, 1, 0.0, a.n_done}, P, work_dev, sp.flagged, none, rg_flag, nullptr, nullptr,
+                        "partition(handed back)", user);
+  if (rc != PB_OK) return rc;
+  side.ss = nullptr;                             // (one stream: a few per cent of the batch at most)
+  return solve_list(r, a, lf, user, side, work_dev, rg_flag, 3, true);
+}
+
+// z = L w and x = h * z of every row (one HRF for all: ldt = 0; pp: one per problem)
+int outputs_impl(const double* w_dev, int64_t ldw, int P, int N, const double* taps_dev, int64_t ldt, int K, double* z_dev,
+                 int64_t ldz, double* x_dev, int64_t ldx, void* stream, bool pp, const char* name) {
+  if (P < 0 || N < 1 || K < 1 || ldw < N || (pp && ldt < K) || (z_dev && ldz < N) || (x_dev && ldx < N))
+    return fail(PB_ERR_INVALID, "%s: bad size", name);
+  if (2 * (int64_t)N + K + 8 > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "%s: N=%d K=%d exceeds LDS", name, N, K);
+  if (P == 0 || (!z_dev && !x_dev)) return PB_OK;
+  if (!w_dev || !taps_dev) return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
+  const size_t lds = (size_t)(2 * N + K + 8) * sizeof(double);
+  hipLaunchKernelGGL(pb::outputs_kernel, dim3(P), dim3(pb::GEN_THREADS), lds, (hipStream_t)stream,
+                     w_dev, ldw, N, taps_dev, ldt, K, z_dev, ldz, x_dev, ldx);
+  return check_launch(name);
+}
+
+pb::HrfModel hrf_model(double a_peak, double loc_peak, double a_under, double loc_under, double ratio) {
+  return pb::HrfModel{a_peak, loc_peak, lgamma(a_peak), a_under, loc_under, lgamma(a_under), ratio,
+                      pb::hrf_int_power(a_peak), pb::hrf_int_power(a_under), std::exp(-lgamma(a_peak)),
+                      std::exp(-lgamma(a_under))};
 }
 
 // the fields every FISTA entry point fills alike (the series, cost trace and per-problem taps are the caller's)
@@ -1052,314 +751,18 @@ static int solve_impl(const float* y_dev, int64_t ldy, int y_rep, double* w_dev,
   const Route r = route(Call{N, K, P, stop_mode, wind, flags, J_dev != nullptr, lbda_dev != nullptr, n_done_dev != nullptr,
                              tol * (double)n_iter, taps_dev != nullptr, workspace, false});
   const hipStream_t user = (hipStream_t)stream;
-  const bool wj = J_dev != nullptr;
-  const bool resolve = !(flags & PB_FLAG_CERT_NO_RESOLVE);
-
-  // ---- the partition BEFORE solving (dense class -> matrix pipe, sparse class -> float32 vector forms) and a compacted
-  // re-solve of what a guard or certificate hands back; list lengths and launch plans live on the device (path.h, plan.h).
-  // Without it a batch whose lambda lies near lambda_max was solved twice -- matrix pipe, then one handed-back problem per
-  // wave (profiles/r4_path_partition.txt: 2.05 against 3.20e9).
-  //   launch_form(form, args, stream, exact_rule) -> 0 / 1 (rejected);  has_form(form, list) says which candidates exist
-  //   (list 0: the call's one list -- matrix-pipe forms for its dense head, vector forms for the rest --, 1 / 2: the
-  //   measurement aids "matrix-pipe candidates only" / "vector candidates only", 3: handed-back problems);
-  //   bound(cand) = grid bound of a candidate in slots
-  // (the ill-conditioned class: register-resident float64 kernel, one or four waves per series, where the shape has an
-  // entry; its window rule is wind = 6)
-  auto ill_exact = [&]() -> const ExactEntry* { return pick_exact_any(N, K, stop_mode, wind, nullptr); };
-  const int64_t nd_g = gen_lds_doubles(N, K, stop_mode, wind);
-  auto run_partition = [&](const pb::PlanSpec& dense, const pb::PlanSpec& sparse, const pb::PlanSpec& flagged, bool no_dense_class,
-                           auto&& launch_form, auto&& has_form, auto&& bound) -> int {
-    const WorkLayout wl = work_layout(P, V_series);
-    // lambda_max of every series (the caller's lmax_dev is not needed any more: the pass also sees max|y| and marks the
-    // ill-conditioned series, which the caller's numbers do not tell) -- float32, ~55 us per 100 k series
-    double* lm = reinterpret_cast<double*>(work_dev + wl.lmax);
-    {
-      pb::LmaxTaps lt;
-      double run = 0.0, csum = 0.0;                   // sum|c| over the N lags of the operator's step response c = cumsum(h)
-      for (int k = 0; k < pb::LMAX_KT; ++k) lt.h[k] = k < K ? (float)taps_host[k] : 0.0f;
-      for (int t = 0; t < N; ++t) { if (t < K) run += taps_host[t]; csum += std::fabs(run); }
-      // (the marked series: float64 register-resident kernel, or the LDS one, which needs the taps in device memory and the row in LDS)
-      const bool guard = !(flags & PB_FLAG_NO_ILL_GUARD);
-      const double unit = csum / std::sqrt((double)N);
-      const float f64_bound = (guard && (ill_exact() || (taps_dev && nd_g <= LDS_DOUBLES_MAX))) ? (float)(PART_GAMMA_F64 * unit) : 0.0f;
-      const float vec_bound = guard ? (float)(part_gamma_matrix_pipe(N, K) * unit) : 0.0f;
-      const dim3 grid((unsigned)((V_series + 3) / 4)), block(256);
-      if (N <= 320) hipLaunchKernelGGL((pb::lmax_wave_kernel<5>), grid, block, 4 * (64 * 5 + pb::LMAX_KT) * sizeof(float), user, y_dev, ldy, V_series, N, lt, K, lm, f64_bound, vec_bound);
-      else if (N <= 640) hipLaunchKernelGGL((pb::lmax_wave_kernel<10>), grid, block, 4 * (64 * 10 + pb::LMAX_KT) * sizeof(float), user, y_dev, ldy, V_series, N, lt, K, lm, f64_bound, vec_bound);
-      else hipLaunchKernelGGL((pb::lmax_wave_kernel<21>), grid, block, 4 * (64 * 21 + pb::LMAX_KT) * sizeof(float), user, y_dev, ldy, V_series, N, lt, K, lm, f64_bound, vec_bound);   // (odd strips: conflict-free)
-    }
-    const double* lmax = lm;
-    const int nblk = (P + pb::PATH_PER_BLOCK - 1) / pb::PATH_PER_BLOCK;
-    int32_t* rg_dense = work_dev + wl.ranges;
-    int32_t* rg_sparse = rg_dense + 2 * pb::CAND_COUNT;
-    int32_t* rg_flag = rg_sparse + 2 * pb::CAND_COUNT;
-    int32_t* rg_ill = rg_flag + 2 * pb::CAND_COUNT;
-    {
-      pb::ClassPred cp{lbda_dev, lbda, lmax, y_rep, no_dense_class ? 0.0 : (dense_ratio > 0.0 ? dense_ratio : (N > 640 ? PB_PATH_DENSE_RATIO_LONGER : (N > MFMA1_NMAX ? PB_PATH_DENSE_RATIO_LONG : PB_PATH_DENSE_RATIO))), nullptr};
-      hipLaunchKernelGGL(pb::path_count_kernel, dim3(nblk), dim3(pb::PATH_THREADS), 0, user, cp, P, work_dev);
-      pb::PlanSpec front = dense;
-      front.merged = 1;
-      hipLaunchKernelGGL(pb::path_scan_kernel, dim3(1), dim3(pb::PATH_THREADS), 0, user, P, nblk, work_dev, front, sparse, rg_dense, rg_sparse, rg_ill);
-      hipLaunchKernelGGL(pb::path_scatter_kernel, dim3(nblk), dim3(pb::PATH_THREADS), 0, user, cp, P, work_dev);
-      const int rc = check_launch("partition");
-      if (rc != PB_OK) return rc;
-    }
-    SideStream* ss = nullptr;
-    std::unique_lock<std::mutex> lock(g_side_mutex, std::defer_lock);
-    if (!dense.one_stream) {
-      lock.lock();
-      ss = side_stream_locked();
-    }
-    // a whole list: its candidates in their static order, the side-stream ones forked after the whole rounds
-    auto solve_list = [&](const int32_t* ranges, int side, int list, bool exact_rule) -> int {
-      int rc = PB_OK;
-      bool forked = false;
-      for (int c = 0; c < pb::CAND_COUNT && rc == PB_OK; ++c) {
-        const int form = pb::cand_form(c);
-        if (!has_form(form, list) || (pb::cand_side(c) && !ss)) continue;
-        // (a plan on one stream has no groups, and a second piece of a form continues the first: plan_to_candidates merges them)
-        if ((c == pb::CAND_PAIR1 || c == pb::CAND_FAST1) && !ss) continue;
-        const int bd = bound(c);
-        if (bd <= 0) continue;
-        if (c >= pb::CAND_FIRST_AFTER_FORK && !forked && ss) {
-          if (hipEventRecord(ss->fork, user) != hipSuccess || hipStreamWaitEvent(ss->stream, ss->fork, 0) != hipSuccess)
-            return fail(PB_ERR_HIP, "pb_fista_solve: fork to the side stream failed");
-          forked = true;
-        }
-        pb::FistaArgs b = a;
-        b.perm = work_dev;
-        b.n_dense = work_dev + P;
-        b.perm_side = side;
-        b.range = ranges + 2 * c;
-        b.grid_slots = bd;
-        if (launch_form(form, b, (pb::cand_side(c) && ss) ? ss->stream : user, exact_rule) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: a kernel form rejected its launch over a device-side list (form %d)", form);
-        rc = check_launch("fista kernel (device-side list)");
-      }
-      if (forked && (hipEventRecord(ss->join, ss->stream) != hipSuccess || hipStreamWaitEvent(user, ss->join, 0) != hipSuccess))
-        return fail(PB_ERR_HIP, "pb_fista_solve: join of the side stream failed");
-      return rc;
-    };
-    // ONE list for the call: positions [0, P) of the list array (dense problems first), one plan (plan.h: plan_partitioned)
-    const bool only_dense = (flags & PB_FLAG_ONLY_DENSE) != 0, only_sparse = (flags & PB_FLAG_ONLY_SPARSE) != 0;   // (measurement aids)
-    int rc = solve_list(rg_dense, 1, only_dense ? 1 : (only_sparse ? 2 : 0), false);
-    if (rc != PB_OK || only_dense || only_sparse) return rc;
-    // the ill-conditioned series (marked by the lambda_max pass, the tail of the list array): float64 LDS kernel, any stop
-    // rule; its workgroups stride over the list, which is empty for ordinary data
-    {
-      pb::FistaArgs b = a;
-      b.perm = work_dev;
-      b.perm_side = 1;
-      b.range = rg_ill;
-      // (the register-resident float64 kernel where the shape has an entry: 1.0e9 voxel-iterations/s against 0.17e9)
-      const ExactEntry* ee = ill_exact();
-      if (ee) {
-        b.grid_slots = P;
-        if (ee->fn(b, taps_host, K, wj, stop_mode, user) != 0)
-          return fail(PB_ERR_INVALID, "pb_fista_solve: float64 kernel rejected the launch (ill-conditioned series)");
-        rc = check_launch("fista_exact_kernel / fista_exact_split_kernel(ill-conditioned series)");
-        if (rc != PB_OK) return rc;
-      } else if (taps_dev && nd_g <= LDS_DOUBLES_MAX) {
-        const int wgs = P < 2048 ? P : 2048;
-        if (J_dev) hipLaunchKernelGGL((pb::fista_generic_kernel<true>), dim3(wgs), dim3(pb::GEN_THREADS), (size_t)nd_g * sizeof(double), user, b, taps_dev, K, wind);
-        else hipLaunchKernelGGL((pb::fista_generic_kernel<false>), dim3(wgs), dim3(pb::GEN_THREADS), (size_t)nd_g * sizeof(double), user, b, taps_dev, K, wind);
-        rc = check_launch("fista_generic_kernel(ill-conditioned series)");
-        if (rc != PB_OK) return rc;
-      }
-    }
-    // what the guards / certificates handed back (n_done = -1): compacted, then the exact vector forms at full occupancy
-    pb::ClassPred cp{nullptr, 0.0, nullptr, 1, 0.0, n_done_dev};
-    const pb::PlanSpec none{0, 0, 0, 0, 1, 0, 0, dense.slots};
-    hipLaunchKernelGGL(pb::path_count_kernel, dim3(nblk), dim3(pb::PATH_THREADS), 0, user, cp, P, work_dev);
-    hipLaunchKernelGGL(pb::path_scan_kernel, dim3(1), dim3(pb::PATH_THREADS), 0, user, P, nblk, work_dev, flagged, none, rg_flag, (int32_t*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(pb::path_scatter_kernel, dim3(nblk), dim3(pb::PATH_THREADS), 0, user, cp, P, work_dev);
-    rc = check_launch("partition(handed back)");
-    if (rc != PB_OK) return rc;
-    ss = nullptr;                                  // (one stream: a few per cent of the batch at most)
-    return solve_list(rg_flag, 3, 3, true);
-  };
-
-  switch (r.path) {
-    case PATH_PART_LONG: {
-      const bool four = N > 640;                     // 641 .. 1 280 scans: the form split over four waves (fista_mfma4.h)
-      const double slots = wave_slots();
-      pb::PlanSpec dense{3, 0, 0, 0, 1, 1, 0, slots};
-      if (four) { dense.pass_mult = 2; dense.rem_num16 = MFMA4_MIN_R_NUM; }
-      pb::PlanSpec sparse{4, r.has_pair ? 1 : 0, 0, 0, 1, 0, 0, slots};
-      pb::PlanSpec flagged{4, 0, 0, 0, 1, 0, 0, slots};
-      dense.backup_form = sparse.backup_form = flagged.backup_form = r.backup_wide ? FORM_WIDE : FORM_FAST1;
-      sparse.min_pair = SPLIT_MIN_P;
-      return run_partition(dense, sparse, flagged, false,
-        [&](int form, const pb::FistaArgs& b, hipStream_t st, bool exact_rule) -> int {
-          if (form == FORM_MFMA2) return r.split(b, taps_host, K, wj, st);
-          if (form == FORM_PAIR) return r.se->fn_pair_split(b, taps_host, K, wj, r.cert && !exact_rule, st);
-          if (form == FORM_WIDE) return r.we->fn(b, taps_host, K, wj, stop_mode, st);
-          return r.fe->fn(b, taps_host, K, wj, stop_mode, st);
-        },
-        [&](int form, int list) -> bool {
-          if (form == FORM_MFMA2) return list <= 1;
-          if (list == 1) return false;
-          if (form == FORM_PAIR) return list != 3 && r.has_pair;
-          if (form == FORM_WIDE) return r.backup_wide;
-          if (form == FORM_FAST1) return !r.backup_wide;
-          return false;
-        },
-        [&](int c) -> int { return (c == pb::CAND_MFMA2 || c == pb::CAND_PAIR0 || c == pb::CAND_FAST0 || c == pb::CAND_WIDE) ? P : 0; });
-    }
-    case PATH_SPLIT_LONG: {
-      const bool four = N > 640;
-      return run_passes(a, r.base, resolve, user,
-        [&](const pb::FistaArgs& b, hipStream_t st) {
-          return four ? launched(r.split(b, taps_host, K, wj, st), "pb_fista_solve: four-wave matrix-pipe kernel rejected the launch", "fista_mfma4_kernel")
-                      : launched(r.split(b, taps_host, K, wj, st), "pb_fista_solve: split matrix-pipe kernel rejected the launch", "fista_mfma2_kernel");
-        },
-        [&](const pb::FistaArgs& b, hipStream_t st) {
-          const int bad = r.backup_wide ? r.we->fn(b, taps_host, K, wj, stop_mode, st) : r.fe->fn(b, taps_host, K, wj, stop_mode, st);
-          if (b.only_flagged)
-            return launched(bad, "pb_fista_solve: no vector form for the re-solve", four ? "fista_fast_kernel(wide, re-solve)" : "fista_fast_kernel(re-solve)");
-          return launched(bad, "pb_fista_solve: no vector form for the remainder", four ? "fista_fast_kernel(wide, remainder)" : "fista_fast_kernel(remainder)");
-        });
-    }
-    case PATH_SPLIT_PAIR: {
-      int rc = launched(r.se->fn_pair_split(a, taps_host, K, wj, r.cert, user), "pb_fista_solve: split pair kernel rejected the launch",
-                        "fista_pair_ffa_kernel(split)");
-      if (rc == PB_OK && r.cert && resolve) {
-        pb::FistaArgs b = a;
-        b.only_flagged = 1;
-        rc = launched(r.we->fn(b, taps_host, K, wj, PB_STOP_WINDOW, user), "pb_fista_solve: no one-problem-per-wave form for the re-solve",
-                      "fista_fast_kernel(wide, re-solve)");
-      }
-      return rc;
-    }
-    case PATH_PART_SHORT: {
-      const FastEntry* fe = r.fe;
-      const bool one_stream = (flags & PB_FLAG_ONE_STREAM) != 0 || stream_is_capturing(user);
-      const double slots = wave_slots();
-      const pb::PlanSpec dense{1, r.has_pair ? 1 : 0, r.has_wide ? 1 : 0, 0, one_stream ? 1 : 0, r.has_mfma2 ? 1 : 0, beside_chunks_for(N), slots};
-      const pb::PlanSpec sparse{2, r.has_pair ? 1 : 0, r.has_wide ? 1 : 0, 0, one_stream ? 1 : 0, 0, 0, slots};
-      const pb::PlanSpec flagged{2, 0, r.has_wide ? 1 : 0, 0, 1, 0, 0, slots};
-      return run_partition(dense, sparse, flagged, r.mfma == nullptr,
-        [&](int form, const pb::FistaArgs& b, hipStream_t st, bool exact_rule) -> int {
-          if (form == FORM_MFMA) return r.mfma(b, taps_host, K, wj, st);
-          if (form == FORM_MFMA2) return r.split(b, taps_host, K, wj, st);
-          if (form == FORM_PAIR && r.cert && !exact_rule) return fe->fn_pair_cert(b, taps_host, K, st);
-          if (form == FORM_PAIR) return fe->fn_pair_ffa(b, taps_host, K, wj, st);
-          if (form == FORM_WIDE) return pick_wide_small(N, K)->fn(b, taps_host, K, wj, stop_mode, st);
-          return fe->fn(b, taps_host, K, wj, stop_mode, st);
-        },
-        [&](int form, int list) -> bool {
-          if (form == FORM_MFMA) return list <= 1 && r.mfma != nullptr;
-          if (form == FORM_MFMA2) return list <= 1 && r.has_mfma2;
-          if (list == 1) return false;                                // (aid: matrix-pipe candidates only)
-          if (form == FORM_PAIR) return list != 3 && r.has_pair;
-          if (form == FORM_WIDE) return r.has_wide;
-          return true;
-        },
-        [&](int c) -> int { return pb::cand_max_slots(c, P, slots); });
-    }
-    case PATH_PIECES: {
-      // whole rounds on the densest form, the remainder on the cheapest (the pair form has no
-      // stop rules; the one-problem-per-wave form has them all); a remainder that fits beside
-      // half a round of pair waves runs on the side stream
-      const FastEntry* fe = r.fe;
-      auto run = [&](int form, int p0, int p1, hipStream_t st) -> int {
-        pb::FistaArgs b = a;
-        b.p0 = p0;
-        b.P = p1;
-        if (form == FORM_MFMA)
-          return launched(!r.mfma || r.mfma(b, taps_host, K, wj, st) != 0, "pb_fista_solve: matrix-pipe kernel rejected the launch", "fista_mfma_kernel");
-        if (form == FORM_MFMA2)
-          return launched(!r.split || r.split(b, taps_host, K, wj, st) != 0, "pb_fista_solve: split matrix-pipe kernel rejected the launch", "fista_mfma2_kernel");
-        if (form == FORM_PAIR && r.cert)
-          return launched(fe->fn_pair_cert(b, taps_host, K, st), "pb_fista_solve: certificate kernel rejected the launch", "fista_pair_ffa_kernel(cert)");
-        if (form == FORM_PAIR) {
-          const launch_fn fn = (fe->fn_pair_ffa && !(flags & PB_FLAG_DIRECT_FIR)) ? fe->fn_pair_ffa : fe->fn_pair;
-          return launched(fn(b, taps_host, K, wj, st), "pb_fista_solve: pair kernel rejected the launch", "fista_pair_kernel");
-        }
-        if (form == FORM_WIDE) {
-          const WideEntry* we = pick_wide_small(N, K);
-          return launched(!we || we->fn(b, taps_host, K, wj, stop_mode, st) != 0, "pb_fista_solve: no one-problem-per-wave form", "fista_fast_kernel(wide)");
-        }
-        return launched(fe->fn(b, taps_host, K, wj, stop_mode, st), "pb_fista_solve: no register-resident form for this stop rule", "fista_fast_kernel");
-      };
-      Piece pc[pb::MAX_PIECES];
-      const bool one_stream = r.one_form || (flags & PB_FLAG_ONE_STREAM) != 0 || stream_is_capturing(user);
-      const int npc = route_pieces(r, N, P, (flags & PB_FLAG_ONE_LAUNCH) != 0, one_stream, pc);
-      bool any_side = false;
-      int q0 = P, q1 = 0;                          // range of the pieces that may leave n_done = -1 (contiguous)
-      for (int i = 0; i < npc; ++i) {
-        any_side |= pc[i].side;
-        if ((pc[i].form == FORM_PAIR && r.cert) || pc[i].form == FORM_MFMA || pc[i].form == FORM_MFMA2) {
-          q0 = pc[i].p0 < q0 ? pc[i].p0 : q0;
-          q1 = pc[i].p1 > q1 ? pc[i].p1 : q1;
-        }
-      }
-      // flagged problems of the pieces [q0, q1): exact rule on the single-row form, on the caller's stream (after the join)
-      auto finish = [&](int rc) -> int {
-        if (rc != PB_OK || q1 <= q0 || !resolve) return rc;
-        pb::FistaArgs b = a;
-        b.p0 = q0;
-        b.P = q1;
-        b.only_flagged = 1;
-        return launched(fe->fn(b, taps_host, K, wj, stop_mode, user), "pb_fista_solve: no single-row form for the re-solve", "fista_fast_kernel(re-solve)");
-      };
-      std::unique_lock<std::mutex> lock(g_side_mutex, std::defer_lock);
-      SideStream* ss = nullptr;
-      if (any_side) {
-        lock.lock();
-        ss = side_stream_locked();
-      }
-      if (!ss) {                                   // (no side stream: the same pieces, one after the other)
-        for (int i = 0; i < npc; ++i) {
-          const int rc = run(pc[i].form, pc[i].p0, pc[i].p1, user);
-          if (rc != PB_OK) return rc;
-        }
-        return finish(PB_OK);
-      }
-      int rc_all = PB_OK;
-      bool forked = false;
-      for (int i = 0; i < npc && rc_all == PB_OK; ++i) {
-        if (pc[i].group && !forked) {              // whole rounds are in the queue: the group starts here
-          if (hipEventRecord(ss->fork, user) != hipSuccess || hipStreamWaitEvent(ss->stream, ss->fork, 0) != hipSuccess)
-            return fail(PB_ERR_HIP, "pb_fista_solve: fork to the side stream failed");
-          forked = true;
-        }
-        rc_all = run(pc[i].form, pc[i].p0, pc[i].p1, pc[i].side ? ss->stream : user);
-      }
-      if (!forked) return finish(rc_all);
-      // join even after an error so that the caller's stream never runs ahead of the side stream
-      if (hipEventRecord(ss->join, ss->stream) != hipSuccess || hipStreamWaitEvent(user, ss->join, 0) != hipSuccess)
-        return fail(PB_ERR_HIP, "pb_fista_solve: join of the side stream failed");
-      return finish(rc_all);
-    }
-    case PATH_MFMA_WIDE:
-      return run_passes(a, r.base, resolve, user,
-        [&](const pb::FistaArgs& b, hipStream_t st) {
-          return launched(r.mfma(b, taps_host, K, wj, st), "pb_fista_solve: matrix-pipe kernel rejected the launch", "fista_mfma_kernel");
-        },
-        [&](const pb::FistaArgs& b, hipStream_t st) {
-          const int bad = r.we->fn(b, taps_host, K, wj, stop_mode, st);
-          if (b.only_flagged) return launched(bad, "pb_fista_solve: no one-problem-per-wave form for the re-solve", "fista_fast_kernel(wide, re-solve)");
-          return launched(bad, "pb_fista_solve: no one-problem-per-wave form", "fista_fast_kernel(wide)");
-        });
-    case PATH_WIDE:
-      return launched(r.we->fn(a, taps_host, K, wj, stop_mode, user), "pb_fista_solve: no one-problem-per-wave form for this stop rule",
-                      "fista_fast_kernel(wide)");
-    case PATH_GENERIC:
-      break;
-  }
+  const HostTapsForms lf{r, "pb_fista_solve", taps_host, K, stop_mode, J_dev != nullptr, (flags & PB_FLAG_DIRECT_FIR) != 0};
+  if (r.path == PATH_PART_LONG || r.path == PATH_PART_SHORT)
+    return run_partition(r, a, lf, user, taps_host, taps_dev, flags, dense_ratio, work_dev);
+  if (r.path != PATH_GENERIC) return run_in_place(r, a, lf, user, flags);
   if (flags & PB_FLAG_FORCE_FAST)
     return fail(PB_ERR_INVALID, "pb_fista_solve: no register-resident kernel for N=%d K=%d stop=%d",
                 N, K, stop_mode);
   // generic path (any N, K that fit LDS; all stop rules)
   if (!taps_dev) return fail(PB_ERR_INVALID, "pb_fista_solve: taps_dev required for the generic kernel");
-  if (nd_g > LDS_DOUBLES_MAX)
+  if (gen_lds_doubles(N, K, stop_mode, wind) > LDS_DOUBLES_MAX)
     return fail(PB_ERR_INVALID, "pb_fista_solve: N=%d K=%d wind=%d exceeds LDS", N, K, wind);
-  const size_t lds = (size_t)nd_g * sizeof(double);
-  if (J_dev)
-    hipLaunchKernelGGL((pb::fista_generic_kernel<true>), dim3(P), dim3(pb::GEN_THREADS), lds, user, a, taps_dev, K, wind);
-  else
-    hipLaunchKernelGGL((pb::fista_generic_kernel<false>), dim3(P), dim3(pb::GEN_THREADS), lds, user, a, taps_dev, K, wind);
+  launch_generic(a, taps_dev, K, wind, J_dev != nullptr, false, P, user);
   return check_launch("fista_generic_kernel");
 }
 
@@ -1455,13 +858,7 @@ int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
       return fail(PB_ERR_INVALID, "pb_fista_solve_d: launch rejected");
     return check_launch(split ? "fista_exact_split_kernel" : "fista_exact_kernel");
   }
-  const size_t lds = (size_t)nd * sizeof(double);
-  if (J_dev)
-    hipLaunchKernelGGL((pb::fista_generic_kernel<true, true>), dim3(P), dim3(pb::GEN_THREADS), lds,
-                       (hipStream_t)stream, a, taps_dev, K, wind);
-  else
-    hipLaunchKernelGGL((pb::fista_generic_kernel<false, true>), dim3(P), dim3(pb::GEN_THREADS), lds,
-                       (hipStream_t)stream, a, taps_dev, K, wind);
+  launch_generic(a, taps_dev, K, wind, J_dev != nullptr, true, P, (hipStream_t)stream);
   return check_launch("fista_generic_kernel(f64)");
 }
 
@@ -1486,7 +883,7 @@ int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw,
   if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: wind=%d (the device-resident search carries wind = 6)", wind);
   if (N > 640) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: N=%d exceeds 640 scans", N);
   if (K > 32) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: K=%d exceeds 32 taps", K);
-  const AutoEntry* ae = pick_auto(N, K);
+  const ExactEntry* ae = pick_auto(N, K);
   if (!ae) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: no specialisation for N=%d K=%d", N, K);
   if (nb_iter < 1 || nb_sub_iter < 0 || outer_chunk < 0)
     return fail(PB_ERR_INVALID, "pb_auto_lbda_d: nb_iter >= 1, nb_sub_iter >= 0 and outer_chunk >= 0 are required (%d, %d, %d)",
@@ -1509,12 +906,12 @@ int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw,
   const int chunk = outer_chunk > 0 ? outer_chunk : auto_outer_chunk(V, nb_sub_iter);
   for (int i0 = 0; i0 < nb_iter; i0 += chunk) {        // outer iterations [i0, i1) of the voxels still searching
     a.init = i0 == 0; a.i0 = i0; a.i1 = (nb_iter - i0 < chunk) ? nb_iter : i0 + chunk; a.final_solve = 0;
-    ae->fn(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
+    ae->fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
     const int rc = check_launch("auto_lbda_kernel");
     if (rc != PB_OK) return rc;
   }
   a.init = 0; a.i0 = a.i1 = nb_iter; a.final_solve = 1;   // the last inner solve of every voxel, then the outputs
-  ae->fn(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
+  ae->fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
   return check_launch("auto_lbda_kernel(final solve)");
 }
 
@@ -1548,31 +945,13 @@ int pb_fista_solve_backtrack_d(const double* y_dev, int64_t ldy, int y_rep, doub
 
 int pb_fista_outputs(const double* w_dev, int64_t ldw, int P, int N, const double* taps_dev, int K,
                      double* z_dev, int64_t ldz, double* x_dev, int64_t ldx, void* stream) {
-  if (P < 0 || N < 1 || K < 1 || ldw < N || (z_dev && ldz < N) || (x_dev && ldx < N))
-    return fail(PB_ERR_INVALID, "pb_fista_outputs: bad size");
-  if (2 * (int64_t)N + K + 8 > LDS_DOUBLES_MAX)
-    return fail(PB_ERR_INVALID, "pb_fista_outputs: N=%d K=%d exceeds LDS", N, K);
-  if (P == 0 || (!z_dev && !x_dev)) return PB_OK;
-  if (!w_dev || !taps_dev) return fail(PB_ERR_INVALID, "pb_fista_outputs: NULL pointer");
-  const size_t lds = (size_t)(2 * N + K + 8) * sizeof(double);
-  hipLaunchKernelGGL(pb::outputs_kernel, dim3(P), dim3(pb::GEN_THREADS), lds, (hipStream_t)stream,
-                     w_dev, ldw, N, taps_dev, (int64_t)0, K, z_dev, ldz, x_dev, ldx);
-  return check_launch("outputs_kernel");
+  return outputs_impl(w_dev, ldw, P, N, taps_dev, 0, K, z_dev, ldz, x_dev, ldx, stream, false, "pb_fista_outputs");
 }
 
 int pb_fista_outputs_pp(const double* w_dev, int64_t ldw, int P, int N, const double* taps_dev,
                         int64_t ldt, int K, double* z_dev, int64_t ldz, double* x_dev, int64_t ldx,
                         void* stream) {
-  if (P < 0 || N < 1 || K < 1 || ldw < N || ldt < K || (z_dev && ldz < N) || (x_dev && ldx < N))
-    return fail(PB_ERR_INVALID, "pb_fista_outputs_pp: bad size");
-  if (2 * (int64_t)N + K + 8 > LDS_DOUBLES_MAX)
-    return fail(PB_ERR_INVALID, "pb_fista_outputs_pp: N=%d K=%d exceeds LDS", N, K);
-  if (P == 0 || (!z_dev && !x_dev)) return PB_OK;
-  if (!w_dev || !taps_dev) return fail(PB_ERR_INVALID, "pb_fista_outputs_pp: NULL pointer");
-  const size_t lds = (size_t)(2 * N + K + 8) * sizeof(double);
-  hipLaunchKernelGGL(pb::outputs_kernel, dim3(P), dim3(pb::GEN_THREADS), lds, (hipStream_t)stream,
-                     w_dev, ldw, N, taps_dev, ldt, K, z_dev, ldz, x_dev, ldx);
-  return check_launch("outputs_kernel(pp)");
+  return outputs_impl(w_dev, ldw, P, N, taps_dev, ldt, K, z_dev, ldz, x_dev, ldx, stream, true, "pb_fista_outputs_pp");
 }
 
 int pb_spm_hrf(const double* deltas_dev, int M, const double* t_dev, int K, double a_peak,
@@ -1735,9 +1114,7 @@ int pb_theta_fit(const double* ne_dev, int64_t ldne, int M, int K, const double*
   if (M == 0) return PB_OK;
   if (!ne_dev || !t_dev || !theta_dev || !cost_dev)
     return fail(PB_ERR_INVALID, "pb_theta_fit: NULL pointer");
-  pb::HrfModel hm{a_peak, loc_peak, lgamma(a_peak), a_under, loc_under, lgamma(a_under), ratio,
-                  pb::hrf_int_power(a_peak), pb::hrf_int_power(a_under), std::exp(-lgamma(a_peak)),
-                  std::exp(-lgamma(a_under))};
+  const pb::HrfModel hm = hrf_model(a_peak, loc_peak, a_under, loc_under, ratio);
   hipLaunchKernelGGL(pb::theta_fit_kernel, dim3(M), dim3(256), (size_t)nd * sizeof(double),
                      (hipStream_t)stream, ne_dev, ldne, M, K, t_dev, hm, lo, hi, n_refine, theta_dev,
                      cost_dev, taps_dev, ldt, 0, (double*)nullptr, 0.0, (double*)nullptr);
@@ -1755,9 +1132,7 @@ int pb_theta_fit_step(const double* msg_dev, int K, const double* t_dev, double 
   if (nd > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "pb_theta_fit_step: K=%d exceeds LDS", K);
   if (!msg_dev || !t_dev || !theta_dev || !cost_dev || !taps_dev || !step_dev || !jcost_dev)
     return fail(PB_ERR_INVALID, "pb_theta_fit_step: NULL pointer");
-  pb::HrfModel hm{a_peak, loc_peak, lgamma(a_peak), a_under, loc_under, lgamma(a_under), ratio,
-                  pb::hrf_int_power(a_peak), pb::hrf_int_power(a_under), std::exp(-lgamma(a_peak)),
-                  std::exp(-lgamma(a_under))};
+  const pb::HrfModel hm = hrf_model(a_peak, loc_peak, a_under, loc_under, ratio);
   hipLaunchKernelGGL(pb::theta_fit_kernel, dim3(1), dim3(256), (size_t)nd * sizeof(double),
                      (hipStream_t)stream, msg_dev, (int64_t)pb::ne_len(K) + 1, 1, K, t_dev, hm, lo, hi,
                      n_refine, theta_dev, cost_dev, taps_dev, (int64_t)K, N, step_dev, lbda, jcost_dev);
@@ -1820,109 +1195,12 @@ int pb_fista_solve_pp(const float* y_dev, int64_t ldy, double* w_dev, int64_t ld
   pb::FistaArgs a = fista_args(P, N, K, n_iter, 1, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, stop_mode, tol, n_done_dev, flags);
   a.y = y_dev; a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = (ldt == 0);
   const hipStream_t user = (hipStream_t)stream;
-  const bool resolve = !(flags & PB_FLAG_CERT_NO_RESOLVE);
-
-  // ONE shared HRF, no stop rule, series of 311 .. 1 280 scans: whole passes on the matrix-pipe form split over two
-  // (up to 640 scans) or four waves, which read the HRF and its step from device memory; the rest, and what the guards hand
-  // back, on the one-problem-per-wave form
-  if (N > MFMA1_NMAX && ldt == 0 && stop_mode == PB_STOP_NONE && n_done_dev && K <= 65 && !(flags & FLAGS_VECTOR_ONLY)) {
-    const bool four = N > 640;
-    const launch_fn split = four ? pick_mfma4(N, K, false) : pick_mfma2(N, K, false);
-    const WideEntry* we = pick_wide(N, K);
-    if (split && we && (four || P >= mfma2_long_min_p(K) || (flags & PB_FLAG_FORCE_MFMA2))) {
-      const bool all = (flags & (PB_FLAG_ONE_LAUNCH | PB_FLAG_FORCE_MFMA2)) != 0;
-      return run_passes(a, four ? mfma4_base(P, all) : mfma2_long_base(P, all), resolve, user,
-        [&](const pb::FistaArgs& b, hipStream_t st) {
-          return launched(split(b, nullptr, K, false, st), "pb_fista_solve_pp: split matrix-pipe kernel rejected the launch",
-                          four ? "fista_mfma4_kernel(shared taps)" : "fista_mfma2_kernel(shared taps)");
-        },
-        [&](const pb::FistaArgs& b, hipStream_t st) {
-          return launched(we->fn_pp(b, stop_mode, st), "pb_fista_solve_pp: launch rejected",
-                          b.only_flagged ? "fista_fast_kernel(wide, pp, re-solve)" : "fista_fast_kernel(wide, pp, remainder)");
-        });
-    }
-  }
-  const FastEntry* fe = (flags & PB_FLAG_FORCE_GENERIC) ? nullptr : pick_fast(N, K);
-  if (fe) {
-    // ONE shared HRF, no stop rule: the pair form (taps read from device memory) wherever the
-    // dispatch model of plain solves would use it, the per-problem-taps kernel elsewhere
-    if (ldt == 0 && stop_mode == PB_STOP_NONE && fe->fn_pair_dev && P >= 2 &&
-        !(flags & (PB_FLAG_NO_PAIR | PB_FLAG_DIRECT_FIR))) {
-      // (the remainder of the whole rounds on the single-row or the one-problem-per-wave kernel,
-      // both reading the shared HRF through their per-problem-taps form)
-      const WideEntry* ws = pick_wide_small(N, K);
-      auto run = [&](int form, int p0, int p1, hipStream_t st) -> int {
-        pb::FistaArgs b = a;
-        b.p0 = p0;
-        b.P = p1;
-        const int bad = (form == FORM_PAIR)   ? fe->fn_pair_dev(b, st)
-                        : (form == FORM_WIDE) ? ws->fn_pp(b, stop_mode, st)
-                                              : fe->fn_pp(b, stop_mode, st);
-        return launched(bad, "pb_fista_solve_pp: launch rejected", form == FORM_PAIR ? "fista_pair_ffa_kernel(shared taps)" : "fista_fast_kernel(pp)");
-      };
-      // whole rounds (and a remainder above half a round) on the matrix-pipe form, which reads the
-      // shared HRF and its step from device memory like the pair form; what the whole rounds leave goes to the
-      // split form (fista_mfma2.h: half the latency for up to half a round) where plan_pieces_mfma would put it
-      const launch_fn mfma = (n_done_dev && !(flags & (PB_FLAG_FORCE_PAIR | PB_FLAG_NO_MFMA))) ? pick_mfma(N, K, false) : nullptr;
-      const launch_fn mfma2 = (mfma && K <= MFMA_K2) ? pick_mfma2(N, K, false) : nullptr;
-      int base = 0, base2 = 0;                     // problems [0, base) on the matrix-pipe form, [base, base2) on the split form
-      if (mfma) {
-        const int round = (int)wave_slots() * 8, half = round / 2;
-        base = (P / round) * round;
-        const int R = P - base;
-        base2 = base;
-        if (flags & PB_FLAG_ONE_LAUNCH) base = base2 = P;
-        else if (mfma2 && R > MFMA2_MIN_R && R <= half) base2 = P;
-        else if (mfma2 && ws && R > half && R - half <= (int)wave_slots()) base2 = base + half;
-        else if (R > half) base = base2 = P;
-      }
-      return run_passes(a, base2, resolve, user,
-        [&](const pb::FistaArgs& m, hipStream_t st) -> int {
-          pb::FistaArgs b = m;
-          if (base > 0) {
-            b.P = base;
-            const int rc = launched(mfma(b, nullptr, K, false, st), "pb_fista_solve_pp: matrix-pipe kernel rejected the launch",
-                                    "fista_mfma_kernel(shared taps)");
-            if (rc != PB_OK || base2 == base) return rc;
-          }
-          b = m;
-          b.p0 = base;
-          return launched(mfma2(b, nullptr, K, false, st), "pb_fista_solve_pp: split matrix-pipe kernel rejected the launch",
-                          "fista_mfma2_kernel(shared taps)");
-        },
-        [&](const pb::FistaArgs& b, hipStream_t st) -> int {
-          if (b.only_flagged)                      // (problems the matrix-pipe form handed back: n_done = -1)
-            return launched(fe->fn_pp(b, stop_mode, st), "pb_fista_solve_pp: launch rejected", "fista_fast_kernel(pp, re-solve)");
-          Plan pl{0, FORM_GENERIC, FORM_PAIR};
-          if (!(flags & PB_FLAG_FORCE_PAIR))
-            pl = plan_plain(P - base2, P - base2 >= 2, ws != nullptr, (flags & PB_FLAG_ONE_LAUNCH) != 0);
-          if (pl.n_main > 0) {
-            const int rc = run(pl.main_form, base2, base2 + pl.n_main, st);
-            if (rc != PB_OK) return rc;
-          }
-          return run(pl.tail_form, base2 + pl.n_main, P, st);
-        });
-    }
-    // one HRF per problem: single-row form, or one problem per wave where that finishes first
-    // (small batches are latency-bound: 0.37 ms against 0.93 ms per 500 iterations up to 2 048)
-    if (!(flags & (PB_FLAG_NO_PAIR | PB_FLAG_FORCE_PAIR | PB_FLAG_ONE_LAUNCH))) {
-      const WideEntry* ws = pick_wide_small(N, K);
-      if (ws && best_form(P, false, true) == FORM_WIDE) {
-        return launched(ws->fn_pp(a, stop_mode, user), "pb_fista_solve_pp: launch rejected", "fista_fast_kernel(wide, pp)");
-      }
-    }
-    return launched(fe->fn_pp(a, stop_mode, user), "pb_fista_solve_pp: launch rejected", "fista_fast_kernel(pp)");
-  }
-  if (!(flags & PB_FLAG_FORCE_GENERIC)) {
-    if (const WideEntry* we = pick_wide(N, K))
-      return launched(we->fn_pp(a, stop_mode, user), "pb_fista_solve_pp: launch rejected", "fista_fast_kernel(wide, pp)");
-  }
+  const Route r = route_pp(N, K, P, ldt == 0, stop_mode, n_done_dev != nullptr, flags);
+  if (r.path != PATH_GENERIC) return run_in_place(r, a, DeviceTapsForms{r, "pb_fista_solve_pp", K, stop_mode}, user, flags);
   if (flags & PB_FLAG_FORCE_FAST)
     return fail(PB_ERR_INVALID, "pb_fista_solve_pp: no register-resident kernel for N=%d K=%d", N, K);
-  const int64_t nd = gen_lds_doubles(N, K, stop_mode, 0);
-  if (nd > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "pb_fista_solve_pp: N=%d K=%d exceeds LDS", N, K);
-  hipLaunchKernelGGL((pb::fista_generic_kernel<false>), dim3(P), dim3(pb::GEN_THREADS),
-                     (size_t)nd * sizeof(double), user, a, taps_dev, K, 0);
+  if (gen_lds_doubles(N, K, stop_mode, 0) > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "pb_fista_solve_pp: N=%d K=%d exceeds LDS", N, K);
+  launch_generic(a, taps_dev, K, 0, false, false, P, user);
   return check_launch("fista_generic_kernel(pp)");
 }
 

@@ -247,8 +247,9 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
     stop  None | "loops" (_loops_deconv rule) | "window" (deconv rule)
     lmax  optional float64 CUDA ``(V,)``: :func:`lambda_max` of every series, if the caller has it (a regularisation
           path, BASELINE config 5, does); otherwise the library computes it when it partitions the call: the problems
-          with ``lbda < dense_ratio * lmax`` (default 0.13) run on the matrix-pipe form, the sparse rest on the float32
-          vector forms (``pb_fista_solve_ex``; any call shape since round 5)
+          with ``lbda < dense_ratio * lmax`` run on the matrix-pipe form, the sparse rest on the float32 vector forms
+          (``pb_fista_solve_ex``; any call shape since round 5).  ``dense_ratio <= 0`` takes the default for the series
+          length: ``PB_PATH_DENSE_RATIO`` 0.19 up to 310 scans, ``_LONG`` 0.22 up to 640, ``_LONGER`` 0.26 up to 1 280
     Returns ``(W float64 (P, N), J float32 (P, n_iter) or None, n_done int32 (P,))``.
     """
     lib = _lib.load()
