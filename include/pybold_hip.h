@@ -14,7 +14,12 @@
  *     device); pointers named *_host are host pointers read synchronously
  *     before the call returns; nothing else is dereferenced on the host;
  *   - matrices are row-major, one row per problem ("voxel"), leading dimension
- *     ld* counted in ELEMENTS;
+ *     ld* counted in ELEMENTS (ld >= the row length, else PB_ERR_INVALID).  A matrix may be a window of a larger
+ *     buffer (pitched allocations, a slice of a batch): no alignment beyond the element's own is required of a matrix
+ *     pointer or of a row start; an output matrix is written only at [rows) x [0, n), never in the ld - n elements
+ *     behind a row nor past the last row; an input is never written, and never read outside its rows.  The same
+ *     holds for vectors (n_done, lbda, ...) and for the workspaces, which are written within their stated lengths
+ *     only (tests/test_gpu_layout.py pins all of it on every solver form);
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream);
  *     all work is enqueued asynchronously in its order, no device memory is allocated, no
  *     host synchronisation is performed (graph-capture safe).  One exception to "on it":

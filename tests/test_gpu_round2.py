@@ -660,8 +660,10 @@ def test_normal_equations_any_tap_count(solver, n, K):
 def test_padded_rows_and_views(solver, golden, force):
     """Leading dimensions larger than the series (row views of wider buffers, the layout an
     allocator with padded pitches hands over): y float32 / float64 with ld > N, per-problem
-    lambda as a strided view, warm start from a view -- same results as contiguous copies,
-    nothing written outside the N columns."""
+    lambda as a strided view, warm start from a view -- same results as contiguous copies, the
+    inputs unchanged inside their N columns.  (The outputs are contiguous here, and the pads are
+    not looked at: that nothing is written outside a window, on any buffer and any solver form,
+    is tests/test_gpu_layout.py's to check, on framed buffers with sentinels around them.)"""
     g = golden("case1")
     hrf, lip = g["hrf"], float(g["lipschitz"])
     rng = np.random.RandomState(21)
