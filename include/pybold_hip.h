@@ -184,6 +184,7 @@ int pb_fista_plan_ex(int N, int K, int P, int stop_mode, int wind, unsigned flag
  *   641 .. 1280  <= 33     (b)                  (b) certificate          (b) in full           fista_mfma4_kernel, four waves per 16 problems
  *   641 .. 1280  34 .. 48  (b)                  (b) certificate          (b) in full           ... with three near tiles
  *   <= 640       <= 32     the noise-driven lambda search (deconv with lbda = None), wind 6, float64 end to end:        auto_lbda_kernel, one voxel per wave (pb_auto_lbda_d)
+ *   641 .. 1280  <= 32     ... the same search, opt-in by name:                                                        auto_lbda_split_kernel, one voxel per workgroup of four waves (pb_auto_lbda_split_d)
  *   longer series, longer HRFs, other windows, a cost trace beside the _loops_deconv rule: (a), one problem per wave up to
  *   2 432 scans, the LDS kernel beyond (and for the window rule beyond 1 280 scans, for 34+ taps beyond 1 280).  Per-problem HRFs (pb_fista_solve_pp, ldt != 0): (a).  A machine-filling batch that lands
  *   on (a) although (b) serves neighbouring shapes is 1.5 .. 4x below the matrix-pipe rate; the Python layer says so once.
@@ -506,8 +507,9 @@ int pb_lambda_max_d(const double* y_dev, int64_t ldy, int V, int N, const double
 
 /*
  * The noise-driven lambda search of deconv (lbda = None: the reference's DEFAULT call, pybold/bold_signal.py:99-214)
- * as one device-resident solve: one voxel per wave64 (auto_lbda_kernel, csrc/fista_auto.h), float64 end to end, no
- * host round trip between outer iterations.  Per voxel, as oracle/pybold_oracle.py::deconv_auto_lbda states the branch:
+ * as one device-resident solve: one voxel per wave64 (auto_lbda_kernel, csrc/fista_auto.h) for series of up to 640
+ * scans, one voxel per workgroup of four waves (auto_lbda_split_kernel, csrc/fista_auto_split.h) for 641 .. 1 280 scans;
+ * float64 end to end, no host round trip between outer iterations.  Per voxel, as oracle/pybold_oracle.py::deconv_auto_lbda states the branch:
  *   alpha = 1, lbda = 1 / (2 alpha), mu = 1e-4                                                       (:104-106)
  *   for i < nb_iter:  inner solve from w (momentum restarted, <= nb_sub_iter iterations of the recurrence of
  *                     pb_fista_solve_d, threshold lbda * step, window rule wind = 6 when early_stopping)   (:114-138)
@@ -537,6 +539,16 @@ int pb_lambda_max_d(const double* y_dev, int64_t ldy, int V, int N, const double
  * outer_chunk = 0: the library chooses max(1, 65536 / (nb_sub_iter * ceil(V / 2048))), i.e. about 65536 inner
  * iterations per wave slot and launch.  The chunking changes no bit of any output.
  * Errors (nothing is launched): wind != 6, N > 640, K > 32, nb_iter < 1, NULL pointers, a workspace too small.
+ *
+ * pb_auto_lbda_split_supported  1 if the four-wave search runs for (N, K, wind): 641 <= N <= 1280, K <= 32, wind = 6; else 0.
+ *                         Host-only query.  pb_auto_lbda_supported and pb_auto_lbda_d keep their limit of 640 scans: the
+ *                         four-wave search is asked for by name.
+ * pb_auto_lbda_split_d    the arguments, the workspace (pb_auto_lbda_work_len), the validation and its order, the launch
+ *                         protocol and the outputs of pb_auto_lbda_d, with one voxel per workgroup of four waves.
+ *                         outer_chunk = 0: the library chooses max(1, 32768 / (nb_sub_iter * ceil(V / 512))): 512 workgroups
+ *                         of this kernel are resident at once (two per compute unit), and its inner iteration takes about
+ *                         twice that of the one-wave kernel, so the budget per slot and launch is half as large.
+ * Errors (nothing is launched): those of pb_auto_lbda_d, with N outside 641..1280 in the place of N > 640.
  */
 int pb_auto_lbda_supported(int N, int K, int wind);
 int64_t pb_auto_lbda_work_len(int V);
@@ -546,6 +558,13 @@ int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw,
                    int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldt,
                    double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev,
                    double* work_dev, int64_t work_len, void* stream);
+int pb_auto_lbda_split_supported(int N, int K, int wind);
+int pb_auto_lbda_split_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                         const double* taps_host, int K, double step, const double* betas_dev,
+                         const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter,
+                         int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldt,
+                         double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev,
+                         double* work_dev, int64_t work_len, void* stream);
 
 /*
  * sigma[v] = MAD of the level-1 db3 detail band of row v, divided by c (mad_daub_noise_est, pybold/utils.py:10-25;

@@ -146,6 +146,14 @@ SIGNATURES = {
         _ptr, _ptr, _ptr, _c_i64,                               # R_dev, G_dev, J_dev, ldt
         _ptr, _ptr, _ptr, _ptr,                                 # alpha_dev, lbda_dev, n_outer_dev, n_inner_dev
         _ptr, _c_i64, _ptr]),                                   # work_dev, work_len, stream
+    "pb_auto_lbda_split_supported": (_c_int, [_c_int, _c_int, _c_int]),
+    "pb_auto_lbda_split_d": (_c_int, [                          # (the argument list of pb_auto_lbda_d)
+        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
+        _ptr, _c_int, _c_dbl, _ptr, _ptr,
+        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,
+        _ptr, _ptr, _ptr, _c_i64,
+        _ptr, _ptr, _ptr, _ptr,
+        _ptr, _c_i64, _ptr]),
     "pb_mad_daub_noise_est": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_dbl, _ptr, _ptr]),
     "pb_mad_daub_noise_est_d": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_dbl, _ptr, _ptr]),
     "pb_inf_norm": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_i64, _ptr]),

@@ -84,7 +84,9 @@ DISPATCH = os.environ.get("PYBOLD_AMD_DISPATCH", "ctypes")
 # Which engine a 2-D `deconv(lbda=None)` runs on: "host" (the default: `_deconv_auto_lbda`, one launch over all voxels per
 # outer iteration, the outer loop in NumPy) or "device" (`deconv_auto(engine="device")`: the whole search resident on
 # the device, one voxel per wave -- series of up to 640 scans, HRFs of up to 32 taps, wind = 6; other shapes keep the
-# host loop).  1-D calls always keep the host loop.  Initialised from the environment variable PYBOLD_AMD_AUTO_LBDA.
+# host loop) or "device_split" (the same, and series of 641 .. 1 280 scans on the search with one voxel per workgroup of four
+# waves, `deconv_auto(engine="device_split")`; shapes neither carries keep the host loop).  1-D calls always keep the host
+# loop.  Initialised from the environment variable PYBOLD_AMD_AUTO_LBDA.
 AUTO_LBDA = os.environ.get("PYBOLD_AMD_AUTO_LBDA", "host")
 
 
@@ -100,9 +102,13 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
     ``(V, max iterations run)`` padded with NaN after a voxel's early stop.
     """
     if lbda is None:
-        if AUTO_LBDA == "device" and _n_dim(y) == 2 and solver.auto_lbda_supported(_n_scans(y), np.size(hrf), wind):
-            return deconv_auto(y, t_r, hrf, early_stopping=early_stopping, tol=tol, wind=wind, nb_iter=nb_iter,
-                               nb_sub_iter=nb_sub_iter, engine="device", verbose=verbose)[:6]
+        if AUTO_LBDA in ("device", "device_split") and _n_dim(y) == 2:
+            engine = ("device" if solver.auto_lbda_supported(_n_scans(y), np.size(hrf), wind)
+                      else "device_split" if AUTO_LBDA == "device_split" and solver.auto_lbda_split_supported(_n_scans(y), np.size(hrf), wind)
+                      else None)
+            if engine:
+                return deconv_auto(y, t_r, hrf, early_stopping=early_stopping, tol=tol, wind=wind, nb_iter=nb_iter,
+                                   nb_sub_iter=nb_sub_iter, engine=engine, verbose=verbose)[:6]
         return _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, verbose)
     Y, one_d = _y_to_device(y)
     n = Y.shape[1]
@@ -167,7 +173,10 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     engine  "device": the whole search as one device-resident solve (``solver.auto_lbda_solve``: one voxel per
             wave, no host round trip; series of up to 640 scans, HRFs of up to 32 taps, ``wind == 6`` --
             ``ValueError`` otherwise); "host": the host-driven loop ``deconv(lbda=None)`` runs by default;
-            "auto": the device where it carries the call, else the host loop with one warning
+            "auto": the device where it carries the call, else the host loop with one warning;
+            "device_split": the device-resident solve with one voxel per workgroup of four waves
+            (``solver.auto_lbda_solve_split``: series of 641 .. 1 280 scans, HRFs of up to 32 taps, ``wind == 6`` --
+            ``ValueError`` otherwise; ``"device"`` and ``"auto"`` do not reach it)
     outer_chunk  device engine: outer iterations per kernel launch (``None``: the library's choice); no effect on
             the result
 
@@ -175,10 +184,15 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     same input (lists for a 1-D ``y``; ``(n_outer, V)`` arrays padded with NaN for a batch, trimmed to the longest
     row's outer iterations; CUDA in -> ``x, z, diff_z`` CUDA); ``info`` holds ``alpha``, ``lbda`` (final, per
     voxel), ``n_outer``, ``n_inner`` (outer / summed inner iterations per voxel), ``sigma`` and ``engine``."""
-    if engine not in ("auto", "device", "host"):
-        raise ValueError("deconv_auto: engine must be 'auto', 'device' or 'host', got %r" % (engine,))
+    if engine not in ("auto", "device", "host", "device_split"):
+        raise ValueError("deconv_auto: engine must be 'auto', 'device', 'host' or 'device_split', got %r" % (engine,))
     n, n_taps = _n_scans(y), int(np.size(hrf))
-    if engine != "host":
+    if engine == "device_split":
+        if not solver.auto_lbda_split_supported(n, n_taps, wind):
+            raise ValueError("deconv_auto(engine='device_split'): the four-wave device-resident lambda search carries series of "
+                             "641..1280 scans, HRFs of up to 32 taps and wind = 6; this call has %d scans, %d taps, wind = %d"
+                             % (n, n_taps, wind))
+    elif engine != "host":
         if solver.auto_lbda_supported(n, n_taps, wind):
             engine = "device"
         else:
@@ -212,9 +226,9 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     hrf = np.asarray(hrf, dtype=np.float64)
     H = ConvAndLinear(DiscretInteg(), hrf, dim_in=n, dim_out=n)
     step = 1.0 / (0.9 * spectral_radius_est(H, (n,)))
-    W, res = solver.auto_lbda_solve(Y, hrf, step, sigma, early_stopping=early_stopping, tol=tol, wind=wind,
-                                    nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter),
-                                    outer_chunk=int(outer_chunk or 0))
+    solve = solver.auto_lbda_solve_split if engine == "device_split" else solver.auto_lbda_solve
+    W, res = solve(Y, hrf, step, sigma, early_stopping=early_stopping, tol=tol, wind=wind,
+                   nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
     X, Z = solver.fista_outputs(W, hrf)
     n_outer = res["n_outer"].cpu().numpy()
     n_max = int(n_outer.max())
@@ -222,7 +236,7 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     info = {"alpha": res["alpha"].cpu().numpy(), "lbda": res["lbda"].cpu().numpy(), "n_outer": n_outer,
             "n_inner": res["n_inner"].cpu().numpy(),
             "sigma": sigma.cpu().numpy() if torch.is_tensor(sigma) else np.broadcast_to(np.asarray(sigma, dtype=np.float64), (V,)).copy(),
-            "engine": "device"}
+            "engine": engine}
     if verbose > 0:
         print("deconv_auto: {0} voxel(s), {1} outer iteration(s) at most, {2} inner iterations in all".format(
             V, n_max, int(info["n_inner"].sum())))

@@ -61,6 +61,18 @@ inline int auto_outer_chunk(int V, int nb_sub_iter) {
   return (int)(c < 1 ? 1 : c);
 }
 
+// the same for the search with one voxel per WORKGROUP of four waves (fista_auto_split.h): its register report allows two
+// waves per SIMD, i.e. two workgroups per compute unit, 512 resident at once on 256 compute units; an inner iteration of a
+// workgroup takes about twice that of a wave of the one-wave kernel (3.4 us against 1.5 us alone), so half the budget per
+// slot and launch keeps the longest dispatch under 0.25 s (measured 0.14 s at most: profiles/auto_lbda_split.txt)
+constexpr int AUTO_SPLIT_LAUNCH_ITERS = 32768, AUTO_SPLIT_WGS_PER_CU = 2, AUTO_SPLIT_RESIDENT_WGS = 256 * AUTO_SPLIT_WGS_PER_CU;
+inline int auto_split_outer_chunk(int V, int nb_sub_iter) {
+  const int64_t rounds = ((int64_t)V + AUTO_SPLIT_RESIDENT_WGS - 1) / AUTO_SPLIT_RESIDENT_WGS;
+  const int64_t per = (int64_t)(nb_sub_iter > 0 ? nb_sub_iter : 1) * (rounds > 0 ? rounds : 1);
+  const int64_t c = AUTO_SPLIT_LAUNCH_ITERS / per;
+  return (int)(c < 1 ? 1 : c);
+}
+
 constexpr int MAD_DAUB_NMAX = 8192;
 template <typename TY>
 int mad_daub_impl(const TY* y_dev, int64_t ldy, int V, int N, double c, double* sigma_dev, void* stream, const char* name) {
@@ -874,45 +886,72 @@ int pb_auto_lbda_supported(int N, int K, int wind) { return (wind == pb::AUTO_WI
 
 int64_t pb_auto_lbda_work_len(int V) { return (int64_t)pb::AUTO_STATE * (V > 0 ? V : 0); }
 
-int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+namespace {
+// pb_auto_lbda_d (split = false: one voxel per wave, up to 640 scans) and pb_auto_lbda_split_d (one voxel per workgroup of
+// four waves, 641 .. 1 280 scans): one validation in one order, one launch protocol; the kernels and the library's chunk differ
+int auto_lbda_impl(const char* name, bool split, const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
                    const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
                    int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
                    double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
                    int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
-  if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: bad size (V=%d N=%d K=%d)", V, N, K);
-  if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: wind=%d (the device-resident search carries wind = 6)", wind);
-  if (N > 640) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: N=%d exceeds 640 scans", N);
-  if (K > 32) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: K=%d exceeds 32 taps", K);
-  const ExactEntry* ae = pick_auto(N, K);
-  if (!ae) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: no specialisation for N=%d K=%d", N, K);
+  if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "%s: bad size (V=%d N=%d K=%d)", name, V, N, K);
+  if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "%s: wind=%d (the device-resident search carries wind = 6)", name, wind);
+  if (!split && N > 640) return fail(PB_ERR_INVALID, "%s: N=%d exceeds 640 scans", name, N);
+  if (split && (N < 641 || N > 1280)) return fail(PB_ERR_INVALID, "%s: N=%d outside 641..1280 scans", name, N);
+  if (K > 32) return fail(PB_ERR_INVALID, "%s: K=%d exceeds 32 taps", name, K);
+  const ExactEntry* ae = split ? pick_auto_split(N, K) : pick_auto(N, K);
+  if (!ae || !ae->fn_auto) return fail(PB_ERR_INVALID, "%s: no specialisation for N=%d K=%d", name, N, K);
   if (nb_iter < 1 || nb_sub_iter < 0 || outer_chunk < 0)
-    return fail(PB_ERR_INVALID, "pb_auto_lbda_d: nb_iter >= 1, nb_sub_iter >= 0 and outer_chunk >= 0 are required (%d, %d, %d)",
+    return fail(PB_ERR_INVALID, "%s: nb_iter >= 1, nb_sub_iter >= 0 and outer_chunk >= 0 are required (%d, %d, %d)", name,
                 nb_iter, nb_sub_iter, outer_chunk);
-  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: leading dimension < N");
-  if ((R_dev || G_dev || J_dev) && ldt < nb_iter) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: ldt < nb_iter");
-  if (!(step > 0.0)) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: step must be positive");
+  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "%s: leading dimension < N", name);
+  if ((R_dev || G_dev || J_dev) && ldt < nb_iter) return fail(PB_ERR_INVALID, "%s: ldt < nb_iter", name);
+  if (!(step > 0.0)) return fail(PB_ERR_INVALID, "%s: step must be positive", name);
   if (work_len < pb_auto_lbda_work_len(V))
-    return fail(PB_ERR_INVALID, "pb_auto_lbda_d: workspace of %lld float64, %lld needed", (long long)work_len,
+    return fail(PB_ERR_INVALID, "%s: workspace of %lld float64, %lld needed", name, (long long)work_len,
                 (long long)pb_auto_lbda_work_len(V));
   if (V == 0) return PB_OK;
   if (!y_dev || !w_dev || !taps_host || !sigma_dev || !work_dev || (nb_sub_iter > 0 && !betas_dev))
-    return fail(PB_ERR_INVALID, "pb_auto_lbda_d: NULL pointer");
-  if (V > (1 << 25)) return fail(PB_ERR_INVALID, "pb_auto_lbda_d: more than 2^25 voxels per call");
+    return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
+  if (V > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 voxels per call", name);
   pb::AutoArgs a;
   a.y = y_dev; a.ldy = ldy; a.w = w_dev; a.ldw = ldw; a.V = V; a.N = N;
   a.cold = cold ? 1 : 0; a.nb_sub_iter = nb_sub_iter; a.step = step; a.tol = tol;
   a.betas = betas_dev; a.sigma = sigma_dev; a.R = R_dev; a.G = G_dev; a.J = J_dev; a.ldt = ldt;
   a.alpha_out = alpha_dev; a.lbda_out = lbda_dev; a.n_outer = n_outer_dev; a.n_inner = n_inner_dev; a.work = work_dev;
-  const int chunk = outer_chunk > 0 ? outer_chunk : auto_outer_chunk(V, nb_sub_iter);
+  const int chunk = outer_chunk > 0 ? outer_chunk : (split ? auto_split_outer_chunk(V, nb_sub_iter) : auto_outer_chunk(V, nb_sub_iter));
   for (int i0 = 0; i0 < nb_iter; i0 += chunk) {        // outer iterations [i0, i1) of the voxels still searching
     a.init = i0 == 0; a.i0 = i0; a.i1 = (nb_iter - i0 < chunk) ? nb_iter : i0 + chunk; a.final_solve = 0;
     ae->fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
-    const int rc = check_launch("auto_lbda_kernel");
+    const int rc = check_launch(split ? "auto_lbda_split_kernel" : "auto_lbda_kernel");
     if (rc != PB_OK) return rc;
   }
   a.init = 0; a.i0 = a.i1 = nb_iter; a.final_solve = 1;   // the last inner solve of every voxel, then the outputs
   ae->fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
-  return check_launch("auto_lbda_kernel(final solve)");
+  return check_launch(split ? "auto_lbda_split_kernel(final solve)" : "auto_lbda_kernel(final solve)");
+}
+}  // namespace
+
+int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                   const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
+                   int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
+                   double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
+                   int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
+  return auto_lbda_impl("pb_auto_lbda_d", false, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev, sigma_dev,
+                        early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt, alpha_dev, lbda_dev,
+                        n_outer_dev, n_inner_dev, work_dev, work_len, stream);
+}
+
+int pb_auto_lbda_split_supported(int N, int K, int wind) { return (wind == pb::AUTO_WIND && pick_auto_split(N, K)) ? 1 : 0; }
+
+int pb_auto_lbda_split_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                         const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
+                         int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
+                         double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
+                         int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
+  return auto_lbda_impl("pb_auto_lbda_split_d", true, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev, sigma_dev,
+                        early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt, alpha_dev, lbda_dev,
+                        n_outer_dev, n_inner_dev, work_dev, work_len, stream);
 }
 
 int pb_mad_daub_noise_est(const float* y_dev, int64_t ldy, int V, int N, double c, double* sigma_dev, void* stream) {

@@ -11,6 +11,7 @@
 #include "fista_exact.h"
 #include "fista_exact_split.h"
 #include "fista_auto.h"
+#include "fista_auto_split.h"
 #include "fista_mfma.h"
 #include "fista_mfma2.h"
 #include "fista_mfma4.h"
@@ -151,7 +152,7 @@ typedef int (*auto_launch_fn)(const pb::AutoArgs&, const double* taps, int K, bo
 struct ExactEntry {
   int S, KT;
   exact_launch_fn fn;
-  auto_launch_fn fn_auto;     // the device-resident lambda search (fista_auto.h) on the same (S, KT); one wave per series only
+  auto_launch_fn fn_auto;     // the device-resident lambda search on the same (S, KT): fista_auto.h, or fista_auto_split.h with four waves per series
 };
 }  // namespace
 namespace pb {
@@ -160,8 +161,9 @@ namespace pb {
   extern template int launch_auto<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);
 #include "exact_table.inc"
 #undef PB_EXACT
-#define PB_EXACT_SPLIT(S, KT) \
-  extern template int launch_exact_split<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t);
+#define PB_EXACT_SPLIT(S, KT)                                                                                    \
+  extern template int launch_exact_split<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t); \
+  extern template int launch_auto_split<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);
 #include "exact_split_table.inc"
 #undef PB_EXACT_SPLIT
 }  // namespace pb
@@ -172,7 +174,7 @@ const ExactEntry kExact[] = {
 };
 #undef PB_EXACT
 // the same form with one series over the four waves of a workgroup (fista_exact_split.h): S samples per lane of each wave
-#define PB_EXACT_SPLIT(S, KT) {S, KT, &pb::launch_exact_split<S, KT>, nullptr},
+#define PB_EXACT_SPLIT(S, KT) {S, KT, &pb::launch_exact_split<S, KT>, &pb::launch_auto_split<S, KT>},
 const ExactEntry kExactSplit[] = {
 #include "exact_split_table.inc"
 };
@@ -198,6 +200,8 @@ const ExactEntry* pick_exact_any(int N, int K, int stop_mode, int wind, bool* sp
 }
 // the device-resident lambda search (fista_auto.h): the (S, KT) pairs of the all-float64 form
 const ExactEntry* pick_auto(int N, int K) { return (N >= 1 && K >= 1) ? pick_exact(N, K) : nullptr; }
+// ... with one voxel over the four waves of a workgroup (fista_auto_split.h): the shapes of the four-wave float64 form
+const ExactEntry* pick_auto_split(int N, int K) { return (N >= 1 && K >= 1) ? pick_exact_split(N, K) : nullptr; }
 
 template <int S, int KT>
 constexpr launch_fn pair_or_null() {

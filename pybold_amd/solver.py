@@ -850,6 +850,11 @@ def auto_lbda_supported(n_scans, n_taps, wind=6):
     return bool(_lib.load().pb_auto_lbda_supported(int(n_scans), int(n_taps), int(wind)))
 
 
+def auto_lbda_split_supported(n_scans, n_taps, wind=6):
+    """Whether :func:`auto_lbda_solve_split` carries this shape (``641 <= N <= 1280``, ``K <= 32``, ``wind == 6``)."""
+    return bool(_lib.load().pb_auto_lbda_split_supported(int(n_scans), int(n_taps), int(wind)))
+
+
 def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
                     outer_chunk=0, W0=None, want_trace=True):
     """The noise-driven lambda search of ``deconv(lbda=None)`` (pybold/bold_signal.py:99-214) for every row of ``Y``
@@ -862,6 +867,19 @@ def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6
     Returns ``(W, info)``: the final iterate and a dict of CUDA tensors ``alpha``, ``lbda`` (float64 ``(V,)``),
     ``n_outer`` (int32), ``n_inner`` (int64, inner iterations summed) and, with ``want_trace``, ``R``, ``G``, ``J``
     (float64 ``(V, nb_iter)``, NaN from a voxel's ``n_outer`` on)."""
+    return _auto_lbda_solve("pb_auto_lbda_d", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+                            outer_chunk, W0, want_trace)
+
+
+def auto_lbda_solve_split(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                          outer_chunk=0, W0=None, want_trace=True):
+    """:func:`auto_lbda_solve` for series of ``641 <= N <= 1280`` scans (``pb_auto_lbda_split_d``: one voxel per
+    workgroup of four waves): the same arguments, the same return value."""
+    return _auto_lbda_solve("pb_auto_lbda_split_d", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+                            outer_chunk, W0, want_trace)
+
+
+def _auto_lbda_solve(entry, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0, want_trace):
     lib = _lib.load()
     Y = _rows(Y, torch.float64, "Y")
     dev = Y.device
@@ -892,7 +910,7 @@ def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6
     n_inner = torch.empty((V,), dtype=torch.int64, device=dev)
     work = torch.empty((int(lib.pb_auto_lbda_work_len(V)),), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.pb_auto_lbda_d(
+        rc = getattr(lib, entry)(
             Y.data_ptr(), _ld(Y), W.data_ptr(), _ld(W), int(W0 is None), V, N,
             taps.ctypes.data, taps.size, float(step), betas.data_ptr(), sig.data_ptr(),
             int(bool(early_stopping)), float(tol), int(wind), nb_iter, nb_sub_iter, int(outer_chunk),
@@ -900,7 +918,7 @@ def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6
             trace[2].data_ptr() if want_trace else None, _ld(trace[0]) if want_trace else 0,
             alpha.data_ptr(), lbda.data_ptr(), n_outer.data_ptr(), n_inner.data_ptr(),
             work.data_ptr(), work.numel(), _stream_ptr(dev))
-    _lib.check(rc, "pb_auto_lbda_d")
+    _lib.check(rc, entry)
     return W, {"alpha": alpha, "lbda": lbda, "n_outer": n_outer, "n_inner": n_inner,
                "R": trace[0], "G": trace[1], "J": trace[2]}
 

@@ -50,6 +50,19 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop_mode=0, 
 def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
                     outer_chunk=0, W0=None, want_trace=True):
     """The same contract as :func:`pybold_amd.solver.auto_lbda_solve` through ``torch.ops.pybold_hip.auto_lbda_solve``."""
+    return _auto_lbda_solve("auto_lbda_solve", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+                            outer_chunk, W0, want_trace)
+
+
+def auto_lbda_solve_split(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                          outer_chunk=0, W0=None, want_trace=True):
+    """The same contract as :func:`pybold_amd.solver.auto_lbda_solve_split` through
+    ``torch.ops.pybold_hip.auto_lbda_solve_split``."""
+    return _auto_lbda_solve("auto_lbda_solve_split", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+                            outer_chunk, W0, want_trace)
+
+
+def _auto_lbda_solve(op, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0, want_trace):
     import numpy as np
     from . import solver
     ops = load()
@@ -58,7 +71,7 @@ def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6
     W = torch.empty_like(Y) if W0 is None else W0.clone()
     R, G, J = (torch.full((Y.shape[0], int(nb_iter)), float("nan"), dtype=torch.float64, device=dev)
                for _ in range(3)) if want_trace else (None, None, None)
-    alpha, lbda, n_outer, n_inner = ops.auto_lbda_solve(
+    alpha, lbda, n_outer, n_inner = getattr(ops, op)(
         Y, W, W0 is None, taps, float(step), solver._betas_on(dev, int(nb_sub_iter)),
         torch.as_tensor(sigma, dtype=torch.float64).to(dev).contiguous().ravel(), bool(early_stopping), float(tol),
         int(wind), int(nb_iter), int(nb_sub_iter), int(outer_chunk), R, G, J)
