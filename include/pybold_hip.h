@@ -184,9 +184,12 @@ int pb_fista_plan_ex(int N, int K, int P, int stop_mode, int wind, unsigned flag
  *   641 .. 1280  <= 33     (b)                  (b) certificate          (b) in full           fista_mfma4_kernel, four waves per 16 problems
  *   641 .. 1280  34 .. 48  (b)                  (b) certificate          (b) in full           ... with three near tiles
  *   <= 640       <= 32     the noise-driven lambda search (deconv with lbda = None), wind 6, float64 end to end:        auto_lbda_kernel, one voxel per wave (pb_auto_lbda_d)
+ *   <= 640       <= 32     one HRF and one step per problem in device memory, float64 end to end (any stop rule, wind 6):    fista_exact_pp_kernel, one problem per wave (pb_fista_solve_pp_d);
+ *                          the lambda search with one HRF per voxel:                                                        auto_lbda_pp_kernel, one voxel per wave (pb_auto_lbda_pp_d)
  *   641 .. 1280  <= 32     ... the same search, opt-in by name:                                                        auto_lbda_split_kernel, one voxel per workgroup of four waves (pb_auto_lbda_split_d)
  *   longer series, longer HRFs, other windows, a cost trace beside the _loops_deconv rule: (a), one problem per wave up to
- *   2 432 scans, the LDS kernel beyond (and for the window rule beyond 1 280 scans, for 34+ taps beyond 1 280).  Per-problem HRFs (pb_fista_solve_pp, ldt != 0): (a).  A machine-filling batch that lands
+ *   2 432 scans, the LDS kernel beyond (and for the window rule beyond 1 280 scans, for 34+ taps beyond 1 280).  Per-problem HRFs: (a) for a float32 y (pb_fista_solve_pp, ldt != 0); float64 end to end
+ *   (pb_fista_solve_pp_d) beyond 640 scans / 32 taps / wind 6: the LDS kernel.  A machine-filling batch that lands
  *   on (a) although (b) serves neighbouring shapes is 1.5 .. 4x below the matrix-pipe rate; the Python layer says so once.
  *
  * (b) is chosen for plain solves (PB_STOP_NONE, or PB_STOP_WINDOW as a certificate with tol * n_iter < 0.02)
@@ -388,6 +391,14 @@ int pb_hrf_cost(const double* z_dev, int64_t ldz, const float* y_dev, int64_t ld
  */
 int pb_spectral_radius(const double* x0_dev, int N, const double* taps_dev, int K,
                        int nb_iter, double tol, double* out_dev, void* stream);
+/*
+ * The same for V HRFs at once, one workgroup per row: row v starts from x0_dev + v * ldx (float64 [V][ldx], N used),
+ * reads its taps from taps_dev + v * ldt (float64 [V][ldt], K used) and writes out_dev[2v] = ||x_new||,
+ * out_dev[2v + 1] = iterations done (float64 [V][2]).  Every row gets the bits pb_spectral_radius gives it alone.
+ * Errors (nothing is launched): NULL pointers, ldt < K, ldx < N, a row that exceeds LDS.  V = 0 is a no-op.
+ */
+int pb_spectral_radius_pp(const double* x0_dev, int64_t ldx, int V, int N, const double* taps_dev, int64_t ldt, int K,
+                          int nb_iter, double tol, double* out_dev, void* stream);
 
 /*
  * Per-voxel HRFs (blind deconvolution with one HRF dilation per voxel, the loop
@@ -466,6 +477,28 @@ int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
                      int n_iter, double* J_dev, int64_t ldj, int stop_mode, double tol, int wind,
                      int32_t* n_done_dev, unsigned flags, void* stream);
 int pb_fista_which_kernel_d(int N, int K, int with_cost_trace, int stop_mode, int wind);
+/*
+ * pb_fista_solve_d with ONE HRF AND ONE STEP PER PROBLEM, both in device memory: the last step of the reference's per-voxel
+ * workflow (bd on every voxel, then deconv of every voxel with its own HRF: examples/icassp_2019/simulation.py:62-72).
+ *   taps_dev   float64 [P][ldt], K used per row (the slots K .. ldt-1 are never read)      step_dev   float64 [P]
+ * Everything else as pb_fista_solve_d: y float64 [ceil(P / y_rep)][ldy], warm start unless PB_FLAG_COLD_START, cost
+ * trace J float64 [P][ldj] or NULL, all three stop rules, negative lambdas (the reference's prox).
+ *   scans N     taps K    window rule     form                                                     pb_fista_which_kernel_pp_d
+ *   <= 640      <= 32     wind = 6        fista_exact_pp_kernel, one problem per wave              9
+ *                                         (csrc/fista_exact_pp.h: the pass body of fista_exact_kernel, taps in scalar registers)
+ *   otherwise (641+ scans, 33+ taps, other windows), or with PB_FLAG_FORCE_GENERIC:                0
+ *                                         the any-size LDS kernel reading taps_dev + p * ldt
+ *   (-1: the shape exceeds LDS as well, the call fails).  There is no four-wave form with per-problem taps: series
+ *   of 641 .. 1 280 scans run on the LDS kernel.  PB_FLAG_FORCE_FAST: the register form or an error.
+ * Errors (nothing is launched): NULL pointers, ldt < K, a leading dimension too small, an unknown stop_mode, a shape
+ * that exceeds LDS.  P = 0 is a no-op.
+ * pb_fista_which_kernel_pp_d  the code of the form pb_fista_solve_pp_d (no flags) runs for a call shape.  Host-only query.
+ */
+int pb_fista_solve_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
+                        const double* taps_dev, int64_t ldt, int K, const double* step_dev, double lbda,
+                        const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj,
+                        int stop_mode, double tol, int wind, int32_t* n_done_dev, unsigned flags, void* stream);
+int pb_fista_which_kernel_pp_d(int N, int K, int with_cost_trace, int stop_mode, int wind);
 /*
  * OPT-IN EXTRA, never part of a parity run: the recurrence of pb_fista_solve_d with a BACKTRACKED step.  The reference
  * has a constant step only (pybold/bold_signal.py:52-53 / :253-254: 1 / (0.9 rho) or 1 / ||A^T A||_F); this is
@@ -558,6 +591,19 @@ int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw,
                    int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldt,
                    double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev,
                    double* work_dev, int64_t work_len, void* stream);
+/*
+ * pb_auto_lbda_d with one HRF and one step per voxel, both in device memory (auto_lbda_pp_kernel, csrc/fista_exact_pp.h):
+ * taps_dev float64 [V][ldt] (K used per row) in the place of taps_host, step_dev float64 [V] in the place of step; ldtr is
+ * the leading dimension of the traces R, G, J.  The shape limits (pb_auto_lbda_supported), the workspace, the
+ * outer_chunk rule, the order of the validation and the launch protocol are those of pb_auto_lbda_d; the chunking
+ * changes no bit of any output.  Errors in addition: ldt < K.
+ */
+int pb_auto_lbda_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                      const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
+                      const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter,
+                      int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr,
+                      double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev,
+                      double* work_dev, int64_t work_len, void* stream);
 int pb_auto_lbda_split_supported(int N, int K, int wind);
 int pb_auto_lbda_split_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
                          const double* taps_host, int K, double step, const double* betas_dev,

@@ -129,6 +129,26 @@ SIGNATURES = {
         _c_int, _c_dbl, _c_int, _ptr,    # stop_mode, tol, wind, n_done_dev
         ctypes.c_uint, _ptr]),           # flags, stream
     "pb_fista_which_kernel_d": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    # one HRF and one step per problem, float64 end to end
+    "pb_spectral_radius_pp": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_i64, _c_int,      # x0, ldx, V, N, taps_dev, ldt, K
+                                       _c_int, _c_dbl, _ptr, _ptr]),                            # nb_iter, tol, out [V][2], stream
+    "pb_fista_solve_pp_d": (_c_int, [
+        _ptr, _c_i64, _c_int,            # y_dev (float64), ldy, y_rep
+        _ptr, _c_i64, _c_int, _c_int,    # w_dev, ldw, P, N
+        _ptr, _c_i64, _c_int, _ptr,      # taps_dev, ldt, K, step_dev
+        _c_dbl, _ptr,                    # lbda, lbda_dev
+        _ptr, _c_int,                    # betas_dev, n_iter
+        _ptr, _c_i64,                    # J_dev (float64), ldj
+        _c_int, _c_dbl, _c_int, _ptr,    # stop_mode, tol, wind, n_done_dev
+        ctypes.c_uint, _ptr]),           # flags, stream
+    "pb_fista_which_kernel_pp_d": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "pb_auto_lbda_pp_d": (_c_int, [
+        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,     # y_dev, ldy, w_dev, ldw, cold, V, N
+        _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr,                 # taps_dev, ldt, K, step_dev, betas_dev, sigma_dev
+        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,         # early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk
+        _ptr, _ptr, _ptr, _c_i64,                               # R_dev, G_dev, J_dev, ldtr
+        _ptr, _ptr, _ptr, _ptr,                                 # alpha_dev, lbda_dev, n_outer_dev, n_inner_dev
+        _ptr, _c_i64, _ptr]),                                   # work_dev, work_len, stream
     "pb_fista_stats_d": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int, _ptr,
                                   _c_int, _ptr, _ptr, _ptr]),
     "pb_hrf_cost_d": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _ptr,

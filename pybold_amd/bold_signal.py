@@ -20,6 +20,11 @@ Deviations from the reference, all deliberate:
     else of the branch is pinned against the reference with the estimate injected,
     tests/golden/auto_lbda.npz); it computes in float64 end to end, batches included
     (see ``_deconv_auto_lbda``).
+  * ``deconv`` / ``deconv_auto`` with a 2-D ``hrf`` ``(V, K)`` -- one HRF per voxel, the last step of the reference's
+    per-voxel workflow (``bd`` per voxel, then ``deconv`` with the estimated HRF) -- keep the batch ``y`` in float64
+    for that call and compute in float64 end to end, fixed lambda included: voxel ``v`` is solved as the reference
+    solves ``deconv(y[v], t_r, hrf[v], ...)``, the ``v``-th of ``V`` consecutive calls (its start vector of the
+    power iteration is row ``v`` of one ``np.random.randn(V, N)`` draw).
 Beyond the reference's surface: ``deconv_auto`` is that ``lbda=None`` call with the noise level as an argument and the
 whole search resident on the device (``engine``), see there.
 There is no CPU fallback: without the HIP library or a GPU these raise.
@@ -76,6 +81,40 @@ def _host(t, shape):
     return a[0] if shape else a
 
 
+def _shape_of(a):
+    return tuple(a.shape) if torch.is_tensor(a) else tuple(np.shape(a))
+
+
+def _per_voxel_hrf(y, hrf, who):
+    """Whether ``hrf`` holds one HRF per voxel (2-D).  Refuses, before anything touches a device, the shapes that are
+    neither that nor the reference's single 1-D HRF."""
+    hs, ys = _shape_of(hrf), _shape_of(y)
+    if len(hs) < 2:
+        return False
+    if len(hs) > 2 or len(ys) != 2 or hs[0] != ys[0]:
+        raise ValueError("%s: one HRF per voxel takes y of shape (V, N) and hrf of shape (V, K) with the same V; "
+                         "got y of shape %s and hrf of shape %s" % (who, ys, hs))
+    return True
+
+
+def _pv_to_device(y, hrf):
+    """-> (Y float64 CUDA (V, N), taps float64 CUDA (V, K), _Shape): the per-voxel-HRF calls are float64 end to end."""
+    on_device = torch.is_tensor(y) and y.is_cuda
+    dev = solver.device(y.device if on_device else None)
+    Y = (y if torch.is_tensor(y) else torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64))).to(device=dev, dtype=torch.float64)
+    T = (hrf if torch.is_tensor(hrf) else torch.from_numpy(np.ascontiguousarray(hrf, dtype=np.float64))).to(device=dev, dtype=torch.float64)
+    if Y.shape[0] == 0:
+        raise ValueError("deconv: empty voxel batch")
+    return Y, T, _Shape(False, on_device)
+
+
+def _pv_steps(T, n):
+    """``1 / (0.9 rho_v)`` of every voxel's operator (NumPy ``(V,)``): the power iteration of ``spectral_radius_est`` from
+    one ``np.random.randn(V, n)`` draw, row ``v`` the draw of the ``v``-th of ``V`` consecutive 1-D calls."""
+    rho, _ = solver.spectral_radius_batch(np.random.randn(T.shape[0], n), T)
+    return 1.0 / (0.9 * rho)
+
+
 # How the batch path of `deconv` reaches the library: "ctypes" (pybold_amd._lib, the default) or "torch_ops"
 # (torch.ops.pybold_hip: the TORCH_LIBRARY shim over the same C ABI) -- same kernels, bit-identical results
 # (tests/test_torch_ops.py).  Initialised from the environment variable PYBOLD_AMD_DISPATCH.
@@ -100,16 +139,31 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
     Returns ``(x, z, diff_z, J, None, None)`` with ``J`` normalised by ``J[0]``.
     For a 2-D ``y`` every output gains a leading voxel axis and ``J`` is
     ``(V, max iterations run)`` padded with NaN after a voxel's early stop.
+
+    ``hrf`` of shape ``(V, K)`` beside a ``(V, N)`` batch (NumPy, or a float64 CUDA tensor): ONE HRF PER VOXEL, what ``bd``
+    on a batch returns.  Voxel ``v`` is solved as the reference solves ``deconv(y[v], t_r, hrf[v], ...)``, the ``v``-th of
+    ``V`` consecutive calls, in float64 end to end (``lbda`` a scalar or ``(V,)``; ``lbda=None`` likewise, see
+    ``deconv_auto``).  Any other 2-D or higher ``hrf`` is a ``ValueError``.
     """
+    per_voxel = _per_voxel_hrf(y, hrf, "deconv")
     if lbda is None:
         if AUTO_LBDA in ("device", "device_split") and _n_dim(y) == 2:
-            engine = ("device" if solver.auto_lbda_supported(_n_scans(y), np.size(hrf), wind)
-                      else "device_split" if AUTO_LBDA == "device_split" and solver.auto_lbda_split_supported(_n_scans(y), np.size(hrf), wind)
+            n_taps = int(_shape_of(hrf)[-1]) if per_voxel else np.size(hrf)
+            engine = ("device" if solver.auto_lbda_supported(_n_scans(y), n_taps, wind)
+                      else "device_split" if AUTO_LBDA == "device_split" and not per_voxel and solver.auto_lbda_split_supported(_n_scans(y), n_taps, wind)
                       else None)
             if engine:
                 return deconv_auto(y, t_r, hrf, early_stopping=early_stopping, tol=tol, wind=wind, nb_iter=nb_iter,
                                    nb_sub_iter=nb_sub_iter, engine=engine, verbose=verbose)[:6]
         return _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, verbose)
+    if per_voxel:
+        # one HRF per voxel: float64 end to end (pb_fista_solve_pp_d; the torch.ops shim has no such operator, so
+        # DISPATCH == "torch_ops" takes this path too)
+        Y, T, one_d = _pv_to_device(y, hrf)
+        W, J, n_done = solver.fista_solve_pp_d(Y, T, _pv_steps(T, Y.shape[1]), lbda, int(nb_iter), want_J=True,
+                                               stop="window" if early_stopping else None, tol=tol, wind=wind)
+        X, Z = solver.fista_outputs_pp(W, T)
+        return _deconv_results(Y, one_d, X, Z, W, J, n_done, verbose)
     Y, one_d = _y_to_device(y)
     n = Y.shape[1]
     if Y.shape[0] == 0:
@@ -130,6 +184,11 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
             Y, hrf, lbda, step, int(nb_iter), want_J=True,
             stop="window" if early_stopping else None, tol=tol, wind=wind)
         X, Z = solver.fista_outputs(W, hrf)
+    return _deconv_results(Y, one_d, X, Z, W, J, n_done, verbose)
+
+
+def _deconv_results(Y, one_d, X, Z, W, J, n_done, verbose):
+    """The return tuple of the fixed-lambda ``deconv``: ``J`` normalised by ``J[0]`` and NaN-padded after a voxel's stop."""
     n_max = max(int(n_done.max()), 1)
     if one_d.on_device:
         # CUDA in -> CUDA out: the cost trace is normalised on the device and stays there
@@ -177,6 +236,8 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
             "device_split": the device-resident solve with one voxel per workgroup of four waves
             (``solver.auto_lbda_solve_split``: series of 641 .. 1 280 scans, HRFs of up to 32 taps, ``wind == 6`` --
             ``ValueError`` otherwise; ``"device"`` and ``"auto"`` do not reach it)
+    hrf     1-D, or ``(V, K)`` beside a ``(V, N)`` batch: one HRF per voxel (``solver.auto_lbda_solve_pp`` on the device engine,
+            the host loop on ``solver.fista_solve_pp_d``; ``"device_split"`` takes one HRF for all voxels: ``ValueError``)
     outer_chunk  device engine: outer iterations per kernel launch (``None``: the library's choice); no effect on
             the result
 
@@ -186,8 +247,14 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     voxel), ``n_outer``, ``n_inner`` (outer / summed inner iterations per voxel), ``sigma`` and ``engine``."""
     if engine not in ("auto", "device", "host", "device_split"):
         raise ValueError("deconv_auto: engine must be 'auto', 'device', 'host' or 'device_split', got %r" % (engine,))
-    n, n_taps = _n_scans(y), int(np.size(hrf))
+    per_voxel = _per_voxel_hrf(y, hrf, "deconv_auto")
+    n, n_taps = _n_scans(y), (int(_shape_of(hrf)[-1]) if per_voxel else int(np.size(hrf)))
     if engine == "device_split":
+        if per_voxel:
+            raise ValueError("deconv_auto(engine='device_split'): the four-wave device-resident lambda search takes one HRF "
+                             "for all voxels; with one HRF per voxel (hrf of shape %s) the device-resident search carries "
+                             "series of up to 640 scans (engine='device'), longer ones run the host loop (engine='host')"
+                             % (_shape_of(hrf),))
         if not solver.auto_lbda_split_supported(n, n_taps, wind):
             raise ValueError("deconv_auto(engine='device_split'): the four-wave device-resident lambda search carries series of "
                              "641..1280 scans, HRFs of up to 32 taps and wind = 6; this call has %d scans, %d taps, wind = %d"
@@ -215,6 +282,13 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
         info["engine"] = "host"
         return out + (info,)
 
+    if per_voxel:
+        Y, T, one_d = _pv_to_device(y, hrf)
+        V = Y.shape[0]
+        W, res = solver.auto_lbda_solve_pp(Y, T, _pv_steps(T, n), sigma, early_stopping=early_stopping, tol=tol, wind=wind,
+                                           nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
+        X, Z = solver.fista_outputs_pp(W, T)
+        return _deconv_auto_results(one_d, V, X, Z, W, res, sigma, engine, verbose)
     one_d = _Shape(_n_dim(y) == 1, on_device)
     if torch.is_tensor(y):
         Y = torch.atleast_2d(y).to(device=solver.device(y.device if on_device else None), dtype=torch.float64)
@@ -230,6 +304,11 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     W, res = solve(Y, hrf, step, sigma, early_stopping=early_stopping, tol=tol, wind=wind,
                    nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
     X, Z = solver.fista_outputs(W, hrf)
+    return _deconv_auto_results(one_d, V, X, Z, W, res, sigma, engine, verbose)
+
+
+def _deconv_auto_results(one_d, V, X, Z, W, res, sigma, engine, verbose):
+    """The return tuple of ``deconv_auto`` from what a device-resident search hands back."""
     n_outer = res["n_outer"].cpu().numpy()
     n_max = int(n_outer.max())
     J, R, G = (res[k][:, :n_max].t().cpu().numpy() for k in ("J", "R", "G"))       # (n_outer, V), NaN after a row's stop
@@ -264,7 +343,11 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
         sigma = np.atleast_1d(mad_daub_noise_est(y_host))
     else:                                            # the caller's noise level (deconv_auto): scalar or one per voxel
         sigma = np.atleast_1d(sigma.detach().cpu().numpy() if torch.is_tensor(sigma) else np.asarray(sigma, dtype=np.float64))
-    Y, one_d = _y_to_device(y)
+    per_voxel = _per_voxel_hrf(y, hrf, "deconv")
+    if per_voxel:
+        Y, T, one_d = _pv_to_device(y, hrf)
+    else:
+        Y, one_d = _y_to_device(y)
     if Y.dtype != torch.float64:
         if Y.shape[0] >= 1024:
             solver.warn_once("auto-lambda-f64",
@@ -287,11 +370,32 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
             Y = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(y_host), dtype=np.float64)).to(Y.device)
     V, n = Y.shape
     dev = Y.device
-    hrf = np.asarray(hrf, dtype=np.float64)
-    H = ConvAndLinear(DiscretInteg(), hrf, dim_in=n, dim_out=n)
-    grad_lipschitz_cst = 0.9 * spectral_radius_est(H, (n,))
-    step = 1.0 / grad_lipschitz_cst
     stop = "window" if early_stopping else None
+    if per_voxel:                                  # one HRF and one step per voxel: the same loop on the per-voxel entry points
+        steps = _pv_steps(T, n)
+
+        def solve(lbda, W):
+            return solver.fista_solve_pp_d(Y, T, steps, lbda, int(nb_sub_iter), W0=W, stop=stop, tol=tol, wind=wind)
+
+        def stats(W):
+            return solver.fista_stats_pp(W, Y, T)
+
+        def outputs(W):
+            return solver.fista_outputs_pp(W, T)
+    else:
+        hrf = np.asarray(hrf, dtype=np.float64)
+        H = ConvAndLinear(DiscretInteg(), hrf, dim_in=n, dim_out=n)
+        grad_lipschitz_cst = 0.9 * spectral_radius_est(H, (n,))
+        step = 1.0 / grad_lipschitz_cst
+
+        def solve(lbda, W):
+            return solver.fista_solve(Y, hrf, lbda, step, int(nb_sub_iter), W0=W, stop=stop, tol=tol, wind=wind)
+
+        def stats(W):
+            return solver.fista_stats(W, Y, hrf)
+
+        def outputs(W):
+            return solver.fista_outputs(W, hrf)
 
     alpha = np.ones(V)
     lbda = 1.0 / (2.0 * alpha)
@@ -303,8 +407,7 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
     n_inner = torch.zeros((V,), dtype=torch.int64, device=dev) if info is not None else None
     n_outer = np.zeros(V, dtype=np.int32)
     for i in range(nb_iter):
-        W_new, _, n_done = solver.fista_solve(Y, hrf, lbda, step, int(nb_sub_iter), W0=W, stop=stop,
-                                              tol=tol, wind=wind)
+        W_new, _, n_done = solve(lbda, W)
         n_outer += active
         if n_inner is not None:                      # (inner iterations of the voxels still searching: deconv_auto's info)
             n_inner += torch.where(torch.from_numpy(active).to(dev), n_done.long(), torch.zeros_like(n_inner))
@@ -312,7 +415,7 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
             W = W_new
         else:
             W = torch.where(torch.from_numpy(active).to(dev)[:, None], W_new, W)
-        r2, l1 = solver.fista_stats(W, Y, hrf)
+        r2, l1 = stats(W)
         r, g = r2.cpu().numpy(), l1.cpu().numpy()
         grad = r - n * sigma ** 2
         alpha = np.where(active, alpha + mu * grad, alpha)
@@ -335,9 +438,8 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
             active &= ~(diff < tol)
             if not active.any():
                 break
-    W, _, n_done = solver.fista_solve(Y, hrf, lbda, step, int(nb_sub_iter), W0=W, stop=stop, tol=tol,
-                                      wind=wind)
-    X, Z = solver.fista_outputs(W, hrf)
+    W, _, n_done = solve(lbda, W)
+    X, Z = outputs(W)
     if info is not None:
         info.update(alpha=alpha.copy(), lbda=lbda.copy(), n_outer=n_outer, n_inner=(n_inner + n_done.long()).cpu().numpy(),
                     sigma=np.broadcast_to(sigma, (V,)).copy())

@@ -18,6 +18,7 @@
 #include "fista_exact.h"
 #include "fista_exact_split.h"
 #include "fista_auto.h"
+#include "fista_exact_pp.h"
 #include "blind.h"
 #include "fista_mfma.h"
 #include "fista_mfma2.h"
@@ -882,6 +883,49 @@ int pb_fista_which_kernel_d(int N, int K, int with_cost_trace, int stop_mode, in
   return gen_lds_doubles(N, K, stop_mode, wind) <= LDS_DOUBLES_MAX ? 0 : -1;
 }
 
+// pb_fista_solve_d with one HRF and one step per problem, both in device memory: the register form with one problem
+// per wave (fista_exact_pp.h) where the shape has an entry, else the LDS kernel with FistaArgs::taps_pp; no four-wave form
+int pb_fista_solve_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
+                        const double* taps_dev, int64_t ldt, int K, const double* step_dev, double lbda,
+                        const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj,
+                        int stop_mode, double tol, int wind, int32_t* n_done_dev, unsigned flags, void* stream) {
+  if (P < 0 || N < 1 || K < 1 || n_iter < 0 || y_rep < 1)
+    return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: bad size (P=%d N=%d K=%d n_iter=%d y_rep=%d)", P, N, K, n_iter, y_rep);
+  if (ldt < K) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: ldt < K");
+  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: leading dimension too small (< N)");
+  if (J_dev && ldj < n_iter) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: leading dimension too small (ldj < n_iter)");
+  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW)
+    return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: unknown stop_mode %d", stop_mode);
+  if (stop_mode == PB_STOP_WINDOW && wind < 2) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: wind must be >= 2");
+  const ExactPPEntry* ee = (flags & PB_FLAG_FORCE_GENERIC) ? nullptr : pick_exact_pp(N, K, stop_mode, wind);
+  if (!ee && (flags & PB_FLAG_FORCE_FAST))
+    return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: no register-resident float64 kernel with one problem per wave for N=%d K=%d", N, K);
+  if (!ee && gen_lds_doubles(N, K, stop_mode, wind) > LDS_DOUBLES_MAX)
+    return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: N=%d K=%d wind=%d exceeds LDS", N, K, wind);
+  if (P == 0) return PB_OK;
+  if (!y_dev || !w_dev || !taps_dev || !step_dev || (n_iter > 0 && !betas_dev))
+    return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: NULL pointer");
+  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: more than 2^25 problems per launch");
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, stop_mode, tol,
+                               n_done_dev, flags);
+  a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj; a.wind = wind;
+  a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = 0;
+  if (ee) {
+    if (ee->fn(a, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
+      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: launch rejected");
+    return check_launch("fista_exact_pp_kernel");
+  }
+  launch_generic(a, taps_dev, K, wind, J_dev != nullptr, true, P, (hipStream_t)stream);
+  return check_launch("fista_generic_kernel(f64, pp)");
+}
+
+int pb_fista_which_kernel_pp_d(int N, int K, int with_cost_trace, int stop_mode, int wind) {
+  (void)with_cost_trace;                                // (every float64 form writes the cost trace)
+  if (N < 1 || K < 1) return 0;
+  if (pick_exact_pp(N, K, stop_mode, wind)) return 9;
+  return gen_lds_doubles(N, K, stop_mode, wind) <= LDS_DOUBLES_MAX ? 0 : -1;
+}
+
 int pb_auto_lbda_supported(int N, int K, int wind) { return (wind == pb::AUTO_WIND && pick_auto(N, K)) ? 1 : 0; }
 
 int64_t pb_auto_lbda_work_len(int V) { return (int64_t)pb::AUTO_STATE * (V > 0 ? V : 0); }
@@ -940,6 +984,52 @@ int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw,
   return auto_lbda_impl("pb_auto_lbda_d", false, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev, sigma_dev,
                         early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt, alpha_dev, lbda_dev,
                         n_outer_dev, n_inner_dev, work_dev, work_len, stream);
+}
+
+// pb_auto_lbda_d with one HRF (taps_dev [V][ldt]) and one step (step_dev [V]) per voxel: its validation in its order (the
+// taps' leading dimension beside the others, the step's sign is the caller's), its chunk, its launch protocol
+int pb_auto_lbda_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                      const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
+                      const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
+                      int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
+                      double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
+                      void* stream) {
+  const char* name = "pb_auto_lbda_pp_d";
+  if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "%s: bad size (V=%d N=%d K=%d)", name, V, N, K);
+  if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "%s: wind=%d (the device-resident search carries wind = 6)", name, wind);
+  if (N > 640) return fail(PB_ERR_INVALID, "%s: N=%d exceeds 640 scans", name, N);
+  if (K > 32) return fail(PB_ERR_INVALID, "%s: K=%d exceeds 32 taps", name, K);
+  const ExactPPEntry* ae = pick_auto(N, K) ? pick_exact_pp(N, K, PB_STOP_WINDOW, wind) : nullptr;
+  if (!ae || !ae->fn_auto) return fail(PB_ERR_INVALID, "%s: no specialisation for N=%d K=%d", name, N, K);
+  if (nb_iter < 1 || nb_sub_iter < 0 || outer_chunk < 0)
+    return fail(PB_ERR_INVALID, "%s: nb_iter >= 1, nb_sub_iter >= 0 and outer_chunk >= 0 are required (%d, %d, %d)", name,
+                nb_iter, nb_sub_iter, outer_chunk);
+  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "%s: leading dimension < N", name);
+  if (ldt < K) return fail(PB_ERR_INVALID, "%s: ldt < K", name);
+  if ((R_dev || G_dev || J_dev) && ldtr < nb_iter) return fail(PB_ERR_INVALID, "%s: leading dimension of the traces < nb_iter", name);
+  if (work_len < pb_auto_lbda_work_len(V))
+    return fail(PB_ERR_INVALID, "%s: workspace of %lld float64, %lld needed", name, (long long)work_len,
+                (long long)pb_auto_lbda_work_len(V));
+  if (V == 0) return PB_OK;
+  if (!y_dev || !w_dev || !taps_dev || !step_dev || !sigma_dev || !work_dev || (nb_sub_iter > 0 && !betas_dev))
+    return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
+  if (V > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 voxels per call", name);
+  pb::AutoArgsPP a;
+  a.y = y_dev; a.ldy = ldy; a.w = w_dev; a.ldw = ldw; a.V = V; a.N = N;
+  a.cold = cold ? 1 : 0; a.nb_sub_iter = nb_sub_iter; a.step = 0.0; a.tol = tol;
+  a.betas = betas_dev; a.sigma = sigma_dev; a.R = R_dev; a.G = G_dev; a.J = J_dev; a.ldt = ldtr;
+  a.alpha_out = alpha_dev; a.lbda_out = lbda_dev; a.n_outer = n_outer_dev; a.n_inner = n_inner_dev; a.work = work_dev;
+  a.taps_pp = taps_dev; a.ld_taps = ldt; a.step_vec = step_dev; a.K = K;
+  const int chunk = outer_chunk > 0 ? outer_chunk : auto_outer_chunk(V, nb_sub_iter);
+  for (int i0 = 0; i0 < nb_iter; i0 += chunk) {        // outer iterations [i0, i1) of the voxels still searching
+    a.init = i0 == 0; a.i0 = i0; a.i1 = (nb_iter - i0 < chunk) ? nb_iter : i0 + chunk; a.final_solve = 0;
+    if (ae->fn_auto(a, early_stopping != 0, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
+    const int rc = check_launch("auto_lbda_pp_kernel");
+    if (rc != PB_OK) return rc;
+  }
+  a.init = 0; a.i0 = a.i1 = nb_iter; a.final_solve = 1;   // the last inner solve of every voxel, then the outputs
+  if (ae->fn_auto(a, early_stopping != 0, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
+  return check_launch("auto_lbda_pp_kernel(final solve)");
 }
 
 int pb_auto_lbda_split_supported(int N, int K, int wind) { return (wind == pb::AUTO_WIND && pick_auto_split(N, K)) ? 1 : 0; }
@@ -1030,8 +1120,24 @@ int pb_spectral_radius(const double* x0_dev, int N, const double* taps_dev, int 
     return fail(PB_ERR_INVALID, "pb_spectral_radius: N=%d K=%d exceeds LDS", N, K);
   const size_t lds = (size_t)(3 * N + K + 8) * sizeof(double);
   hipLaunchKernelGGL(pb::power_iter_kernel, dim3(1), dim3(pb::GEN_THREADS), lds, (hipStream_t)stream,
-                     x0_dev, N, taps_dev, K, nb_iter, tol, out_dev);
+                     x0_dev, (int64_t)0, N, taps_dev, (int64_t)0, K, nb_iter, tol, out_dev);
   return check_launch("power_iter_kernel");
+}
+
+int pb_spectral_radius_pp(const double* x0_dev, int64_t ldx, int V, int N, const double* taps_dev, int64_t ldt, int K,
+                          int nb_iter, double tol, double* out_dev, void* stream) {
+  if (V < 0 || N < 1 || K < 1 || nb_iter < 0)
+    return fail(PB_ERR_INVALID, "pb_spectral_radius_pp: bad size (V=%d N=%d K=%d nb_iter=%d)", V, N, K, nb_iter);
+  if (ldt < K) return fail(PB_ERR_INVALID, "pb_spectral_radius_pp: ldt < K");
+  if (ldx < N) return fail(PB_ERR_INVALID, "pb_spectral_radius_pp: leading dimension too small (ldx < N)");
+  if (3 * (int64_t)N + K + 8 > LDS_DOUBLES_MAX)
+    return fail(PB_ERR_INVALID, "pb_spectral_radius_pp: N=%d K=%d exceeds LDS", N, K);
+  if (V == 0) return PB_OK;
+  if (!x0_dev || !taps_dev || !out_dev) return fail(PB_ERR_INVALID, "pb_spectral_radius_pp: NULL pointer");
+  const size_t lds = (size_t)(3 * N + K + 8) * sizeof(double);
+  hipLaunchKernelGGL(pb::power_iter_kernel, dim3(V), dim3(pb::GEN_THREADS), lds, (hipStream_t)stream,
+                     x0_dev, ldx, N, taps_dev, ldt, K, nb_iter, tol, out_dev);
+  return check_launch("power_iter_kernel(pp)");
 }
 
 int pb_integ_op(const double* x, int64_t ldx, double* out, int64_t ldo, int V, int N, void* st) {

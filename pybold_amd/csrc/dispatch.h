@@ -12,6 +12,7 @@
 #include "fista_exact_split.h"
 #include "fista_auto.h"
 #include "fista_auto_split.h"
+#include "fista_exact_pp.h"
 #include "fista_mfma.h"
 #include "fista_mfma2.h"
 #include "fista_mfma4.h"
@@ -202,6 +203,34 @@ const ExactEntry* pick_exact_any(int N, int K, int stop_mode, int wind, bool* sp
 const ExactEntry* pick_auto(int N, int K) { return (N >= 1 && K >= 1) ? pick_exact(N, K) : nullptr; }
 // ... with one voxel over the four waves of a workgroup (fista_auto_split.h): the shapes of the four-wave float64 form
 const ExactEntry* pick_auto_split(int N, int K) { return (N >= 1 && K >= 1) ? pick_exact_split(N, K) : nullptr; }
+
+// one HRF and one step per problem, in device memory (fista_exact_pp.h): the (S, KT) pairs of the all-float64 form
+typedef int (*exact_pp_launch_fn)(const pb::FistaArgs&, bool with_j, int stop, hipStream_t);
+typedef int (*auto_pp_launch_fn)(const pb::AutoArgsPP&, bool early_stopping, hipStream_t);
+struct ExactPPEntry {
+  int S, KT;
+  exact_pp_launch_fn fn;
+  auto_pp_launch_fn fn_auto;
+};
+}  // namespace
+namespace pb {
+#define PB_EXACT(S, KT)                                                                  \
+  extern template int launch_exact_pp<S, KT>(const FistaArgs&, bool, int, hipStream_t); \
+  extern template int launch_auto_pp<S, KT>(const AutoArgsPP&, bool, hipStream_t);
+#include "exact_table.inc"
+#undef PB_EXACT
+}  // namespace pb
+namespace {
+#define PB_EXACT(S, KT) {S, KT, &pb::launch_exact_pp<S, KT>, &pb::launch_auto_pp<S, KT>},
+const ExactPPEntry kExactPP[] = {
+#include "exact_table.inc"
+};
+#undef PB_EXACT
+// the window rule of the register form is wind = 6; no four-wave form behind it
+const ExactPPEntry* pick_exact_pp(int N, int K, int stop_mode, int wind) {
+  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
+  return pick_cheapest(kExactPP, N, K, 64);
+}
 
 template <int S, int KT>
 constexpr launch_fn pair_or_null() {

@@ -333,11 +333,16 @@ __global__ __launch_bounds__(GEN_THREADS) void hrf_cost_kernel(const double* z, 
 // Power iteration of pybold/utils.py:94-109 on H^T H, H = toeplitz(taps) . cumsum, entirely in
 // one workgroup: x <- H^T H x / ||x||, stop when | ||x_new|| - ||x_old|| | < tol or after nb_iter
 // steps; out[0] = ||x_new||, out[1] = steps done.  LDS: x[N] a[N] b[N] k[K] red[8].
-__global__ __launch_bounds__(GEN_THREADS) void power_iter_kernel(const double* x0, int N,
-                                                                 const double* taps, int K,
+// One workgroup per row: row v starts from x0 + v * ldx, reads its taps from taps + v * ldt and writes out[2v], out[2v+1]
+// (pb_spectral_radius: one row; pb_spectral_radius_pp: one HRF per row).
+__global__ __launch_bounds__(GEN_THREADS) void power_iter_kernel(const double* x0, int64_t ldx, int N,
+                                                                 const double* taps, int64_t ldt, int K,
                                                                  int nb_iter, double tol,
                                                                  double* out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  x0 += (int64_t)blockIdx.x * ldx;
+  taps += (int64_t)blockIdx.x * ldt;
+  out += 2 * (int64_t)blockIdx.x;
   double* x = reinterpret_cast<double*>(smem);
   double* a = x + N;
   double* b = a + N;

@@ -201,7 +201,8 @@ KERNEL_NAMES = {0: "fista_generic_kernel (LDS)", 1: "fista_fast_kernel (register
                    "the four SIMDs of a compute unit --, both operators on the matrix pipe)",
                 7: "fista_exact_kernel (register-resident, float64 end to end, one problem per wave)",
                 8: "fista_exact_split_kernel (register-resident, float64 end to end, one problem per workgroup of four "
-                   "waves)"}
+                   "waves)",
+                9: "fista_exact_pp_kernel (register-resident, float64 end to end, one problem per wave, one HRF per problem)"}
 
 
 def which_kernel(n_scans, n_taps, n_problems, want_J=False, stop=None, wind=6):
@@ -214,6 +215,15 @@ def which_kernel_f64(n_scans, n_taps, want_J=False, stop=None, wind=6):
     """Name of the kernel :func:`fista_solve` dispatches to for a float64 ``Y`` of this shape (``pb_fista_solve_d``: the
     1-D calls of the API, ``deconv(lbda=None)``); raises ``ValueError`` where not even the LDS kernel holds the shape."""
     form = _lib.load().pb_fista_which_kernel_d(int(n_scans), int(n_taps), int(bool(want_J)), _STOP[stop], int(wind))
+    if form < 0:
+        raise ValueError("no float64 kernel for %d scans, %d taps, wind=%d: the series exceeds LDS" % (n_scans, n_taps, wind))
+    return KERNEL_NAMES[form]
+
+
+def which_kernel_pp_f64(n_scans, n_taps, want_J=False, stop=None, wind=6):
+    """Name of the kernel :func:`fista_solve_pp_d` dispatches to for this shape (``pb_fista_which_kernel_pp_d``); raises
+    ``ValueError`` where not even the LDS kernel holds the shape."""
+    form = _lib.load().pb_fista_which_kernel_pp_d(int(n_scans), int(n_taps), int(bool(want_J)), _STOP[stop], int(wind))
     if form < 0:
         raise ValueError("no float64 kernel for %d scans, %d taps, wind=%d: the series exceeds LDS" % (n_scans, n_taps, wind))
     return KERNEL_NAMES[form]
@@ -590,6 +600,26 @@ def spectral_radius(x0, hrf, nb_iter=30, tol=1.0e-6):
     return float(rho), int(n_it)
 
 
+def spectral_radius_batch(X0, taps, nb_iter=30, tol=1.0e-6):
+    """:func:`spectral_radius` for one HRF per row in one launch (``pb_spectral_radius_pp``): ``X0`` float64 ``(V, N)``
+    start vectors, ``taps`` float64 ``(V, K)`` (arrays or CUDA tensors; padded row strides are kept).  Row ``v`` gets
+    the bits ``spectral_radius(X0[v], taps[v])`` gives.  Returns ``(rho (V,) float64, n_it (V,) int)`` as NumPy arrays."""
+    lib = _lib.load()
+    dev = device(X0.device if torch.is_tensor(X0) and X0.is_cuda else None)
+    X = _rows(torch.as_tensor(X0, dtype=torch.float64).to(dev), torch.float64, "X0")
+    T = _rows(torch.as_tensor(taps, dtype=torch.float64).to(dev), torch.float64, "taps")
+    V, N = X.shape
+    if T.shape[0] != V:
+        raise ValueError("taps must have one row per row of X0: %s against %s" % (tuple(T.shape), tuple(X.shape)))
+    out = torch.empty((V, 2), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.pb_spectral_radius_pp(X.data_ptr(), _ld(X), V, N, T.data_ptr(), _ld(T), T.shape[1], int(nb_iter),
+                                       float(tol), out.data_ptr(), _stream_ptr(dev))
+    _lib.check(rc, "pb_spectral_radius_pp")
+    o = out.cpu().numpy()
+    return o[:, 0].copy(), o[:, 1].astype(np.int64)
+
+
 def _apply(fn_name, X, n_out, taps=None, n_in=None):
     lib = _lib.load()
     X = _rows(X, torch.float64, "x")
@@ -738,6 +768,64 @@ def fista_solve_pp(Y, taps, steps, lbda, n_iter, W0=None, stop=None, tol=0.0, fo
     return W, n_done
 
 
+def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=None, tol=0.0, wind=6, force=None):
+    """:func:`fista_solve` on a float64 ``Y`` with one HRF and one step per problem (``pb_fista_solve_pp_d``): float64 end
+    to end, the reference's arithmetic, every stop rule, the cost trace, negative lambdas.
+
+    Y      float64 CUDA ``(V, N)``;  taps  float64 CUDA ``(V, K)``;  steps  float64 ``(V,)``
+    lbda   scalar or ``(V,)``;  W0  optional float64 CUDA ``(V, N)`` warm start (not modified)
+    force  None | "fast" (the register form, one problem per wave: ``N <= 640``, ``K <= 32``, window rule at
+           ``wind == 6``) | "generic" (the LDS kernel); :func:`which_kernel_pp_f64` names the dispatch's choice
+    Returns ``(W float64 (V, N), J float64 (V, n_iter) or None, n_done int32 (V,))``."""
+    lib = _lib.load()
+    Y = _rows(Y, torch.float64, "Y")
+    dev = Y.device
+    V, N = Y.shape
+    taps = _rows(taps, torch.float64, "taps")
+    if taps.shape[0] != V:
+        raise ValueError("taps must have one row per voxel: %s against %s" % (tuple(taps.shape), tuple(Y.shape)))
+    steps = torch.as_tensor(steps, dtype=torch.float64).to(dev).contiguous().ravel()
+    if steps.numel() != V:
+        raise ValueError("steps must have one entry per voxel (%d)" % V)
+    if force not in (None, "generic", "fast"):
+        raise ValueError("float64 y: force must be None, 'fast' (register-resident float64 kernel, one problem per "
+                         "wave) or 'generic' (LDS kernel)")
+    cold = 0
+    if W0 is None:
+        W = torch.empty((V, N), dtype=torch.float64, device=dev)
+        cold = PB_FLAG_COLD_START
+    else:
+        W = _rows(W0, torch.float64, "W0").clone()
+        if W.shape != (V, N):
+            raise ValueError("W0 must be %s, got %s" % ((V, N), tuple(W.shape)))
+    lbda_dev, lbda_scalar = None, 0.0
+    if np.ndim(lbda) == 0 and not torch.is_tensor(lbda):
+        lbda_scalar = float(lbda)
+    else:
+        lbda_dev = torch.as_tensor(lbda, dtype=torch.float64).to(dev).contiguous().ravel()
+        if lbda_dev.numel() != V:
+            raise ValueError("per-problem lbda must have %d entries" % V)
+    betas = _betas_on(dev, n_iter)
+    J = torch.full((V, max(n_iter, 1)), float("nan"), dtype=torch.float64, device=dev) if want_J else None
+    n_done = torch.empty((V,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.pb_fista_solve_pp_d(
+            Y.data_ptr(), _ld(Y), 1, W.data_ptr(), _ld(W), V, N, taps.data_ptr(), _ld(taps), taps.shape[1],
+            steps.data_ptr(), lbda_scalar, lbda_dev.data_ptr() if lbda_dev is not None else None,
+            betas.data_ptr(), int(n_iter), J.data_ptr() if J is not None else None, _ld(J) if J is not None else 0,
+            _STOP[stop], float(tol), int(wind), n_done.data_ptr(), _FORCE[force] | cold, _stream_ptr(dev))
+    _lib.check(rc, "pb_fista_solve_pp_d")
+    return W, J, n_done
+
+
+def fista_stats_pp(W, Y, taps):
+    """:func:`fista_stats` with one HRF per row (float64 ``Y``; ``taps`` float64 CUDA ``(V, K)``): the residual comes
+    from :func:`fista_outputs_pp`, the two sums from ``torch`` (the host engine of the per-voxel lambda search; the
+    device engine forms them in its kernel)."""
+    X, _ = fista_outputs_pp(W, taps)
+    return ((X - Y) ** 2).sum(dim=1), W.abs().sum(dim=1)
+
+
 def fista_outputs_pp(W, taps):
     """``z = cumsum(w)``, ``x = taps_v * z`` with one HRF per row."""
     lib = _lib.load()
@@ -879,12 +967,28 @@ def auto_lbda_solve_split(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, 
                             outer_chunk, W0, want_trace)
 
 
+def auto_lbda_solve_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                       outer_chunk=0, W0=None, want_trace=True):
+    """:func:`auto_lbda_solve` with one HRF and one step per voxel (``pb_auto_lbda_pp_d``): ``taps`` float64 CUDA
+    ``(V, K)``, ``steps`` float64 ``(V,)``; the same limits (:func:`auto_lbda_supported`), the same return value."""
+    Y = _rows(Y, torch.float64, "Y")
+    taps = _rows(taps, torch.float64, "taps")
+    if taps.shape[0] != Y.shape[0]:
+        raise ValueError("taps must have one row per voxel: %s against %s" % (tuple(taps.shape), tuple(Y.shape)))
+    steps = torch.as_tensor(steps, dtype=torch.float64).to(Y.device).contiguous().ravel()
+    if steps.numel() != Y.shape[0]:
+        raise ValueError("steps must have one entry per voxel (%d)" % Y.shape[0])
+    return _auto_lbda_solve("pb_auto_lbda_pp_d", Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+                            outer_chunk, W0, want_trace)
+
+
 def _auto_lbda_solve(entry, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0, want_trace):
     lib = _lib.load()
     Y = _rows(Y, torch.float64, "Y")
     dev = Y.device
     V, N = Y.shape
-    taps = _as_taps(hrf)
+    pp = entry == "pb_auto_lbda_pp_d"              # hrf: CUDA (V, K), step: CUDA (V,)
+    taps = None if pp else _as_taps(hrf)
     nb_iter, nb_sub_iter = int(nb_iter), int(nb_sub_iter)
     if W0 is None:
         W = torch.empty((V, N), dtype=torch.float64, device=dev)
@@ -912,7 +1016,8 @@ def _auto_lbda_solve(entry, Y, hrf, step, sigma, early_stopping, tol, wind, nb_i
     with torch.cuda.device(dev):
         rc = getattr(lib, entry)(
             Y.data_ptr(), _ld(Y), W.data_ptr(), _ld(W), int(W0 is None), V, N,
-            taps.ctypes.data, taps.size, float(step), betas.data_ptr(), sig.data_ptr(),
+            *((hrf.data_ptr(), _ld(hrf), hrf.shape[1], step.data_ptr()) if pp else (taps.ctypes.data, taps.size, float(step))),
+            betas.data_ptr(), sig.data_ptr(),
             int(bool(early_stopping)), float(tol), int(wind), nb_iter, nb_sub_iter, int(outer_chunk),
             trace[0].data_ptr() if want_trace else None, trace[1].data_ptr() if want_trace else None,
             trace[2].data_ptr() if want_trace else None, _ld(trace[0]) if want_trace else 0,
