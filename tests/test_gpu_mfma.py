@@ -85,7 +85,8 @@ def test_series_lengths_and_tap_counts(solver, n, k):
     assert rel_rows(W3.cpu().numpy(), Wo) < EPS
 
 
-@pytest.mark.parametrize("n,k", [(300, 34), (300, 40), (300, 48), (225, 41), (160, 34), (129, 48), (304, 47)])
+@pytest.mark.parametrize("n,k", [(300, 34), (300, 40), (300, 48), (225, 41), (160, 34), (129, 48), (304, 47),
+                                 (200, 40), (260, 36)])      # (seven and nine blocks: profiles/table_entries.txt)
 def test_three_near_tiles_for_hrfs_of_34_to_48_taps(solver, n, k):
     """HRFs of 34..48 taps (short TR): the matrix-pipe form with a third near tile (lags up to 95, far
     field from lag 65 on); plain solves and the cost trace (the window-rule certificate of such
@@ -274,3 +275,65 @@ def test_window_rule_certificate_on_the_matrix_pipe(solver, golden):
     _, _, ndc = solver.fista_solve(Y[:2048], hrf, 1.0, 1.0 / lip, 1000, want_J=True, stop="window", tol=1e-6, wind=6,
                                    force="mfmacertonly")
     assert int((ndc < 0).sum()) == 0                     # the reference default: nothing handed back
+
+
+@pytest.mark.parametrize("n,k", [(150, 27), (180, 30), (210, 27), (240, 30), (270, 27)])
+def test_rule_certificate_and_device_taps_at_every_block_count(solver, n, k):
+    """`fista_mfma_kernel<NB, ...>` at 5 .. 9 blocks (ten: the 300-scan tests above and in tests/test_gpu_round4.py) in the
+    three instances no series length of the other tests runs: the window rule as a certificate (stop iterations and iterates
+    of the exact rule, the flagged rows re-solved; what the certificate alone clears ran every iteration), the _loops_deconv
+    rule inside the kernel (+-1 on 3 % at most, as tests/test_gpu_round5.py allows the split forms), the shared-HRF z-step
+    with the taps in device memory -- against the float64 oracles."""
+    rng = np.random.RandomState(n * 3 + k)
+    hrf = orc.spm_hrf(1.0, 1.0, float(k), False)[0][:k]
+    lip = orc.gram_lipschitz(hrf, n)
+    assert solver.launch_plan(n, k, 100000, stop="loops")[1].startswith("fista_mfma_kernel")
+    assert "matrix pipe" in solver.which_kernel(n, k, 40000, want_J=True, stop="window", wind=6)
+    # the certificate
+    Yv = rng.randn(24, n)
+    Y32 = Yv.astype(np.float32).astype(np.float64)
+    Yd = dev32(Yv)
+    tol = 0.01
+    n_fire = np.array([orc.deconv_fixed_lbda(Y32[v], hrf, 0.7, nb_iter=400, tol=tol, lipschitz=lip, dense=False)[4] for v in range(24)])
+    n_iter = int(np.median(n_fire))
+    out = [orc.deconv_fixed_lbda(Y32[v], hrf, 0.7, nb_iter=n_iter, tol=tol, lipschitz=lip, dense=False) for v in range(24)]
+    Wr, nr = np.stack([o[2] for o in out]), np.array([o[4] for o in out])
+    assert 0 < (nr < n_iter).sum() < 24
+    Ww, Jw, ndw = solver.fista_solve(Yd, hrf, 0.7, 1.0 / lip, n_iter, want_J=True, stop="window", tol=tol, wind=6, force="mfmacert")
+    assert (ndw.cpu().numpy() == nr).all(), (ndw.cpu().numpy(), nr)
+    assert rel_rows(Ww.cpu().numpy(), Wr) < EPS
+    _, _, ndc = solver.fista_solve(Yd, hrf, 0.7, 1.0 / lip, n_iter, want_J=True, stop="window", tol=tol, wind=6, force="mfmacertonly")
+    ndc = ndc.cpu().numpy()
+    assert ((ndc == -1) | (ndc == n_iter)).all() and (ndc[nr < n_iter] == -1).all()
+    Wp, Jp, _ = solver.fista_solve(Yd, hrf, 0.7, 1.0 / lip, 200, want_J=True, force="mfmaonly")
+    Wd, Jd, ndd = solver.fista_solve(Yd, hrf, 0.7, 1.0 / lip, 200, want_J=True, stop="window", tol=1e-6, wind=6, force="mfmacertonly")
+    assert int(ndd.min()) == 200 and torch.equal(Wd, Wp) and torch.equal(Jd, Jp)      # nothing fires: the plain solve, bit for bit
+    # the _loops_deconv rule: series whose stops spread over the run
+    V = 48
+    Z = np.zeros((V, n))
+    for v in range(V):
+        for _ in range(5):
+            o = rng.randint(0, n - 20)
+            Z[v, o:o + rng.randint(8, 16)] = 1.0
+    X = orc.causal_conv(hrf, Z)
+    noise = rng.randn(V, n)
+    noise *= (np.linalg.norm(X, axis=1) / np.linalg.norm(noise, axis=1) / np.sqrt(10 ** (np.linspace(-5, 20, V) / 10)))[:, None]
+    Yl = dev32(X + noise)
+    Yh = Yl.cpu().numpy().astype(np.float64)
+    lbda = 0.003 * float(np.median(orc.lambda_max(Yh, hrf)))
+    Wo, ndo = orc.loops_batch(Yh, hrf, lbda, 1.0 / lip, 300, 1e-3)
+    W, _, nd = solver.fista_solve(Yl, hrf, lbda, 1.0 / lip, 300, stop="loops", tol=1e-3, force="mfma")
+    ndn = nd.cpu().numpy()
+    same = ndn == ndo
+    assert np.abs(ndn - ndo).max() <= 1 and same.mean() >= 0.97, (ndn, ndo)
+    assert rel_rows(W.cpu().numpy()[same], Wo[same]) < EPS
+    assert len(set(ndo.tolist())) > 5 and ndo.min() < 300
+    # taps and step in device memory: everything on the matrix-pipe form in one launch
+    taps, stepc = dev64(hrf), dev64(np.array([1.0 / lip]))
+    Wt, ndt = solver.fista_solve_pp(Yd, taps, stepc, 0.7, 60, force="one")
+    assert int(ndt.min()) == 60
+    Wot, _, _ = c_oracle.fista_batch(Y32, hrf, 0.7, 1.0 / lip, 60, threads=4)
+    assert rel_rows(Wt.cpu().numpy(), Wot) < EPS
+    Wv, _ = solver.fista_solve_pp(Yd, taps, stepc, 0.7, 60, force="valu")
+    d = ((Wt - Wv).norm(dim=1) / Wv.norm(dim=1)).cpu().numpy()
+    assert d.max() < 4e-6 and d.max() > 0.0                 # (and it is not a vector form that ran)

@@ -161,7 +161,11 @@ def test_adversarial_series_through_the_default_dispatch(solver, n, k):
 # ---- the matrix-pipe form with every series split over two waves (fista_mfma2.h) ---------------------------------
 @pytest.mark.parametrize("n,k", [(300, 30), (320, 33), (160, 27), (129, 16), (225, 27), (289, 2), (321, 30), (330, 16),
                                  (400, 27), (480, 30), (577, 30), (600, 30), (608, 30), (640, 33),
-                                 (330, 34), (400, 40), (600, 42), (640, 48)])      # (round 5: 34+ taps, three near tiles)
+                                 (330, 34), (400, 40), (600, 42), (640, 48),       # (round 5: 34+ taps, three near tiles)
+                                 # the block counts no shape above lands in: 6, 7, 9, 12, 14, 16, 17, 18 (profiles/table_entries.txt)
+                                 (192, 27), (224, 30), (288, 30), (384, 30), (448, 27), (512, 30), (544, 27), (576, 33),
+                                 # ... and with three near tiles: 8, 9, 10, 12, 14 .. 18 blocks
+                                 (250, 36), (280, 40), (310, 34), (370, 36), (440, 40), (470, 34), (500, 44), (540, 38), (570, 48)])
 def test_split_matrix_pipe_form_matches_oracle(solver, n, k):
     """`fista_mfma2_kernel`: 16 problems per workgroup of two waves, the left wave owning the first
     ceil(nb / 2) blocks of 32 samples and the right wave the rest (5 <= nb <= 20: 129 .. 640 scans -- the
@@ -362,7 +366,13 @@ def test_loops_rule_inside_the_matrix_pipe_kernel(solver, golden):
     assert torch.equal(Wl[:250], Wl[250:500])
 
 
-@pytest.mark.parametrize("n,k", [(600, 30), (400, 27), (640, 33), (300, 30), (161, 16), (600, 42), (400, 48), (300, 42), (240, 48)])
+@pytest.mark.parametrize("n,k", [(600, 30), (400, 27), (640, 33), (300, 30), (161, 16), (600, 42), (400, 48), (300, 42), (240, 48),
+                                 # every other pair of block counts the cost trace and the certificate are compiled for
+                                 # (profiles/table_entries.txt): two near tiles at 5, 7, 8, 9, 11, 12, 14 .. 18 blocks ...
+                                 (150, 20), (200, 30), (250, 27), (270, 30), (340, 30), (370, 27), (420, 30), (460, 27), (490, 30),
+                                 (530, 33), (560, 28),
+                                 # ... three at 9, 11, 12, 14 .. 18, 20
+                                 (260, 40), (350, 36), (360, 44), (430, 34), (450, 48), (500, 40), (520, 36), (550, 42), (620, 38)])
 def test_split_form_cost_trace_and_window_rule(solver, n, k):
     """`fista_mfma2_kernel<..., WITH_J, CERT>`: the cost trace (each wave adds up its half of ||r||^2 and ||w||_1, the
     halves meet at the barrier of the forward pass) against the float64 oracle's; the window rule (wind = 6) as a

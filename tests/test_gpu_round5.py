@@ -421,7 +421,8 @@ def test_ill_conditioned_series_are_solved_in_float64(solver, golden):
 # Round 5: series of 641 .. 1 280 scans on the matrix pipe (fista_mfma4.h: one series over the four waves of a workgroup)
 @pytest.mark.parametrize("n,k", [(641, 30), (700, 27), (768, 33), (769, 16), (900, 30), (1000, 2), (1024, 30), (1025, 30),
                                  (1200, 28), (1216, 33), (1217, 30), (1279, 30), (1280, 32),
-                                 (700, 34), (900, 40), (1200, 42), (1216, 48), (641, 48), (1250, 42), (1280, 48)])
+                                 (700, 34), (900, 40), (1200, 42), (1216, 48), (641, 48), (1250, 42), (1280, 48),
+                                 (800, 40), (1100, 36)])     # (three near tiles at seven and nine blocks per wave: profiles/table_entries.txt)
 def test_four_wave_matrix_pipe_form_matches_oracle(solver, n, k):
     """`fista_mfma4_kernel`: 16 problems per workgroup of four waves, wave j owning blocks j A .. j A + A - 1 of 32 samples
     (A = ceil(N / 128): 6 .. 10; the last wave holds the end of the series and the padding behind it) -- HCP-length
@@ -509,14 +510,24 @@ def test_partition_and_guard_for_series_of_1200_scans(solver):
     assert int(nd.min()) == 150 and rel_rows(W[idx].cpu().numpy()[nz], Wo1[nz]).max() < 1e-5
 
 
-@pytest.mark.parametrize("n,k", [(600, 30), (330, 27), (640, 33), (1200, 28), (700, 30), (600, 42), (640, 48), (1200, 42), (300, 42)])
+@pytest.mark.parametrize("n,k", [(600, 30), (330, 27), (640, 33), (1200, 28), (700, 30), (600, 42), (640, 48), (1200, 42), (300, 42),
+                                 # every other block count the rule is compiled for (profiles/table_entries.txt) -- two waves, two
+                                 # near tiles: 5 .. 10 and 12 .. 18 blocks ...
+                                 (140, 27), (170, 27), (210, 30), (230, 27), (260, 30), (316, 30), (370, 30), (410, 27), (440, 30),
+                                 (470, 27), (500, 30), (530, 27), (570, 30),
+                                 # ... three near tiles: 8, 9, 11 .. 18 blocks ...
+                                 (250, 40), (280, 36), (340, 42), (380, 34), (400, 44), (430, 40), (480, 36), (510, 48), (540, 40),
+                                 (560, 34),
+                                 # ... four waves: 7, 8, 9 blocks per wave with two near tiles, 6 .. 9 with three
+                                 (800, 30), (1000, 27), (1100, 30), (700, 40), (850, 36), (1020, 42), (1150, 34)])
 def test_loops_rule_inside_the_split_forms(solver, n, k):
     """`_loops_deconv`'s criterion (pybold/bold_signal.py:267-273) in full inside `fista_mfma2_kernel<..., LOOPS>` (311 .. 640
     scans) and `fista_mfma4_kernel<..., LOOPS>` (641 .. 1 280): every wave adds up its share of the two float64 norms beside the
     update, the shares meet in LDS at the barrier that ends the iteration; a problem that meets the rule is written out at
     that moment and its lanes keep iterating.  Stop iterations and iterates against the float64 oracle on series whose
     stops spread over the run (a criterion within ~1e-6 of `tol` may cross one iteration apart: +-1 on 2 % at most);
-    through the library's own dispatch too (whole passes on the split form, the rest on the one-problem-per-wave form)."""
+    through the library's own dispatch too (whole passes on the split form, the rest on the one-problem-per-wave form; series of
+    up to 310 scans with up to 33 taps reach the two-wave form through the pin only, their default dispatch is the one-wave form)."""
     rng = np.random.RandomState(n + k)
     hrf = orc.spm_hrf(1.0, 1.0, float(k), False)[0][:k]
     lip = orc.gram_lipschitz(hrf, n)
@@ -546,7 +557,8 @@ def test_loops_rule_inside_the_split_forms(solver, n, k):
     # the default dispatch at a batch size that fills passes
     reps = 6000 // V + 1
     Yl = Y.repeat(reps, 1)[:6000].contiguous()
-    assert ("split over" in solver.which_kernel(n, k, 6000, stop="loops")) or ("four waves" in solver.which_kernel(n, k, 6000, stop="loops"))
+    if n > 310 or k > 33:                    # (shorter series with up to 33 taps: the one-wave form, with the same rule inside)
+        assert ("split over" in solver.which_kernel(n, k, 6000, stop="loops")) or ("four waves" in solver.which_kernel(n, k, 6000, stop="loops"))
     Wl, _, ndl = solver.fista_solve(Yl, hrf, lbda, 1.0 / lip, 300, stop="loops", tol=tol)
     ref_nd = ndo[np.arange(6000) % V]
     assert np.abs(ndl.cpu().numpy() - ref_nd).max() <= 1 and (ndl.cpu().numpy() == ref_nd).mean() >= 0.97
@@ -554,15 +566,31 @@ def test_loops_rule_inside_the_split_forms(solver, n, k):
     assert rel_rows(Wl[:V].cpu().numpy()[ok], Wo[ok]).max() < 1e-5
 
 
-@pytest.mark.parametrize("n,k,P", [(600, 27, 8192 + 150), (1200, 28, 4096 + 90), (400, 20, 6000), (600, 40, 8192 + 150), (1000, 44, 4096 + 90)])
+@pytest.mark.parametrize("n,k,P", [(600, 27, 8192 + 150), (1200, 28, 4096 + 90), (400, 20, 6000), (600, 40, 8192 + 150), (1000, 44, 4096 + 90),
+                                   # every other block count compiled with the taps in device memory that a call reaches
+                                   # (profiles/table_entries.txt), in batches that one pass of the split form takes whole --
+                                   # two waves, two near tiles: 5 .. 12, 14 .. 18 and 20 blocks (up to 310 scans: what whole rounds
+                                   # of the one-wave form leave, between 4 608 problems and half a round) ...
+                                   (150, 20, 6000), (180, 27, 6000), (210, 20, 6000), (250, 27, 6000), (280, 30, 6000), (300, 27, 6000),
+                                   (340, 27, 6000), (380, 30, 6000), (440, 27, 6000), (470, 30, 6000), (500, 20, 6000), (540, 27, 6000),
+                                   (570, 30, 6000), (640, 33, 6000),
+                                   # ... three near tiles (311+ scans): 10 .. 18 and 20 blocks ...
+                                   (315, 40, 3000), (350, 36, 3000), (380, 40, 3000), (410, 34, 3000), (440, 44, 3000), (470, 38, 3000),
+                                   (500, 40, 3000), (530, 36, 3000), (560, 48, 3000), (630, 40, 3000),
+                                   # ... four waves: 6 .. 9 blocks per wave with two near tiles, 6, 7, 9, 10 with three
+                                   (700, 27, 2800), (800, 30, 2800), (1000, 20, 2800), (1100, 27, 2800),
+                                   (650, 40, 2800), (850, 36, 2800), (1100, 44, 2800), (1250, 40, 2800)])
 def test_shared_hrf_z_step_of_long_series_on_the_split_forms(solver, n, k, P):
     """`pb_fista_solve_pp` with ONE HRF and step in device memory (the blind step's z-step, bd_shared) at 321 .. 1 280 scans:
     whole passes on `fista_mfma2_kernel<..., TAPS_DEV>` / `fista_mfma4_kernel<..., TAPS_DEV>`, the rest and what the guards
     hand back on the one-problem-per-wave form -- against the float64 oracle and against the vector dispatch; HRFs of 34+ taps
-    with three near tiles (the cumulative taps beyond lag 63 built on the device)."""
+    with three near tiles (the cumulative taps beyond lag 63 built on the device).  Series of 129 .. 310 scans meet the two-wave
+    form in what whole rounds of the one-wave form leave (here: a batch of 6 000, one pass)."""
     rng = np.random.RandomState(n + k)
     h = orc.spm_hrf(0.9, 20.0 / k, 20.0, False)[0][:k]            # (a 20 s HRF sampled at k points)
     assert len(h) == k
+    plan = solver.launch_plan(n, k, P)                            # (the plain call's plan: the z-step takes the same pieces)
+    assert any(s and ("split over two" in s or "four waves" in s) for s in plan[1:]), plan
     lip = orc.gram_lipschitz(h, n)
     Yb = torch.from_numpy(rng.randn(P, n).astype(np.float32)).cuda()
     taps, stepc = torch.from_numpy(h.copy()).cuda(), torch.from_numpy(np.array([1.0 / lip])).cuda()
