@@ -77,6 +77,7 @@ extern "C" {
 #define PB_FLAG_ONLY_DENSE 131072u  /* measurement aids for a partitioned call: only the dense class / only the sparse */
 #define PB_FLAG_ONLY_SPARSE 262144u /*   class is solved; the other class's rows of w and n_done are left untouched */
 #define PB_FLAG_NO_ILL_GUARD 524288u /* partitioned calls: do not single out ill-conditioned series (see pb_fista_solve_ex) */
+#define PB_FLAG_PP_SPLIT 1048576u   /* pb_fista_solve_pp_d only: the four-wave form with per-problem taps (641 .. 1 280 scans), or an error */
 #define PB_FLAG_ONE_LAUNCH 32u    /* never split a plain solve into a full-rounds launch and a
                                      remainder launch (see pb_fista_solve) */
 
@@ -488,17 +489,27 @@ int pb_fista_which_kernel_d(int N, int K, int with_cost_trace, int stop_mode, in
  *                                         (csrc/fista_exact_pp.h: the pass body of fista_exact_kernel, taps in scalar registers)
  *   otherwise (641+ scans, 33+ taps, other windows), or with PB_FLAG_FORCE_GENERIC:                0
  *                                         the any-size LDS kernel reading taps_dev + p * ldt
- *   (-1: the shape exceeds LDS as well, the call fails).  There is no four-wave form with per-problem taps: series
- *   of 641 .. 1 280 scans run on the LDS kernel.  PB_FLAG_FORCE_FAST: the register form or an error.
+ *   (-1: the shape exceeds LDS as well, the call fails).  PB_FLAG_FORCE_FAST: the register form or an error.
+ *   OPT-IN, with PB_FLAG_PP_SPLIT only:
+ *   641 .. 1280 <= 32     wind = 6        fista_exact_split_pp_kernel, one problem per workgroup   (not reported: the
+ *                                         of four waves (csrc/fista_exact_split_pp.h: the pass      query describes the
+ *                                         halves of fista_exact_split_kernel, taps in scalar        call without flags)
+ *                                         registers); row p carries the bits pb_fista_solve_d returns for that row alone
+ *   Without the flag series of 641 .. 1 280 scans run on the LDS kernel, as before the four-wave form existed.  With it the
+ *   call runs that form or fails (PB_ERR_INVALID, nothing launched): N outside 641..1280, K > 32, the window rule with
+ *   wind != 6, or the flag together with PB_FLAG_FORCE_GENERIC / PB_FLAG_FORCE_FAST.  No other entry point reads the flag.
  * Errors (nothing is launched): NULL pointers, ldt < K, a leading dimension too small, an unknown stop_mode, a shape
  * that exceeds LDS.  P = 0 is a no-op.
  * pb_fista_which_kernel_pp_d  the code of the form pb_fista_solve_pp_d (no flags) runs for a call shape.  Host-only query.
+ * pb_fista_pp_split_supported  1 if pb_fista_solve_pp_d with PB_FLAG_PP_SPLIT runs for (N, K, stop_mode, wind):
+ *                     641 <= N <= 1280, 1 <= K <= 32, a known stop_mode, wind = 6 under PB_STOP_WINDOW; else 0.  Host-only query.
  */
 int pb_fista_solve_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
                         const double* taps_dev, int64_t ldt, int K, const double* step_dev, double lbda,
                         const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj,
                         int stop_mode, double tol, int wind, int32_t* n_done_dev, unsigned flags, void* stream);
 int pb_fista_which_kernel_pp_d(int N, int K, int with_cost_trace, int stop_mode, int wind);
+int pb_fista_pp_split_supported(int N, int K, int stop_mode, int wind);
 /*
  * OPT-IN EXTRA, never part of a parity run: the recurrence of pb_fista_solve_d with a BACKTRACKED step.  The reference
  * has a constant step only (pybold/bold_signal.py:52-53 / :253-254: 1 / (0.9 rho) or 1 / ||A^T A||_F); this is
@@ -581,6 +592,7 @@ int pb_lambda_max_d(const double* y_dev, int64_t ldy, int V, int N, const double
  *                         outer_chunk = 0: the library chooses max(1, 32768 / (nb_sub_iter * ceil(V / 512))): 512 workgroups
  *                         of this kernel are resident at once (two per compute unit), and its inner iteration takes about
  *                         twice that of the one-wave kernel, so the budget per slot and launch is half as large.
+ *                         It answers for the shapes of pb_auto_lbda_split_pp_d too.
  * Errors (nothing is launched): those of pb_auto_lbda_d, with N outside 641..1280 in the place of N > 640.
  */
 int pb_auto_lbda_supported(int N, int K, int wind);
@@ -604,6 +616,19 @@ int pb_auto_lbda_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t l
                       int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr,
                       double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev,
                       double* work_dev, int64_t work_len, void* stream);
+/*
+ * OPT-IN: pb_auto_lbda_pp_d with one voxel per workgroup of four waves (auto_lbda_split_pp_kernel,
+ * csrc/fista_exact_split_pp.h) for series of 641 .. 1 280 scans: the parameter list of pb_auto_lbda_pp_d; the shape limits
+ * (pb_auto_lbda_split_supported), the workspace (pb_auto_lbda_work_len), the outer_chunk rule and the launch protocol of
+ * pb_auto_lbda_split_d.  Row v carries the bits pb_auto_lbda_split_d returns for that voxel alone with its HRF and step.
+ * pb_auto_lbda_pp_d keeps its limit of 640 scans: this form is asked for by name.  Errors in addition: ldt < K.
+ */
+int pb_auto_lbda_split_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                            const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
+                            const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter,
+                            int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr,
+                            double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev,
+                            double* work_dev, int64_t work_len, void* stream);
 int pb_auto_lbda_split_supported(int N, int K, int wind);
 int pb_auto_lbda_split_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
                          const double* taps_host, int K, double step, const double* betas_dev,

@@ -31,6 +31,7 @@ PB_FLAG_FORCE_MFMA2 = 65536
 PB_FLAG_ONLY_DENSE = 131072
 PB_FLAG_ONLY_SPARSE = 262144
 PB_FLAG_NO_ILL_GUARD = 524288
+PB_FLAG_PP_SPLIT = 1048576           # pb_fista_solve_pp_d only: the four-wave per-problem-tap form or an error
 PB_PATH_DENSE_RATIO = 0.19          # include/pybold_hip.h (series of up to 310 scans; 0.22 beyond)
 PB_STOP_NONE = 0
 PB_STOP_LOOPS = 1
@@ -142,6 +143,7 @@ SIGNATURES = {
         _c_int, _c_dbl, _c_int, _ptr,    # stop_mode, tol, wind, n_done_dev
         ctypes.c_uint, _ptr]),           # flags, stream
     "pb_fista_which_kernel_pp_d": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "pb_fista_pp_split_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int]),
     "pb_auto_lbda_pp_d": (_c_int, [
         _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,     # y_dev, ldy, w_dev, ldw, cold, V, N
         _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr,                 # taps_dev, ldt, K, step_dev, betas_dev, sigma_dev
@@ -166,6 +168,13 @@ SIGNATURES = {
         _ptr, _ptr, _ptr, _c_i64,                               # R_dev, G_dev, J_dev, ldt
         _ptr, _ptr, _ptr, _ptr,                                 # alpha_dev, lbda_dev, n_outer_dev, n_inner_dev
         _ptr, _c_i64, _ptr]),                                   # work_dev, work_len, stream
+    "pb_auto_lbda_split_pp_d": (_c_int, [                       # (the argument list of pb_auto_lbda_pp_d)
+        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
+        _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr,
+        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,
+        _ptr, _ptr, _ptr, _c_i64,
+        _ptr, _ptr, _ptr, _ptr,
+        _ptr, _c_i64, _ptr]),
     "pb_auto_lbda_split_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "pb_auto_lbda_split_d": (_c_int, [                          # (the argument list of pb_auto_lbda_d)
         _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,

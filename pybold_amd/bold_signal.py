@@ -125,8 +125,21 @@ DISPATCH = os.environ.get("PYBOLD_AMD_DISPATCH", "ctypes")
 # the device, one voxel per wave -- series of up to 640 scans, HRFs of up to 32 taps, wind = 6; other shapes keep the
 # host loop) or "device_split" (the same, and series of 641 .. 1 280 scans on the search with one voxel per workgroup of four
 # waves, `deconv_auto(engine="device_split")`; shapes neither carries keep the host loop).  1-D calls always keep the host
-# loop.  Initialised from the environment variable PYBOLD_AMD_AUTO_LBDA.
+# loop.  "device_split_pp": everything "device_split" does, and calls with one HRF per voxel (a 2-D `hrf`) of 641 .. 1 280
+# scans on `deconv_auto(engine="device_split_pp")`.  Initialised from the environment variable PYBOLD_AMD_AUTO_LBDA.
 AUTO_LBDA = os.environ.get("PYBOLD_AMD_AUTO_LBDA", "host")
+
+# Opt-in: the fixed-lambda solves with one HRF per voxel (a 2-D `hrf`: `deconv` with a `lbda`, and the inner solves of the
+# host-loop lambda search) run series of 641 .. 1 280 scans on the register-resident form with one voxel per workgroup of
+# four waves (`solver.fista_solve_pp_d(force="split")`) instead of the LDS kernel, where `solver.pp_split_supported` says
+# the shape is carried.  Off by default: no call changes its kernel unless asked.  Initialised from the environment
+# variable PYBOLD_AMD_PP_SPLIT ("1" is on).
+PER_VOXEL_SPLIT = os.environ.get("PYBOLD_AMD_PP_SPLIT", "0") == "1"
+
+
+def _pv_force(n, n_taps, stop, wind):
+    """``force`` of a per-voxel-HRF solve: ``"split"`` when ``PER_VOXEL_SPLIT`` is on and the shape is carried."""
+    return "split" if PER_VOXEL_SPLIT and solver.pp_split_supported(n, n_taps, stop, wind) else None
 
 
 def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
@@ -147,10 +160,12 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
     """
     per_voxel = _per_voxel_hrf(y, hrf, "deconv")
     if lbda is None:
-        if AUTO_LBDA in ("device", "device_split") and _n_dim(y) == 2:
+        if AUTO_LBDA in ("device", "device_split", "device_split_pp") and _n_dim(y) == 2:
             n_taps = int(_shape_of(hrf)[-1]) if per_voxel else np.size(hrf)
+            split = AUTO_LBDA != "device" and solver.auto_lbda_split_supported(_n_scans(y), n_taps, wind)
             engine = ("device" if solver.auto_lbda_supported(_n_scans(y), n_taps, wind)
-                      else "device_split" if AUTO_LBDA == "device_split" and not per_voxel and solver.auto_lbda_split_supported(_n_scans(y), n_taps, wind)
+                      else "device_split" if split and not per_voxel
+                      else "device_split_pp" if split and per_voxel and AUTO_LBDA == "device_split_pp"
                       else None)
             if engine:
                 return deconv_auto(y, t_r, hrf, early_stopping=early_stopping, tol=tol, wind=wind, nb_iter=nb_iter,
@@ -160,8 +175,10 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
         # one HRF per voxel: float64 end to end (pb_fista_solve_pp_d; the torch.ops shim has no such operator, so
         # DISPATCH == "torch_ops" takes this path too)
         Y, T, one_d = _pv_to_device(y, hrf)
+        stop = "window" if early_stopping else None
         W, J, n_done = solver.fista_solve_pp_d(Y, T, _pv_steps(T, Y.shape[1]), lbda, int(nb_iter), want_J=True,
-                                               stop="window" if early_stopping else None, tol=tol, wind=wind)
+                                               stop=stop, tol=tol, wind=wind,
+                                               force=_pv_force(Y.shape[1], T.shape[1], stop, wind))
         X, Z = solver.fista_outputs_pp(W, T)
         return _deconv_results(Y, one_d, X, Z, W, J, n_done, verbose)
     Y, one_d = _y_to_device(y)
@@ -235,9 +252,12 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
             "auto": the device where it carries the call, else the host loop with one warning;
             "device_split": the device-resident solve with one voxel per workgroup of four waves
             (``solver.auto_lbda_solve_split``: series of 641 .. 1 280 scans, HRFs of up to 32 taps, ``wind == 6`` --
-            ``ValueError`` otherwise; ``"device"`` and ``"auto"`` do not reach it)
+            ``ValueError`` otherwise; ``"device"`` and ``"auto"`` do not reach it);
+            "device_split_pp": the same with one HRF per voxel (``solver.auto_lbda_solve_split_pp``; a 2-D ``hrf`` is
+            required, the same limits -- ``ValueError`` otherwise; no other engine reaches it)
     hrf     1-D, or ``(V, K)`` beside a ``(V, N)`` batch: one HRF per voxel (``solver.auto_lbda_solve_pp`` on the device engine,
-            the host loop on ``solver.fista_solve_pp_d``; ``"device_split"`` takes one HRF for all voxels: ``ValueError``)
+            the host loop on ``solver.fista_solve_pp_d``; ``"device_split"`` takes one HRF for all voxels, ``ValueError``;
+            ``"device_split_pp"`` takes one per voxel)
     outer_chunk  device engine: outer iterations per kernel launch (``None``: the library's choice); no effect on
             the result
 
@@ -245,20 +265,30 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     same input (lists for a 1-D ``y``; ``(n_outer, V)`` arrays padded with NaN for a batch, trimmed to the longest
     row's outer iterations; CUDA in -> ``x, z, diff_z`` CUDA); ``info`` holds ``alpha``, ``lbda`` (final, per
     voxel), ``n_outer``, ``n_inner`` (outer / summed inner iterations per voxel), ``sigma`` and ``engine``."""
-    if engine not in ("auto", "device", "host", "device_split"):
-        raise ValueError("deconv_auto: engine must be 'auto', 'device', 'host' or 'device_split', got %r" % (engine,))
+    if engine not in ("auto", "device", "host", "device_split", "device_split_pp"):
+        raise ValueError("deconv_auto: engine must be 'auto', 'device', 'host', 'device_split' or 'device_split_pp', got %r"
+                         % (engine,))
     per_voxel = _per_voxel_hrf(y, hrf, "deconv_auto")
     n, n_taps = _n_scans(y), (int(_shape_of(hrf)[-1]) if per_voxel else int(np.size(hrf)))
     if engine == "device_split":
         if per_voxel:
             raise ValueError("deconv_auto(engine='device_split'): the four-wave device-resident lambda search takes one HRF "
                              "for all voxels; with one HRF per voxel (hrf of shape %s) the device-resident search carries "
-                             "series of up to 640 scans (engine='device'), longer ones run the host loop (engine='host')"
+                             "series of up to 640 scans (engine='device'), longer ones run the host loop (engine='host') "
+                             "or, opt-in, the four-wave search with per-voxel HRFs (engine='device_split_pp')"
                              % (_shape_of(hrf),))
         if not solver.auto_lbda_split_supported(n, n_taps, wind):
             raise ValueError("deconv_auto(engine='device_split'): the four-wave device-resident lambda search carries series of "
                              "641..1280 scans, HRFs of up to 32 taps and wind = 6; this call has %d scans, %d taps, wind = %d"
                              % (n, n_taps, wind))
+    elif engine == "device_split_pp":
+        if not per_voxel:
+            raise ValueError("deconv_auto(engine='device_split_pp'): the four-wave device-resident lambda search with one HRF "
+                             "per voxel takes hrf of shape (V, K); a 1-D hrf runs on engine='device_split'")
+        if not solver.auto_lbda_split_supported(n, n_taps, wind):
+            raise ValueError("deconv_auto(engine='device_split_pp'): the four-wave device-resident lambda search carries "
+                             "series of 641..1280 scans, HRFs of up to 32 taps and wind = 6; this call has %d scans, %d taps, "
+                             "wind = %d" % (n, n_taps, wind))
     elif engine != "host":
         if solver.auto_lbda_supported(n, n_taps, wind):
             engine = "device"
@@ -285,8 +315,9 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     if per_voxel:
         Y, T, one_d = _pv_to_device(y, hrf)
         V = Y.shape[0]
-        W, res = solver.auto_lbda_solve_pp(Y, T, _pv_steps(T, n), sigma, early_stopping=early_stopping, tol=tol, wind=wind,
-                                           nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
+        solve = solver.auto_lbda_solve_split_pp if engine == "device_split_pp" else solver.auto_lbda_solve_pp
+        W, res = solve(Y, T, _pv_steps(T, n), sigma, early_stopping=early_stopping, tol=tol, wind=wind,
+                       nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
         X, Z = solver.fista_outputs_pp(W, T)
         return _deconv_auto_results(one_d, V, X, Z, W, res, sigma, engine, verbose)
     one_d = _Shape(_n_dim(y) == 1, on_device)
@@ -373,9 +404,11 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
     stop = "window" if early_stopping else None
     if per_voxel:                                  # one HRF and one step per voxel: the same loop on the per-voxel entry points
         steps = _pv_steps(T, n)
+        force = _pv_force(n, T.shape[1], stop, wind)
 
         def solve(lbda, W):
-            return solver.fista_solve_pp_d(Y, T, steps, lbda, int(nb_sub_iter), W0=W, stop=stop, tol=tol, wind=wind)
+            return solver.fista_solve_pp_d(Y, T, steps, lbda, int(nb_sub_iter), W0=W, stop=stop, tol=tol, wind=wind,
+                                           force=force)
 
         def stats(W):
             return solver.fista_stats_pp(W, Y, T)

@@ -19,6 +19,7 @@
 #include "fista_exact_split.h"
 #include "fista_auto.h"
 #include "fista_exact_pp.h"
+#include "fista_exact_split_pp.h"
 #include "blind.h"
 #include "fista_mfma.h"
 #include "fista_mfma2.h"
@@ -884,7 +885,8 @@ int pb_fista_which_kernel_d(int N, int K, int with_cost_trace, int stop_mode, in
 }
 
 // pb_fista_solve_d with one HRF and one step per problem, both in device memory: the register form with one problem
-// per wave (fista_exact_pp.h) where the shape has an entry, else the LDS kernel with FistaArgs::taps_pp; no four-wave form
+// per wave (fista_exact_pp.h) where the shape has an entry, else the LDS kernel with FistaArgs::taps_pp.  The four-wave form
+// (fista_exact_split_pp.h, 641 .. 1 280 scans) runs only when PB_FLAG_PP_SPLIT names it: without the flag nothing changes
 int pb_fista_solve_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
                         const double* taps_dev, int64_t ldt, int K, const double* step_dev, double lbda,
                         const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj,
@@ -897,10 +899,21 @@ int pb_fista_solve_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_d
   if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW)
     return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: unknown stop_mode %d", stop_mode);
   if (stop_mode == PB_STOP_WINDOW && wind < 2) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: wind must be >= 2");
-  const ExactPPEntry* ee = (flags & PB_FLAG_FORCE_GENERIC) ? nullptr : pick_exact_pp(N, K, stop_mode, wind);
+  const ExactSplitPPEntry* se = nullptr;
+  if (flags & PB_FLAG_PP_SPLIT) {
+    if (flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_FAST))
+      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: PB_FLAG_PP_SPLIT names the four-wave form; it excludes PB_FLAG_FORCE_GENERIC and PB_FLAG_FORCE_FAST");
+    if (N < 641 || N > 1280) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: PB_FLAG_PP_SPLIT with N=%d outside 641..1280 scans", N);
+    if (K > 32) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: PB_FLAG_PP_SPLIT with K=%d exceeds 32 taps", K);
+    if (stop_mode == PB_STOP_WINDOW && wind != 6)
+      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: PB_FLAG_PP_SPLIT with wind=%d (the four-wave form carries wind = 6)", wind);
+    se = pick_exact_split_pp(N, K, stop_mode, wind);
+    if (!se) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: no four-wave specialisation for N=%d K=%d", N, K);
+  }
+  const ExactPPEntry* ee = (se || (flags & PB_FLAG_FORCE_GENERIC)) ? nullptr : pick_exact_pp(N, K, stop_mode, wind);
   if (!ee && (flags & PB_FLAG_FORCE_FAST))
     return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: no register-resident float64 kernel with one problem per wave for N=%d K=%d", N, K);
-  if (!ee && gen_lds_doubles(N, K, stop_mode, wind) > LDS_DOUBLES_MAX)
+  if (!ee && !se && gen_lds_doubles(N, K, stop_mode, wind) > LDS_DOUBLES_MAX)
     return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: N=%d K=%d wind=%d exceeds LDS", N, K, wind);
   if (P == 0) return PB_OK;
   if (!y_dev || !w_dev || !taps_dev || !step_dev || (n_iter > 0 && !betas_dev))
@@ -910,6 +923,11 @@ int pb_fista_solve_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_d
                                n_done_dev, flags);
   a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj; a.wind = wind;
   a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = 0;
+  if (se) {
+    if (se->fn(a, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
+      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: launch rejected");
+    return check_launch("fista_exact_split_pp_kernel");
+  }
   if (ee) {
     if (ee->fn(a, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
       return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: launch rejected");
@@ -917,6 +935,10 @@ int pb_fista_solve_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_d
   }
   launch_generic(a, taps_dev, K, wind, J_dev != nullptr, true, P, (hipStream_t)stream);
   return check_launch("fista_generic_kernel(f64, pp)");
+}
+
+int pb_fista_pp_split_supported(int N, int K, int stop_mode, int wind) {
+  return pick_exact_split_pp(N, K, stop_mode, wind) ? 1 : 0;
 }
 
 int pb_fista_which_kernel_pp_d(int N, int K, int with_cost_trace, int stop_mode, int wind) {
@@ -988,19 +1010,29 @@ int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw,
 
 // pb_auto_lbda_d with one HRF (taps_dev [V][ldt]) and one step (step_dev [V]) per voxel: its validation in its order (the
 // taps' leading dimension beside the others, the step's sign is the caller's), its chunk, its launch protocol
-int pb_auto_lbda_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+// (split = true: pb_auto_lbda_split_pp_d, one voxel per workgroup of four waves, 641 .. 1 280 scans, with the limits and the
+// chunk of pb_auto_lbda_split_d)
+namespace {
+int auto_lbda_pp_impl(const char* name, bool split, const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
                       const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
                       const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
                       int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
                       double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
                       void* stream) {
-  const char* name = "pb_auto_lbda_pp_d";
   if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "%s: bad size (V=%d N=%d K=%d)", name, V, N, K);
   if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "%s: wind=%d (the device-resident search carries wind = 6)", name, wind);
-  if (N > 640) return fail(PB_ERR_INVALID, "%s: N=%d exceeds 640 scans", name, N);
+  if (!split && N > 640) return fail(PB_ERR_INVALID, "%s: N=%d exceeds 640 scans", name, N);
+  if (split && (N < 641 || N > 1280)) return fail(PB_ERR_INVALID, "%s: N=%d outside 641..1280 scans", name, N);
   if (K > 32) return fail(PB_ERR_INVALID, "%s: K=%d exceeds 32 taps", name, K);
-  const ExactPPEntry* ae = pick_auto(N, K) ? pick_exact_pp(N, K, PB_STOP_WINDOW, wind) : nullptr;
-  if (!ae || !ae->fn_auto) return fail(PB_ERR_INVALID, "%s: no specialisation for N=%d K=%d", name, N, K);
+  auto_pp_launch_fn fn_auto = nullptr;
+  if (split) {
+    const ExactSplitPPEntry* se = pick_auto_split(N, K) ? pick_exact_split_pp(N, K, PB_STOP_WINDOW, wind) : nullptr;
+    fn_auto = se ? se->fn_auto : nullptr;
+  } else {
+    const ExactPPEntry* ae = pick_auto(N, K) ? pick_exact_pp(N, K, PB_STOP_WINDOW, wind) : nullptr;
+    fn_auto = ae ? ae->fn_auto : nullptr;
+  }
+  if (!fn_auto) return fail(PB_ERR_INVALID, "%s: no specialisation for N=%d K=%d", name, N, K);
   if (nb_iter < 1 || nb_sub_iter < 0 || outer_chunk < 0)
     return fail(PB_ERR_INVALID, "%s: nb_iter >= 1, nb_sub_iter >= 0 and outer_chunk >= 0 are required (%d, %d, %d)", name,
                 nb_iter, nb_sub_iter, outer_chunk);
@@ -1020,16 +1052,39 @@ int pb_auto_lbda_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t l
   a.betas = betas_dev; a.sigma = sigma_dev; a.R = R_dev; a.G = G_dev; a.J = J_dev; a.ldt = ldtr;
   a.alpha_out = alpha_dev; a.lbda_out = lbda_dev; a.n_outer = n_outer_dev; a.n_inner = n_inner_dev; a.work = work_dev;
   a.taps_pp = taps_dev; a.ld_taps = ldt; a.step_vec = step_dev; a.K = K;
-  const int chunk = outer_chunk > 0 ? outer_chunk : auto_outer_chunk(V, nb_sub_iter);
+  const int chunk = outer_chunk > 0 ? outer_chunk : (split ? auto_split_outer_chunk(V, nb_sub_iter) : auto_outer_chunk(V, nb_sub_iter));
   for (int i0 = 0; i0 < nb_iter; i0 += chunk) {        // outer iterations [i0, i1) of the voxels still searching
     a.init = i0 == 0; a.i0 = i0; a.i1 = (nb_iter - i0 < chunk) ? nb_iter : i0 + chunk; a.final_solve = 0;
-    if (ae->fn_auto(a, early_stopping != 0, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
-    const int rc = check_launch("auto_lbda_pp_kernel");
+    if (fn_auto(a, early_stopping != 0, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
+    const int rc = check_launch(split ? "auto_lbda_split_pp_kernel" : "auto_lbda_pp_kernel");
     if (rc != PB_OK) return rc;
   }
   a.init = 0; a.i0 = a.i1 = nb_iter; a.final_solve = 1;   // the last inner solve of every voxel, then the outputs
-  if (ae->fn_auto(a, early_stopping != 0, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
-  return check_launch("auto_lbda_pp_kernel(final solve)");
+  if (fn_auto(a, early_stopping != 0, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
+  return check_launch(split ? "auto_lbda_split_pp_kernel(final solve)" : "auto_lbda_pp_kernel(final solve)");
+}
+}  // namespace
+
+int pb_auto_lbda_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                      const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
+                      const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
+                      int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
+                      double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
+                      void* stream) {
+  return auto_lbda_pp_impl("pb_auto_lbda_pp_d", false, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev, betas_dev,
+                           sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldtr,
+                           alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
+}
+
+int pb_auto_lbda_split_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                            const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
+                            const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
+                            int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
+                            double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
+                            void* stream) {
+  return auto_lbda_pp_impl("pb_auto_lbda_split_pp_d", true, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev, betas_dev,
+                           sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldtr,
+                           alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
 }
 
 int pb_auto_lbda_split_supported(int N, int K, int wind) { return (wind == pb::AUTO_WIND && pick_auto_split(N, K)) ? 1 : 0; }

@@ -232,6 +232,36 @@ const ExactPPEntry* pick_exact_pp(int N, int K, int stop_mode, int wind) {
   return pick_cheapest(kExactPP, N, K, 64);
 }
 
+// ... and with one problem over the four waves of a workgroup (fista_exact_split_pp.h): the pairs of
+// exact_split_table.inc.  OPT-IN: pick_exact_pp above never falls through to it -- PB_FLAG_PP_SPLIT and
+// pb_auto_lbda_split_pp_d name it
+struct ExactSplitPPEntry {
+  int S, KT;
+  exact_pp_launch_fn fn;
+  auto_pp_launch_fn fn_auto;
+};
+}  // namespace
+namespace pb {
+#define PB_EXACT_SPLIT(S, KT)                                                                  \
+  extern template int launch_exact_split_pp<S, KT>(const FistaArgs&, bool, int, hipStream_t); \
+  extern template int launch_auto_split_pp<S, KT>(const AutoArgsPP&, bool, hipStream_t);
+#include "exact_split_table.inc"
+#undef PB_EXACT_SPLIT
+}  // namespace pb
+namespace {
+#define PB_EXACT_SPLIT(S, KT) {S, KT, &pb::launch_exact_split_pp<S, KT>, &pb::launch_auto_split_pp<S, KT>},
+const ExactSplitPPEntry kExactSplitPP[] = {
+#include "exact_split_table.inc"
+};
+#undef PB_EXACT_SPLIT
+// the shapes beyond the one-wave entries only (641 .. 1 280 scans); the window rule is wind = 6
+const ExactSplitPPEntry* pick_exact_split_pp(int N, int K, int stop_mode, int wind) {
+  if (N < 1 || K < 1 || pick_exact(N, K)) return nullptr;
+  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return nullptr;
+  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
+  return N > 640 ? pick_cheapest(kExactSplitPP, N, K, 64 * pb::SPLIT_WAVES) : nullptr;
+}
+
 template <int S, int KT>
 constexpr launch_fn pair_or_null() {
   if constexpr (S <= 20 && KT <= 32) return &pb::launch_pair<S, KT>; else return nullptr;

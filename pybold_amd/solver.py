@@ -262,6 +262,8 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
           length: ``PB_PATH_DENSE_RATIO`` 0.19 up to 310 scans, ``_LONG`` 0.22 up to 640, ``_LONGER`` 0.26 up to 1 280
     Returns ``(W float64 (P, N), J float32 (P, n_iter) or None, n_done int32 (P,))``.
     """
+    if force == "split":
+        raise ValueError("force='split' names the four-wave form with one HRF per problem: fista_solve_pp_d only")
     lib = _lib.load()
     f64 = torch.is_tensor(Y) and Y.dtype == torch.float64
     Y = _rows(Y, torch.float64 if f64 else torch.float32, "Y")
@@ -776,6 +778,9 @@ def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=N
     lbda   scalar or ``(V,)``;  W0  optional float64 CUDA ``(V, N)`` warm start (not modified)
     force  None | "fast" (the register form, one problem per wave: ``N <= 640``, ``K <= 32``, window rule at
            ``wind == 6``) | "generic" (the LDS kernel); :func:`which_kernel_pp_f64` names the dispatch's choice
+           | "split" (opt-in, ``PB_FLAG_PP_SPLIT``: one problem per workgroup of four waves, ``641 <= N <= 1280``,
+           ``K <= 32``, window rule at ``wind == 6`` -- :func:`pp_split_supported`; any other shape is an error.
+           Without it such series run on the LDS kernel)
     Returns ``(W float64 (V, N), J float64 (V, n_iter) or None, n_done int32 (V,))``."""
     lib = _lib.load()
     Y = _rows(Y, torch.float64, "Y")
@@ -787,9 +792,10 @@ def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=N
     steps = torch.as_tensor(steps, dtype=torch.float64).to(dev).contiguous().ravel()
     if steps.numel() != V:
         raise ValueError("steps must have one entry per voxel (%d)" % V)
-    if force not in (None, "generic", "fast"):
+    if force not in (None, "generic", "fast", "split"):
         raise ValueError("float64 y: force must be None, 'fast' (register-resident float64 kernel, one problem per "
-                         "wave) or 'generic' (LDS kernel)")
+                         "wave), 'split' (the same over four waves, 641..1280 scans) or 'generic' (LDS kernel)")
+    flags = _lib.PB_FLAG_PP_SPLIT if force == "split" else _FORCE[force]
     cold = 0
     if W0 is None:
         W = torch.empty((V, N), dtype=torch.float64, device=dev)
@@ -813,9 +819,15 @@ def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=N
             Y.data_ptr(), _ld(Y), 1, W.data_ptr(), _ld(W), V, N, taps.data_ptr(), _ld(taps), taps.shape[1],
             steps.data_ptr(), lbda_scalar, lbda_dev.data_ptr() if lbda_dev is not None else None,
             betas.data_ptr(), int(n_iter), J.data_ptr() if J is not None else None, _ld(J) if J is not None else 0,
-            _STOP[stop], float(tol), int(wind), n_done.data_ptr(), _FORCE[force] | cold, _stream_ptr(dev))
+            _STOP[stop], float(tol), int(wind), n_done.data_ptr(), flags | cold, _stream_ptr(dev))
     _lib.check(rc, "pb_fista_solve_pp_d")
     return W, J, n_done
+
+
+def pp_split_supported(n_scans, n_taps, stop=None, wind=6):
+    """Whether :func:`fista_solve_pp_d` with ``force="split"`` carries this shape (``pb_fista_pp_split_supported``:
+    ``641 <= N <= 1280``, ``K <= 32``, the window rule at ``wind == 6``)."""
+    return bool(_lib.load().pb_fista_pp_split_supported(int(n_scans), int(n_taps), _STOP[stop], int(wind)))
 
 
 def fista_stats_pp(W, Y, taps):
@@ -968,7 +980,7 @@ def auto_lbda_solve_split(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, 
 
 
 def auto_lbda_solve_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                       outer_chunk=0, W0=None, want_trace=True):
+                       outer_chunk=0, W0=None, want_trace=True, _entry="pb_auto_lbda_pp_d"):
     """:func:`auto_lbda_solve` with one HRF and one step per voxel (``pb_auto_lbda_pp_d``): ``taps`` float64 CUDA
     ``(V, K)``, ``steps`` float64 ``(V,)``; the same limits (:func:`auto_lbda_supported`), the same return value."""
     Y = _rows(Y, torch.float64, "Y")
@@ -978,8 +990,17 @@ def auto_lbda_solve_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, w
     steps = torch.as_tensor(steps, dtype=torch.float64).to(Y.device).contiguous().ravel()
     if steps.numel() != Y.shape[0]:
         raise ValueError("steps must have one entry per voxel (%d)" % Y.shape[0])
-    return _auto_lbda_solve("pb_auto_lbda_pp_d", Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+    return _auto_lbda_solve(_entry, Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
                             outer_chunk, W0, want_trace)
+
+
+def auto_lbda_solve_split_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                             outer_chunk=0, W0=None, want_trace=True):
+    """:func:`auto_lbda_solve_pp` for series of ``641 <= N <= 1280`` scans (``pb_auto_lbda_split_pp_d``: one voxel per
+    workgroup of four waves; :func:`auto_lbda_split_supported` answers for its shapes): the same arguments, the same
+    return value.  Opt-in: :func:`auto_lbda_solve_pp` keeps its limit of 640 scans."""
+    return auto_lbda_solve_pp(Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0,
+                              want_trace, _entry="pb_auto_lbda_split_pp_d")
 
 
 def _auto_lbda_solve(entry, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0, want_trace):
@@ -987,7 +1008,7 @@ def _auto_lbda_solve(entry, Y, hrf, step, sigma, early_stopping, tol, wind, nb_i
     Y = _rows(Y, torch.float64, "Y")
     dev = Y.device
     V, N = Y.shape
-    pp = entry == "pb_auto_lbda_pp_d"              # hrf: CUDA (V, K), step: CUDA (V,)
+    pp = entry in ("pb_auto_lbda_pp_d", "pb_auto_lbda_split_pp_d")     # hrf: CUDA (V, K), step: CUDA (V,)
     taps = None if pp else _as_taps(hrf)
     nb_iter, nb_sub_iter = int(nb_iter), int(nb_sub_iter)
     if W0 is None:
