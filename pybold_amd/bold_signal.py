@@ -126,7 +126,9 @@ DISPATCH = os.environ.get("PYBOLD_AMD_DISPATCH", "ctypes")
 # host loop) or "device_split" (the same, and series of 641 .. 1 280 scans on the search with one voxel per workgroup of four
 # waves, `deconv_auto(engine="device_split")`; shapes neither carries keep the host loop).  1-D calls always keep the host
 # loop.  "device_split_pp": everything "device_split" does, and calls with one HRF per voxel (a 2-D `hrf`) of 641 .. 1 280
-# scans on `deconv_auto(engine="device_split_pp")`.  Initialised from the environment variable PYBOLD_AMD_AUTO_LBDA.
+# scans on `deconv_auto(engine="device_split_pp")`.  "device_long_hrf": everything "device" does, and HRFs of 33 .. 48 taps
+# (1-D or one per voxel) on series of up to 640 scans on `deconv_auto(engine="device_long_hrf")`.  Initialised from the
+# environment variable PYBOLD_AMD_AUTO_LBDA.
 AUTO_LBDA = os.environ.get("PYBOLD_AMD_AUTO_LBDA", "host")
 
 # Opt-in: the fixed-lambda solves with one HRF per voxel (a 2-D `hrf`: `deconv` with a `lbda`, and the inner solves of the
@@ -137,9 +139,25 @@ AUTO_LBDA = os.environ.get("PYBOLD_AMD_AUTO_LBDA", "host")
 PER_VOXEL_SPLIT = os.environ.get("PYBOLD_AMD_PP_SPLIT", "0") == "1"
 
 
+# Opt-in: the float64 fixed-lambda solves of `deconv` (1-D calls, the inner solves of the host-loop lambda search, a 2-D
+# `hrf`) run HRFs of 33 .. 48 taps on series of up to 640 scans on the one-wave register form with the taps in one VGPR pair
+# (`force="long_hrf"`) instead of the LDS kernel, where `solver.long_hrf_supported` says the shape is carried.  Off by
+# default: no call changes its kernel unless asked.  Initialised from the environment variable PYBOLD_AMD_LONG_HRF ("1" is on).
+LONG_HRF = os.environ.get("PYBOLD_AMD_LONG_HRF", "0") == "1"
+
+
+def _long_hrf_force(n, n_taps, stop, wind):
+    """``force`` of a float64 solve: ``"long_hrf"`` when ``LONG_HRF`` is on, the HRF has more than 32 taps (up to 32 the
+    default register form carries the call) and the shape is carried."""
+    return "long_hrf" if LONG_HRF and n_taps > 32 and solver.long_hrf_supported(n, n_taps, stop, wind) else None
+
+
 def _pv_force(n, n_taps, stop, wind):
-    """``force`` of a per-voxel-HRF solve: ``"split"`` when ``PER_VOXEL_SPLIT`` is on and the shape is carried."""
-    return "split" if PER_VOXEL_SPLIT and solver.pp_split_supported(n, n_taps, stop, wind) else None
+    """``force`` of a per-voxel-HRF solve: ``"split"`` when ``PER_VOXEL_SPLIT`` is on and the shape is carried,
+    ``"long_hrf"`` likewise under ``LONG_HRF``."""
+    if PER_VOXEL_SPLIT and solver.pp_split_supported(n, n_taps, stop, wind):
+        return "split"
+    return _long_hrf_force(n, n_taps, stop, wind)
 
 
 def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
@@ -160,10 +178,13 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
     """
     per_voxel = _per_voxel_hrf(y, hrf, "deconv")
     if lbda is None:
-        if AUTO_LBDA in ("device", "device_split", "device_split_pp") and _n_dim(y) == 2:
+        if AUTO_LBDA in ("device", "device_split", "device_split_pp", "device_long_hrf") and _n_dim(y) == 2:
             n_taps = int(_shape_of(hrf)[-1]) if per_voxel else np.size(hrf)
-            split = AUTO_LBDA != "device" and solver.auto_lbda_split_supported(_n_scans(y), n_taps, wind)
+            split = (AUTO_LBDA in ("device_split", "device_split_pp")
+                     and solver.auto_lbda_split_supported(_n_scans(y), n_taps, wind))
             engine = ("device" if solver.auto_lbda_supported(_n_scans(y), n_taps, wind)
+                      else "device_long_hrf" if (AUTO_LBDA == "device_long_hrf" and n_taps > 32
+                                                 and solver.auto_lbda_long_supported(_n_scans(y), n_taps, wind))
                       else "device_split" if split and not per_voxel
                       else "device_split_pp" if split and per_voxel and AUTO_LBDA == "device_split_pp"
                       else None)
@@ -197,9 +218,10 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
                                              tol=tol, wind=wind)
         X, Z = torch_ops.load().fista_outputs(W, torch.from_numpy(np.ascontiguousarray(hrf)).to(W.device))
     else:
+        stop = "window" if early_stopping else None
         W, J, n_done = solver.fista_solve(
-            Y, hrf, lbda, step, int(nb_iter), want_J=True,
-            stop="window" if early_stopping else None, tol=tol, wind=wind)
+            Y, hrf, lbda, step, int(nb_iter), want_J=True, stop=stop, tol=tol, wind=wind,
+            force=_long_hrf_force(n, hrf.size, stop, wind) if Y.dtype == torch.float64 else None)
         X, Z = solver.fista_outputs(W, hrf)
     return _deconv_results(Y, one_d, X, Z, W, J, n_done, verbose)
 
@@ -254,7 +276,10 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
             (``solver.auto_lbda_solve_split``: series of 641 .. 1 280 scans, HRFs of up to 32 taps, ``wind == 6`` --
             ``ValueError`` otherwise; ``"device"`` and ``"auto"`` do not reach it);
             "device_split_pp": the same with one HRF per voxel (``solver.auto_lbda_solve_split_pp``; a 2-D ``hrf`` is
-            required, the same limits -- ``ValueError`` otherwise; no other engine reaches it)
+            required, the same limits -- ``ValueError`` otherwise; no other engine reaches it);
+            "device_long_hrf": the one-wave device-resident solve for HRFs of 33 .. 48 taps (``solver.auto_lbda_solve_long`` /
+            ``solver.auto_lbda_solve_long_pp``: a 1-D or ``(V, K)`` ``hrf``, series of up to 640 scans, ``wind == 6`` --
+            ``ValueError`` otherwise; no other engine reaches it, ``"device"`` and ``"auto"`` keep their limit of 32 taps)
     hrf     1-D, or ``(V, K)`` beside a ``(V, N)`` batch: one HRF per voxel (``solver.auto_lbda_solve_pp`` on the device engine,
             the host loop on ``solver.fista_solve_pp_d``; ``"device_split"`` takes one HRF for all voxels, ``ValueError``;
             ``"device_split_pp"`` takes one per voxel)
@@ -265,9 +290,9 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     same input (lists for a 1-D ``y``; ``(n_outer, V)`` arrays padded with NaN for a batch, trimmed to the longest
     row's outer iterations; CUDA in -> ``x, z, diff_z`` CUDA); ``info`` holds ``alpha``, ``lbda`` (final, per
     voxel), ``n_outer``, ``n_inner`` (outer / summed inner iterations per voxel), ``sigma`` and ``engine``."""
-    if engine not in ("auto", "device", "host", "device_split", "device_split_pp"):
-        raise ValueError("deconv_auto: engine must be 'auto', 'device', 'host', 'device_split' or 'device_split_pp', got %r"
-                         % (engine,))
+    if engine not in ("auto", "device", "host", "device_split", "device_split_pp", "device_long_hrf"):
+        raise ValueError("deconv_auto: engine must be 'auto', 'device', 'host', 'device_split', 'device_split_pp' or "
+                         "'device_long_hrf', got %r" % (engine,))
     per_voxel = _per_voxel_hrf(y, hrf, "deconv_auto")
     n, n_taps = _n_scans(y), (int(_shape_of(hrf)[-1]) if per_voxel else int(np.size(hrf)))
     if engine == "device_split":
@@ -289,6 +314,11 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
             raise ValueError("deconv_auto(engine='device_split_pp'): the four-wave device-resident lambda search carries "
                              "series of 641..1280 scans, HRFs of up to 32 taps and wind = 6; this call has %d scans, %d taps, "
                              "wind = %d" % (n, n_taps, wind))
+    elif engine == "device_long_hrf":
+        if not (33 <= n_taps <= 48 and solver.auto_lbda_long_supported(n, n_taps, wind)):
+            raise ValueError("deconv_auto(engine='device_long_hrf'): the device-resident lambda search for long HRFs carries "
+                             "HRFs of 33..48 taps, series of up to 640 scans and wind = 6 (up to 32 taps: engine='device'); "
+                             "this call has %d scans, %d taps, wind = %d" % (n, n_taps, wind))
     elif engine != "host":
         if solver.auto_lbda_supported(n, n_taps, wind):
             engine = "device"
@@ -315,7 +345,8 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     if per_voxel:
         Y, T, one_d = _pv_to_device(y, hrf)
         V = Y.shape[0]
-        solve = solver.auto_lbda_solve_split_pp if engine == "device_split_pp" else solver.auto_lbda_solve_pp
+        solve = {"device_split_pp": solver.auto_lbda_solve_split_pp,
+                 "device_long_hrf": solver.auto_lbda_solve_long_pp}.get(engine, solver.auto_lbda_solve_pp)
         W, res = solve(Y, T, _pv_steps(T, n), sigma, early_stopping=early_stopping, tol=tol, wind=wind,
                        nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
         X, Z = solver.fista_outputs_pp(W, T)
@@ -331,7 +362,8 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     hrf = np.asarray(hrf, dtype=np.float64)
     H = ConvAndLinear(DiscretInteg(), hrf, dim_in=n, dim_out=n)
     step = 1.0 / (0.9 * spectral_radius_est(H, (n,)))
-    solve = solver.auto_lbda_solve_split if engine == "device_split" else solver.auto_lbda_solve
+    solve = {"device_split": solver.auto_lbda_solve_split,
+             "device_long_hrf": solver.auto_lbda_solve_long}.get(engine, solver.auto_lbda_solve)
     W, res = solve(Y, hrf, step, sigma, early_stopping=early_stopping, tol=tol, wind=wind,
                    nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
     X, Z = solver.fista_outputs(W, hrf)
@@ -422,7 +454,8 @@ def _deconv_auto_lbda(y, hrf, early_stopping, tol, wind, nb_iter, nb_sub_iter, v
         step = 1.0 / grad_lipschitz_cst
 
         def solve(lbda, W):
-            return solver.fista_solve(Y, hrf, lbda, step, int(nb_sub_iter), W0=W, stop=stop, tol=tol, wind=wind)
+            return solver.fista_solve(Y, hrf, lbda, step, int(nb_sub_iter), W0=W, stop=stop, tol=tol, wind=wind,
+                                      force=_long_hrf_force(n, hrf.size, stop, wind))
 
         def stats(W):
             return solver.fista_stats(W, Y, hrf)

@@ -75,6 +75,18 @@ inline int auto_split_outer_chunk(int V, int nb_sub_iter) {
   return (int)(c < 1 ? 1 : c);
 }
 
+// the same for the one-wave search with up to 48 taps (fista_exact_long.h): its register reports allow the residency of
+// auto_lbda_kernel, but a pass carries 48 taps for 32 (1.5x the multiply-adds, and two lane reads per tap and half): at that
+// kernel's budget its longest dispatch (0.16 s, profiles/auto_lbda_device.txt) would pass 0.25 s -- half the budget here
+// (measured: profiles/long_hrf.txt)
+constexpr int AUTO_LONG_LAUNCH_ITERS = 32768;
+inline int auto_long_outer_chunk(int V, int nb_sub_iter) {
+  const int64_t rounds = ((int64_t)V + AUTO_RESIDENT_WAVES - 1) / AUTO_RESIDENT_WAVES;
+  const int64_t per = (int64_t)(nb_sub_iter > 0 ? nb_sub_iter : 1) * (rounds > 0 ? rounds : 1);
+  const int64_t c = AUTO_LONG_LAUNCH_ITERS / per;
+  return (int)(c < 1 ? 1 : c);
+}
+
 constexpr int MAD_DAUB_NMAX = 8192;
 template <typename TY>
 int mad_daub_impl(const TY* y_dev, int64_t ldy, int V, int N, double c, double* sigma_dev, void* stream, const char* name) {
@@ -833,6 +845,24 @@ int pb_fista_solve(const float* y_dev, int64_t ldy, int y_rep, double* w_dev, in
                     J_dev, ldj, stop_mode, tol, wind, n_done_dev, flags, stream, nullptr, 0.0, work, len);
 }
 
+namespace {
+// PB_FLAG_LONG_HRF on pb_fista_solve_d / pb_fista_solve_pp_d: the entry of the 48-tap register form, or the error of a call
+// it does not carry (nothing is launched)
+int long_hrf_entry(const char* name, int N, int K, int stop_mode, int wind, unsigned flags, const ExactLongEntry** le) {
+  if (flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_FAST | PB_FLAG_PP_SPLIT))
+    return fail(PB_ERR_INVALID, "%s: PB_FLAG_LONG_HRF names the 48-tap register form; it excludes PB_FLAG_FORCE_GENERIC, PB_FLAG_FORCE_FAST and PB_FLAG_PP_SPLIT", name);
+  if (N > LONG_HRF_NMAX) return fail(PB_ERR_INVALID, "%s: PB_FLAG_LONG_HRF with N=%d outside 1..640 scans", name, N);
+  if (K > LONG_HRF_KMAX) return fail(PB_ERR_INVALID, "%s: PB_FLAG_LONG_HRF with K=%d outside 1..48 taps", name, K);
+  if (stop_mode == PB_STOP_WINDOW && wind != 6)
+    return fail(PB_ERR_INVALID, "%s: PB_FLAG_LONG_HRF with wind=%d (the 48-tap register form carries wind = 6)", name, wind);
+  *le = pick_exact_long(N, K, stop_mode, wind);
+  if (!*le) return fail(PB_ERR_INVALID, "%s: no 48-tap specialisation for N=%d K=%d", name, N, K);
+  return PB_OK;
+}
+}  // namespace
+
+int pb_fista_long_hrf_supported(int N, int K, int stop_mode, int wind) { return pick_exact_long(N, K, stop_mode, wind) ? 1 : 0; }
+
 int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw,
                      int P, int N, const double* taps_host, const double* taps_dev, int K,
                      double step, double lbda, const double* lbda_dev, const double* betas_dev,
@@ -848,6 +878,21 @@ int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
     return fail(PB_ERR_INVALID, "pb_fista_solve_d: unknown stop_mode %d", stop_mode);
   if (stop_mode == PB_STOP_WINDOW && wind < 2)
     return fail(PB_ERR_INVALID, "pb_fista_solve_d: wind must be >= 2");
+  if (flags & PB_FLAG_LONG_HRF) {               // opt-in: HRFs of up to 48 taps on the one-wave register form, or an error
+    const ExactLongEntry* le = nullptr;
+    const int rc = long_hrf_entry("pb_fista_solve_d", N, K, stop_mode, wind, flags, &le);
+    if (rc != PB_OK) return rc;
+    if (P == 0) return PB_OK;
+    if (!y_dev || !w_dev || !taps_host || (n_iter > 0 && !betas_dev))
+      return fail(PB_ERR_INVALID, "pb_fista_solve_d: NULL pointer (PB_FLAG_LONG_HRF reads taps_host)");
+    if (P > (1 << 25)) return fail(PB_ERR_INVALID, "pb_fista_solve_d: more than 2^25 problems per launch");
+    pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, step, lbda, lbda_dev, betas_dev, stop_mode, tol,
+                                 n_done_dev, flags);
+    a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj;
+    if (le->fn(a, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
+      return fail(PB_ERR_INVALID, "pb_fista_solve_d: launch rejected");
+    return check_launch("fista_exact_long_kernel");
+  }
   // register-resident float64 form (one problem per wave) when the shape has an entry and
   // the host copy of the taps is given; the window rule there is the reference default wind = 6
   // (one problem per wave up to 640 scans, one per workgroup of four waves up to 1 280: fista_exact_split.h)
@@ -899,6 +944,22 @@ int pb_fista_solve_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_d
   if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW)
     return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: unknown stop_mode %d", stop_mode);
   if (stop_mode == PB_STOP_WINDOW && wind < 2) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: wind must be >= 2");
+  if (flags & PB_FLAG_LONG_HRF) {               // opt-in: HRFs of up to 48 taps on the one-wave register form, or an error
+    const ExactLongEntry* le = nullptr;
+    const int rc = long_hrf_entry("pb_fista_solve_pp_d", N, K, stop_mode, wind, flags, &le);
+    if (rc != PB_OK) return rc;
+    if (P == 0) return PB_OK;
+    if (!y_dev || !w_dev || !taps_dev || !step_dev || (n_iter > 0 && !betas_dev))
+      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: NULL pointer");
+    if (P > (1 << 25)) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: more than 2^25 problems per launch");
+    pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, stop_mode, tol,
+                                 n_done_dev, flags);
+    a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj; a.wind = wind;
+    a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = 0;
+    if (le->fn_pp(a, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
+      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: launch rejected");
+    return check_launch("fista_exact_long_pp_kernel");
+  }
   const ExactSplitPPEntry* se = nullptr;
   if (flags & PB_FLAG_PP_SPLIT) {
     if (flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_FAST))
@@ -955,18 +1016,39 @@ int64_t pb_auto_lbda_work_len(int V) { return (int64_t)pb::AUTO_STATE * (V > 0 ?
 namespace {
 // pb_auto_lbda_d (split = false: one voxel per wave, up to 640 scans) and pb_auto_lbda_split_d (one voxel per workgroup of
 // four waves, 641 .. 1 280 scans): one validation in one order, one launch protocol; the kernels and the library's chunk differ
-int auto_lbda_impl(const char* name, bool split, const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+enum AutoForm { AUTO_ONE_WAVE = 0, AUTO_FOUR_WAVES = 1, AUTO_LONG_HRF = 2 };   // (the long-HRF form: one wave, up to 48 taps, opt-in)
+inline const char* auto_kernel_name(int form, bool pp, bool final_solve) {
+  static const char* const names[3][2][2] = {
+      {{"auto_lbda_kernel", "auto_lbda_kernel(final solve)"}, {"auto_lbda_pp_kernel", "auto_lbda_pp_kernel(final solve)"}},
+      {{"auto_lbda_split_kernel", "auto_lbda_split_kernel(final solve)"}, {"auto_lbda_split_pp_kernel", "auto_lbda_split_pp_kernel(final solve)"}},
+      {{"auto_lbda_long_kernel", "auto_lbda_long_kernel(final solve)"}, {"auto_lbda_long_pp_kernel", "auto_lbda_long_pp_kernel(final solve)"}}};
+  return names[form][pp][final_solve];
+}
+inline int auto_form_chunk(int form, int V, int nb_sub_iter) {
+  return form == AUTO_FOUR_WAVES ? auto_split_outer_chunk(V, nb_sub_iter)
+         : form == AUTO_LONG_HRF ? auto_long_outer_chunk(V, nb_sub_iter) : auto_outer_chunk(V, nb_sub_iter);
+}
+int auto_lbda_impl(const char* name, int form, const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
                    const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
                    int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
                    double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
                    int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
   if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "%s: bad size (V=%d N=%d K=%d)", name, V, N, K);
   if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "%s: wind=%d (the device-resident search carries wind = 6)", name, wind);
+  const bool split = form == AUTO_FOUR_WAVES;
+  const int k_max = form == AUTO_LONG_HRF ? LONG_HRF_KMAX : 32;
   if (!split && N > 640) return fail(PB_ERR_INVALID, "%s: N=%d exceeds 640 scans", name, N);
   if (split && (N < 641 || N > 1280)) return fail(PB_ERR_INVALID, "%s: N=%d outside 641..1280 scans", name, N);
-  if (K > 32) return fail(PB_ERR_INVALID, "%s: K=%d exceeds 32 taps", name, K);
-  const ExactEntry* ae = split ? pick_auto_split(N, K) : pick_auto(N, K);
-  if (!ae || !ae->fn_auto) return fail(PB_ERR_INVALID, "%s: no specialisation for N=%d K=%d", name, N, K);
+  if (K > k_max) return fail(PB_ERR_INVALID, "%s: K=%d exceeds %d taps", name, K, k_max);
+  auto_launch_fn fn_auto = nullptr;
+  if (form == AUTO_LONG_HRF) {
+    const ExactLongEntry* le = pick_exact_long(N, K, PB_STOP_WINDOW, wind);
+    fn_auto = le ? le->fn_auto : nullptr;
+  } else {
+    const ExactEntry* ae = split ? pick_auto_split(N, K) : pick_auto(N, K);
+    fn_auto = ae ? ae->fn_auto : nullptr;
+  }
+  if (!fn_auto) return fail(PB_ERR_INVALID, "%s: no specialisation for N=%d K=%d", name, N, K);
   if (nb_iter < 1 || nb_sub_iter < 0 || outer_chunk < 0)
     return fail(PB_ERR_INVALID, "%s: nb_iter >= 1, nb_sub_iter >= 0 and outer_chunk >= 0 are required (%d, %d, %d)", name,
                 nb_iter, nb_sub_iter, outer_chunk);
@@ -985,16 +1067,16 @@ int auto_lbda_impl(const char* name, bool split, const double* y_dev, int64_t ld
   a.cold = cold ? 1 : 0; a.nb_sub_iter = nb_sub_iter; a.step = step; a.tol = tol;
   a.betas = betas_dev; a.sigma = sigma_dev; a.R = R_dev; a.G = G_dev; a.J = J_dev; a.ldt = ldt;
   a.alpha_out = alpha_dev; a.lbda_out = lbda_dev; a.n_outer = n_outer_dev; a.n_inner = n_inner_dev; a.work = work_dev;
-  const int chunk = outer_chunk > 0 ? outer_chunk : (split ? auto_split_outer_chunk(V, nb_sub_iter) : auto_outer_chunk(V, nb_sub_iter));
+  const int chunk = outer_chunk > 0 ? outer_chunk : auto_form_chunk(form, V, nb_sub_iter);
   for (int i0 = 0; i0 < nb_iter; i0 += chunk) {        // outer iterations [i0, i1) of the voxels still searching
     a.init = i0 == 0; a.i0 = i0; a.i1 = (nb_iter - i0 < chunk) ? nb_iter : i0 + chunk; a.final_solve = 0;
-    ae->fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
-    const int rc = check_launch(split ? "auto_lbda_split_kernel" : "auto_lbda_kernel");
+    fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
+    const int rc = check_launch(auto_kernel_name(form, false, false));
     if (rc != PB_OK) return rc;
   }
   a.init = 0; a.i0 = a.i1 = nb_iter; a.final_solve = 1;   // the last inner solve of every voxel, then the outputs
-  ae->fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
-  return check_launch(split ? "auto_lbda_split_kernel(final solve)" : "auto_lbda_kernel(final solve)");
+  fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
+  return check_launch(auto_kernel_name(form, false, true));
 }
 }  // namespace
 
@@ -1003,7 +1085,7 @@ int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw,
                    int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
                    double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
                    int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
-  return auto_lbda_impl("pb_auto_lbda_d", false, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev, sigma_dev,
+  return auto_lbda_impl("pb_auto_lbda_d", AUTO_ONE_WAVE, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev, sigma_dev,
                         early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt, alpha_dev, lbda_dev,
                         n_outer_dev, n_inner_dev, work_dev, work_len, stream);
 }
@@ -1013,7 +1095,7 @@ int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw,
 // (split = true: pb_auto_lbda_split_pp_d, one voxel per workgroup of four waves, 641 .. 1 280 scans, with the limits and the
 // chunk of pb_auto_lbda_split_d)
 namespace {
-int auto_lbda_pp_impl(const char* name, bool split, const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+int auto_lbda_pp_impl(const char* name, int form, const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
                       const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
                       const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
                       int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
@@ -1021,11 +1103,16 @@ int auto_lbda_pp_impl(const char* name, bool split, const double* y_dev, int64_t
                       void* stream) {
   if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "%s: bad size (V=%d N=%d K=%d)", name, V, N, K);
   if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "%s: wind=%d (the device-resident search carries wind = 6)", name, wind);
+  const bool split = form == AUTO_FOUR_WAVES;
+  const int k_max = form == AUTO_LONG_HRF ? LONG_HRF_KMAX : 32;
   if (!split && N > 640) return fail(PB_ERR_INVALID, "%s: N=%d exceeds 640 scans", name, N);
   if (split && (N < 641 || N > 1280)) return fail(PB_ERR_INVALID, "%s: N=%d outside 641..1280 scans", name, N);
-  if (K > 32) return fail(PB_ERR_INVALID, "%s: K=%d exceeds 32 taps", name, K);
+  if (K > k_max) return fail(PB_ERR_INVALID, "%s: K=%d exceeds %d taps", name, K, k_max);
   auto_pp_launch_fn fn_auto = nullptr;
-  if (split) {
+  if (form == AUTO_LONG_HRF) {
+    const ExactLongEntry* le = pick_exact_long(N, K, PB_STOP_WINDOW, wind);
+    fn_auto = le ? le->fn_auto_pp : nullptr;
+  } else if (split) {
     const ExactSplitPPEntry* se = pick_auto_split(N, K) ? pick_exact_split_pp(N, K, PB_STOP_WINDOW, wind) : nullptr;
     fn_auto = se ? se->fn_auto : nullptr;
   } else {
@@ -1052,16 +1139,16 @@ int auto_lbda_pp_impl(const char* name, bool split, const double* y_dev, int64_t
   a.betas = betas_dev; a.sigma = sigma_dev; a.R = R_dev; a.G = G_dev; a.J = J_dev; a.ldt = ldtr;
   a.alpha_out = alpha_dev; a.lbda_out = lbda_dev; a.n_outer = n_outer_dev; a.n_inner = n_inner_dev; a.work = work_dev;
   a.taps_pp = taps_dev; a.ld_taps = ldt; a.step_vec = step_dev; a.K = K;
-  const int chunk = outer_chunk > 0 ? outer_chunk : (split ? auto_split_outer_chunk(V, nb_sub_iter) : auto_outer_chunk(V, nb_sub_iter));
+  const int chunk = outer_chunk > 0 ? outer_chunk : auto_form_chunk(form, V, nb_sub_iter);
   for (int i0 = 0; i0 < nb_iter; i0 += chunk) {        // outer iterations [i0, i1) of the voxels still searching
     a.init = i0 == 0; a.i0 = i0; a.i1 = (nb_iter - i0 < chunk) ? nb_iter : i0 + chunk; a.final_solve = 0;
     if (fn_auto(a, early_stopping != 0, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
-    const int rc = check_launch(split ? "auto_lbda_split_pp_kernel" : "auto_lbda_pp_kernel");
+    const int rc = check_launch(auto_kernel_name(form, true, false));
     if (rc != PB_OK) return rc;
   }
   a.init = 0; a.i0 = a.i1 = nb_iter; a.final_solve = 1;   // the last inner solve of every voxel, then the outputs
   if (fn_auto(a, early_stopping != 0, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
-  return check_launch(split ? "auto_lbda_split_pp_kernel(final solve)" : "auto_lbda_pp_kernel(final solve)");
+  return check_launch(auto_kernel_name(form, true, true));
 }
 }  // namespace
 
@@ -1071,7 +1158,7 @@ int pb_auto_lbda_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t l
                       int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
                       double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
                       void* stream) {
-  return auto_lbda_pp_impl("pb_auto_lbda_pp_d", false, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev, betas_dev,
+  return auto_lbda_pp_impl("pb_auto_lbda_pp_d", AUTO_ONE_WAVE, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev, betas_dev,
                            sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldtr,
                            alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
 }
@@ -1082,9 +1169,34 @@ int pb_auto_lbda_split_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int
                             int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
                             double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
                             void* stream) {
-  return auto_lbda_pp_impl("pb_auto_lbda_split_pp_d", true, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev, betas_dev,
+  return auto_lbda_pp_impl("pb_auto_lbda_split_pp_d", AUTO_FOUR_WAVES, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev, betas_dev,
                            sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldtr,
                            alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
+}
+
+int pb_auto_lbda_long_supported(int N, int K, int wind) {
+  return (wind == pb::AUTO_WIND && pick_exact_long(N, K, PB_STOP_WINDOW, wind)) ? 1 : 0;
+}
+
+int pb_auto_lbda_long_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                        const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
+                        int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
+                        double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
+                        int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
+  return auto_lbda_impl("pb_auto_lbda_long_d", AUTO_LONG_HRF, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev,
+                        sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt, alpha_dev,
+                        lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
+}
+
+int pb_auto_lbda_long_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                           const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
+                           const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
+                           int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
+                           double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
+                           void* stream) {
+  return auto_lbda_pp_impl("pb_auto_lbda_long_pp_d", AUTO_LONG_HRF, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev,
+                           betas_dev, sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev,
+                           ldtr, alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
 }
 
 int pb_auto_lbda_split_supported(int N, int K, int wind) { return (wind == pb::AUTO_WIND && pick_auto_split(N, K)) ? 1 : 0; }
@@ -1094,7 +1206,7 @@ int pb_auto_lbda_split_d(const double* y_dev, int64_t ldy, double* w_dev, int64_
                          int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
                          double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
                          int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
-  return auto_lbda_impl("pb_auto_lbda_split_d", true, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev, sigma_dev,
+  return auto_lbda_impl("pb_auto_lbda_split_d", AUTO_FOUR_WAVES, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev, sigma_dev,
                         early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt, alpha_dev, lbda_dev,
                         n_outer_dev, n_inner_dev, work_dev, work_len, stream);
 }

@@ -13,6 +13,7 @@
 #include "fista_auto.h"
 #include "fista_auto_split.h"
 #include "fista_exact_pp.h"
+#include "fista_exact_long.h"
 #include "fista_mfma.h"
 #include "fista_mfma2.h"
 #include "fista_mfma4.h"
@@ -260,6 +261,42 @@ const ExactSplitPPEntry* pick_exact_split_pp(int N, int K, int stop_mode, int wi
   if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return nullptr;
   if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
   return N > 640 ? pick_cheapest(kExactSplitPP, N, K, 64 * pb::SPLIT_WAVES) : nullptr;
+}
+
+// ... and HRFs of up to 48 taps with the taps in one VGPR pair of the wave (fista_exact_long.h): the pairs of
+// exact_long_table.inc.  OPT-IN: no picker above falls through to it -- PB_FLAG_LONG_HRF, pb_auto_lbda_long_d and
+// pb_auto_lbda_long_pp_d name it
+struct ExactLongEntry {
+  int S, KT;
+  exact_launch_fn fn;
+  auto_launch_fn fn_auto;
+  exact_pp_launch_fn fn_pp;
+  auto_pp_launch_fn fn_auto_pp;
+};
+}  // namespace
+namespace pb {
+#define PB_EXACT_LONG(S, KT)                                                                                  \
+  extern template int launch_exact_long<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t); \
+  extern template int launch_auto_long<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);        \
+  extern template int launch_exact_long_pp<S, KT>(const FistaArgs&, bool, int, hipStream_t);                  \
+  extern template int launch_auto_long_pp<S, KT>(const AutoArgsPP&, bool, hipStream_t);
+#include "exact_long_table.inc"
+#undef PB_EXACT_LONG
+}  // namespace pb
+namespace {
+#define PB_EXACT_LONG(S, KT) \
+  {S, KT, &pb::launch_exact_long<S, KT>, &pb::launch_auto_long<S, KT>, &pb::launch_exact_long_pp<S, KT>, &pb::launch_auto_long_pp<S, KT>},
+const ExactLongEntry kExactLong[] = {
+#include "exact_long_table.inc"
+};
+#undef PB_EXACT_LONG
+constexpr int LONG_HRF_NMAX = 640, LONG_HRF_KMAX = 48;
+// the window rule is wind = 6
+const ExactLongEntry* pick_exact_long(int N, int K, int stop_mode, int wind) {
+  if (N < 1 || N > LONG_HRF_NMAX || K < 1 || K > LONG_HRF_KMAX) return nullptr;
+  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return nullptr;
+  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
+  return pick_cheapest(kExactLong, N, K, 64);
 }
 
 template <int S, int KT>

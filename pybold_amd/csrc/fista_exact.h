@@ -25,9 +25,14 @@
 
 namespace pb {
 
+// The taps of a pass are read through a HOLDER: any type with `template <int m> double tap() const`.  TapsD keeps them
+// where the by-value kernel argument puts them (scalar registers: 32 float64 taps fill the scalar file); TapsLane
+// (fista_exact_long.h) keeps up to 64 of them in one VGPR pair of the wave.
 template <int KT>
 struct TapsD {
   double h[KT];
+  template <int m>
+  __host__ __device__ __forceinline__ double tap() const { return h[m]; }
 };
 
 template <int KT>
@@ -134,17 +139,18 @@ __device__ __forceinline__ void exact_window_above(const double (&r)[S], double 
 }
 
 // r = (h * z - y) on the samples of the series from the window Z of z: own samples at [H, H+S), halo below them
-template <int S, int KT>
+template <int S, int KT, class TAPS>
 __device__ __forceinline__ void exact_fir_residual(const double (&Z)[KT - 1 + S], const double (&y)[S], const double (&mk)[S],
-                                                   const TapsD<KT>& taps, double (&r)[S]) {
+                                                   const TAPS& taps, double (&r)[S]) {
   constexpr int H = KT - 1;
   // ---- r = h * z - y -------------------------------------------------------
   static_for<0, S>([&](auto jc) { r[decltype(jc)::value] = -y[decltype(jc)::value]; });
   static_for<0, KT>([&](auto mc) {          // tap-major: S independent chains
     constexpr int m = decltype(mc)::value;
+    const double hm = taps.template tap<m>();
     static_for<0, S>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      r[j] = fma(taps.h[m], Z[H + j - m], r[j]);
+      r[j] = fma(hm, Z[H + j - m], r[j]);
     });
   });
 #pragma unroll
@@ -152,15 +158,16 @@ __device__ __forceinline__ void exact_fir_residual(const double (&Z)[KT - 1 + S]
 }
 
 // g = K^T r from the window R of r (own samples at [0, S), halo above them), summed from the lane's last sample down
-template <int S, int KT>
-__device__ __forceinline__ void exact_corr_suffix(const double (&R)[S + KT - 1], const TapsD<KT>& taps, double (&g)[S]) {
+template <int S, int KT, class TAPS>
+__device__ __forceinline__ void exact_corr_suffix(const double (&R)[S + KT - 1], const TAPS& taps, double (&g)[S]) {
 #pragma unroll
   for (int j = 0; j < S; ++j) g[j] = 0.0;
   static_for<0, KT>([&](auto mc) {
     constexpr int m = decltype(mc)::value;
+    const double hm = taps.template tap<m>();
     static_for<0, S>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      g[j] = fma(taps.h[m], R[j + m], g[j]);
+      g[j] = fma(hm, R[j + m], g[j]);
     });
   });
 #pragma unroll
@@ -222,9 +229,9 @@ __device__ __forceinline__ void exact_update(const double (&g)[S], double (&w)[S
 // first alone), on the residual the forward half returns.
 
 // forward half: z = cumsum(w), x = h * z, r = (x - y) on the samples of the series (0 on the padding)
-template <int S, int KT>
+template <int S, int KT, class TAPS>
 __device__ __forceinline__ void exact_forward(const double (&w)[S], const double (&y)[S], const double (&mk)[S],
-                                              const TapsD<KT>& taps, double (&r)[S]) {
+                                              const TAPS& taps, double (&r)[S]) {
   constexpr int H = KT - 1;
   // ---- z = cumsum(w) ----------------------------------------------------
   double z[S];
@@ -243,8 +250,8 @@ __device__ __forceinline__ void exact_forward(const double (&w)[S], const double
 
 // backward half: g = revcumsum(K^T r), gradient step, prox, momentum; with a stop rule (STOP 1: _loops_deconv, 2: window,
 // wind = 6) the two wave-wide sums of its criterion come back in num / den (and the window state moves on one iteration)
-template <int S, int KT, int STOP>
-__device__ __forceinline__ void exact_backward(const double (&r)[S], double (&w)[S], const TapsD<KT>& taps, double nstep,
+template <int S, int KT, int STOP, class TAPS>
+__device__ __forceinline__ void exact_backward(const double (&r)[S], double (&w)[S], const TAPS& taps, double nstep,
                                                double th, const double* beta_k, double (&uprev)[STOP == 2 ? S : 1],
                                                double (&d1)[STOP == 2 ? S : 1], double (&d2)[STOP == 2 ? S : 1],
                                                double (&d3)[STOP == 2 ? S : 1], double& num, double& den) {

@@ -249,7 +249,10 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
           float64 CUDA ``(V, N)``: float64 end to end (``pb_fista_solve_d``: register-resident
           kernels for K <= 32 -- one problem per wave for N <= 640, one per workgroup of four
           waves for N <= 1280 --, else the LDS kernel; :func:`which_kernel_f64`), the
-          reference's arithmetic -- what the 1-D calls of the API use
+          reference's arithmetic -- what the 1-D calls of the API use.  ``force="long_hrf"`` (opt-in,
+          ``PB_FLAG_LONG_HRF``): the one-wave register form for HRFs of up to 48 taps, ``N <= 640``, window rule at
+          ``wind == 6`` -- :func:`long_hrf_supported`; any other shape is an error.  Without it 33+ taps run on the
+          LDS kernel
     hrf   1-D array of K taps (host)
     lbda  scalar, or array/tensor of ``V * y_rep`` per-problem values
     step  ``1 / L``
@@ -266,6 +269,8 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
         raise ValueError("force='split' names the four-wave form with one HRF per problem: fista_solve_pp_d only")
     lib = _lib.load()
     f64 = torch.is_tensor(Y) and Y.dtype == torch.float64
+    if force == "long_hrf" and not f64:
+        raise ValueError("force='long_hrf' names the float64 register form for HRFs of up to 48 taps: float64 Y only")
     Y = _rows(Y, torch.float64 if f64 else torch.float32, "Y")
     dev = Y.device
     V, N = Y.shape
@@ -299,9 +304,11 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
         J.fill_(float("nan"))
     n_done = torch.empty((P,), dtype=torch.int32, device=dev)
     if f64:
-        if force not in (None, "generic", "fast"):
+        if force not in (None, "generic", "fast", "long_hrf"):
             raise ValueError("float64 y: force must be None, 'fast' (register-resident float64 "
-                             "kernel, one problem per wave) or 'generic' (LDS kernel)")
+                             "kernel, one problem per wave), 'generic' (LDS kernel) or 'long_hrf' (the register form "
+                             "for HRFs of up to 48 taps, up to 640 scans)")
+        flags = _lib.PB_FLAG_LONG_HRF if force == "long_hrf" else _FORCE[force]
         with torch.cuda.device(dev):
             rc = lib.pb_fista_solve_d(
                 Y.data_ptr(), _ld(Y), int(y_rep), W.data_ptr(), _ld(W), P, N,
@@ -309,7 +316,7 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
                 lbda_dev.data_ptr() if lbda_dev is not None else None,
                 betas.data_ptr(), int(n_iter),
                 J.data_ptr() if J is not None else None, _ld(J) if J is not None else 0,
-                _STOP[stop], float(tol), int(wind), n_done.data_ptr(), _FORCE[force] | cold,
+                _STOP[stop], float(tol), int(wind), n_done.data_ptr(), flags | cold,
                 _stream_ptr(dev))
         _lib.check(rc, "pb_fista_solve_d")
         return W, J, n_done
@@ -781,6 +788,9 @@ def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=N
            | "split" (opt-in, ``PB_FLAG_PP_SPLIT``: one problem per workgroup of four waves, ``641 <= N <= 1280``,
            ``K <= 32``, window rule at ``wind == 6`` -- :func:`pp_split_supported`; any other shape is an error.
            Without it such series run on the LDS kernel)
+           | "long_hrf" (opt-in, ``PB_FLAG_LONG_HRF``: one problem per wave, ``N <= 640``, ``K <= 48``, window rule at
+           ``wind == 6`` -- :func:`long_hrf_supported`; any other shape is an error.  Without it 33+ taps run on the
+           LDS kernel)
     Returns ``(W float64 (V, N), J float64 (V, n_iter) or None, n_done int32 (V,))``."""
     lib = _lib.load()
     Y = _rows(Y, torch.float64, "Y")
@@ -792,10 +802,11 @@ def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=N
     steps = torch.as_tensor(steps, dtype=torch.float64).to(dev).contiguous().ravel()
     if steps.numel() != V:
         raise ValueError("steps must have one entry per voxel (%d)" % V)
-    if force not in (None, "generic", "fast", "split"):
+    if force not in (None, "generic", "fast", "split", "long_hrf"):
         raise ValueError("float64 y: force must be None, 'fast' (register-resident float64 kernel, one problem per "
-                         "wave), 'split' (the same over four waves, 641..1280 scans) or 'generic' (LDS kernel)")
-    flags = _lib.PB_FLAG_PP_SPLIT if force == "split" else _FORCE[force]
+                         "wave), 'split' (the same over four waves, 641..1280 scans), 'generic' (LDS kernel) or "
+                         "'long_hrf' (one problem per wave, HRFs of up to 48 taps)")
+    flags = {"split": _lib.PB_FLAG_PP_SPLIT, "long_hrf": _lib.PB_FLAG_LONG_HRF}.get(force, _FORCE.get(force, 0))
     cold = 0
     if W0 is None:
         W = torch.empty((V, N), dtype=torch.float64, device=dev)
@@ -828,6 +839,12 @@ def pp_split_supported(n_scans, n_taps, stop=None, wind=6):
     """Whether :func:`fista_solve_pp_d` with ``force="split"`` carries this shape (``pb_fista_pp_split_supported``:
     ``641 <= N <= 1280``, ``K <= 32``, the window rule at ``wind == 6``)."""
     return bool(_lib.load().pb_fista_pp_split_supported(int(n_scans), int(n_taps), _STOP[stop], int(wind)))
+
+
+def long_hrf_supported(n_scans, n_taps, stop=None, wind=6):
+    """Whether :func:`fista_solve` (float64 ``Y``) and :func:`fista_solve_pp_d` with ``force="long_hrf"`` carry this
+    shape (``pb_fista_long_hrf_supported``: ``N <= 640``, ``K <= 48``, the window rule at ``wind == 6``)."""
+    return bool(_lib.load().pb_fista_long_hrf_supported(int(n_scans), int(n_taps), _STOP[stop], int(wind)))
 
 
 def fista_stats_pp(W, Y, taps):
@@ -955,6 +972,12 @@ def auto_lbda_split_supported(n_scans, n_taps, wind=6):
     return bool(_lib.load().pb_auto_lbda_split_supported(int(n_scans), int(n_taps), int(wind)))
 
 
+def auto_lbda_long_supported(n_scans, n_taps, wind=6):
+    """Whether :func:`auto_lbda_solve_long` and :func:`auto_lbda_solve_long_pp` carry this shape (``N <= 640``,
+    ``K <= 48``, ``wind == 6``)."""
+    return bool(_lib.load().pb_auto_lbda_long_supported(int(n_scans), int(n_taps), int(wind)))
+
+
 def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
                     outer_chunk=0, W0=None, want_trace=True):
     """The noise-driven lambda search of ``deconv(lbda=None)`` (pybold/bold_signal.py:99-214) for every row of ``Y``
@@ -976,6 +999,15 @@ def auto_lbda_solve_split(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, 
     """:func:`auto_lbda_solve` for series of ``641 <= N <= 1280`` scans (``pb_auto_lbda_split_d``: one voxel per
     workgroup of four waves): the same arguments, the same return value."""
     return _auto_lbda_solve("pb_auto_lbda_split_d", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+                            outer_chunk, W0, want_trace)
+
+
+def auto_lbda_solve_long(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                         outer_chunk=0, W0=None, want_trace=True):
+    """:func:`auto_lbda_solve` for HRFs of up to 48 taps (``pb_auto_lbda_long_d``: one voxel per wave, the taps in one
+    VGPR pair; :func:`auto_lbda_long_supported`): the same arguments, the same return value; with ``K <= 32`` the same
+    bits.  Opt-in: :func:`auto_lbda_solve` keeps its limit of 32 taps."""
+    return _auto_lbda_solve("pb_auto_lbda_long_d", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
                             outer_chunk, W0, want_trace)
 
 
@@ -1003,12 +1035,21 @@ def auto_lbda_solve_split_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0
                               want_trace, _entry="pb_auto_lbda_split_pp_d")
 
 
+def auto_lbda_solve_long_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                            outer_chunk=0, W0=None, want_trace=True):
+    """:func:`auto_lbda_solve_pp` for HRFs of up to 48 taps (``pb_auto_lbda_long_pp_d``;
+    :func:`auto_lbda_long_supported` answers for its shapes): the same arguments, the same return value.  Opt-in:
+    :func:`auto_lbda_solve_pp` keeps its limit of 32 taps."""
+    return auto_lbda_solve_pp(Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0,
+                              want_trace, _entry="pb_auto_lbda_long_pp_d")
+
+
 def _auto_lbda_solve(entry, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0, want_trace):
     lib = _lib.load()
     Y = _rows(Y, torch.float64, "Y")
     dev = Y.device
     V, N = Y.shape
-    pp = entry in ("pb_auto_lbda_pp_d", "pb_auto_lbda_split_pp_d")     # hrf: CUDA (V, K), step: CUDA (V,)
+    pp = entry in ("pb_auto_lbda_pp_d", "pb_auto_lbda_split_pp_d", "pb_auto_lbda_long_pp_d")     # hrf: CUDA (V, K), step: CUDA (V,)
     taps = None if pp else _as_taps(hrf)
     nb_iter, nb_sub_iter = int(nb_iter), int(nb_sub_iter)
     if W0 is None:

@@ -3,6 +3,7 @@ builds, from the ISA listings `make build/exact_5_32.s build/exact_10_32.s [buil
 pybold_amd/csrc/build (hipcc for gfx950, no GPU needed):
 
     python tools/exact_core_isa.py <dir with the parent's exact_*.s / .res> <dir with this tree's> > profiles/exact_core_isa.txt
+    python tools/exact_core_isa.py <parent's dir> <this tree's dir> exact_5_32 exactpp_10_32 autosplit_5_32 ...   (listings by name)
 
 Per kernel: the resource report, the instruction count, the opcode histogram's differences, and whether the instruction
 text is identical / identical up to register names / identical as a multiset (scheduling order only)."""
@@ -45,9 +46,14 @@ def anonymise(ins):
 
 def main():
     old, new = sys.argv[1], sys.argv[2]
-    print("tools/exact_core_isa.py: fista_exact_kernel of this tree (pass body in exact_forward / exact_backward, shared with")
-    print("auto_lbda_kernel) against a build of the parent commit.  hipcc for gfx950, no GPU.\n")
-    for name in ("exact_5_32", "exact_10_32", "auto_5_32", "auto_10_32"):
+    names = sys.argv[3:]
+    if names:
+        print("tools/exact_core_isa.py: the kernels of %s of this tree against a build of the parent commit." % ", ".join(names))
+        print("hipcc for gfx950, no GPU.\n")
+    else:
+        print("tools/exact_core_isa.py: fista_exact_kernel of this tree (pass body in exact_forward / exact_backward, shared with")
+        print("auto_lbda_kernel) against a build of the parent commit.  hipcc for gfx950, no GPU.\n")
+    for name in names or ("exact_5_32", "exact_10_32", "auto_5_32", "auto_10_32"):
         if name.startswith("auto") and not all(os.path.exists(os.path.join(d, name + ".s")) for d in (old, new)):
             continue
         ko, kn = kernels(os.path.join(old, name + ".s")), kernels(os.path.join(new, name + ".s"))

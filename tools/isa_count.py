@@ -14,7 +14,7 @@ def kernels(path):
             continue
         if name is not None:
             body.append(line.rstrip())
-            if line.strip().startswith("s_endpgm"):
+            if line.startswith(".Lfunc_end"):       # (not the first s_endpgm: a kernel may leave early in its prologue)
                 yield name, body
                 name = None
 
@@ -40,6 +40,8 @@ def classify(op):
     if op.startswith("v_pk_"): return "v_pk_other"
     if "dpp" in op: return "dpp"
     if op.endswith("_f64") or "_f64_" in op: return "f64"
+    if op.startswith(("v_readlane", "v_writelane")): return op.split("_b32")[0]
+    if op.startswith("v_accvgpr"): return "v_accvgpr"
     if op.startswith("v_cvt"): return "cvt"
     if op.startswith("v_cndmask"): return "cndmask"
     if op.startswith("v_mov"): return "v_mov"
