@@ -192,6 +192,8 @@ int pb_fista_plan_ex(int N, int K, int P, int stop_mode, int wind, unsigned flag
  *   641 .. 1280  <= 32     ... the same search, opt-in by name:                                                        auto_lbda_split_kernel, one voxel per workgroup of four waves (pb_auto_lbda_split_d)
  *   <= 640       <= 48     float64 end to end with up to 48 taps, OPT-IN by name (any stop rule, wind 6; shared HRF or one per problem):   fista_exact_long_kernel / fista_exact_long_pp_kernel, one problem per wave
  *                          (pb_fista_solve_d / pb_fista_solve_pp_d with PB_FLAG_LONG_HRF); the lambda search:                              auto_lbda_long_kernel / auto_lbda_long_pp_kernel (pb_auto_lbda_long_d / pb_auto_lbda_long_pp_d)
+ *   641 .. 1280  <= 48     the same with one problem per workgroup of four waves, OPT-IN by name (any stop rule, wind 6; shared HRF or one per problem):   fista_exact_split_long_kernel / fista_exact_split_long_pp_kernel
+ *                          (pb_fista_solve_split_long_d / pb_fista_solve_split_long_pp_d); the lambda search:                              auto_lbda_split_long_kernel / auto_lbda_split_long_pp_kernel (pb_auto_lbda_split_long_d / pb_auto_lbda_split_long_pp_d)
  *   longer series, longer HRFs, other windows, a cost trace beside the _loops_deconv rule: (a), one problem per wave up to
  *   2 432 scans, the LDS kernel beyond (and for the window rule beyond 1 280 scans, for 34+ taps beyond 1 280).  Per-problem HRFs: (a) for a float32 y (pb_fista_solve_pp, ldt != 0); float64 end to end
  *   (pb_fista_solve_pp_d) beyond 640 scans / 32 taps / wind 6: the LDS kernel.  A machine-filling batch that lands
@@ -481,6 +483,20 @@ int pb_spm_hrf(const double* deltas_dev, int M, const double* t_dev, int K,
  *                     wind != 6, or the flag together with PB_FLAG_FORCE_GENERIC / PB_FLAG_FORCE_FAST / PB_FLAG_PP_SPLIT.
  * pb_fista_long_hrf_supported  1 if pb_fista_solve_d and pb_fista_solve_pp_d with PB_FLAG_LONG_HRF run for (N, K, stop_mode, wind):
  *                     1 <= N <= 640, 1 <= K <= 48, a known stop_mode, wind = 6 under PB_STOP_WINDOW; else 0.  Host-only query.
+ *                     OPT-IN, by an entry point of its own (no flag; not reported by pb_fista_which_kernel_d either):
+ * pb_fista_solve_split_long_d   the parameter list of pb_fista_solve_d (taps_dev is not read and may be NULL), on
+ *                       641 .. 1280   fista_exact_split_long_kernel, one problem per workgroup of four waves, HRFs of up to 48 taps
+ *                                     (csrc/fista_exact_split_long.h: the pass of fista_exact_split_kernel with the taps in one VGPR
+ *                                     pair of every wave).  With K <= 32 the call returns the bits of fista_exact_split_kernel.
+ *                     pb_fista_solve_d itself runs 33+ taps at these lengths on the LDS kernel, as before.  The call runs that form
+ *                     or fails (PB_ERR_INVALID, nothing launched): the errors of pb_fista_solve_d, N outside 641..1280, K outside
+ *                     1..48, taps_host NULL, the window rule with wind != 6, or one of PB_FLAG_FORCE_GENERIC / PB_FLAG_FORCE_FAST /
+ *                     PB_FLAG_PP_SPLIT / PB_FLAG_LONG_HRF in flags (PB_FLAG_COLD_START is read as everywhere).
+ * pb_fista_solve_split_long_pp_d   the parameter list of pb_fista_solve_pp_d: fista_exact_split_long_pp_kernel, the same limits and
+ *                     errors (taps_dev / step_dev in the place of taps_host, ldt >= K; the slots K .. ldt-1 of a row are not
+ *                     read); with K <= 32 row p carries the bits of fista_exact_split_pp_kernel.
+ * pb_fista_split_long_hrf_supported  1 if the two run for (N, K, stop_mode, wind): 641 <= N <= 1280, 1 <= K <= 48, a known
+ *                     stop_mode, wind = 6 under PB_STOP_WINDOW; else 0.  Host-only query.
  * pb_fista_which_kernel_d  which of them pb_fista_solve_d (no flags, taps_host given) runs for a call shape: the codes
  *                     above.  Host-only query.
  * pb_fista_stats_d, pb_hrf_cost_d, pb_hrf_cost_pv_d   as their float32-y namesakes.
@@ -492,6 +508,16 @@ int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
                      int32_t* n_done_dev, unsigned flags, void* stream);
 int pb_fista_which_kernel_d(int N, int K, int with_cost_trace, int stop_mode, int wind);
 int pb_fista_long_hrf_supported(int N, int K, int stop_mode, int wind);
+int pb_fista_split_long_hrf_supported(int N, int K, int stop_mode, int wind);
+int pb_fista_solve_split_long_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw,
+                                int P, int N, const double* taps_host, const double* taps_dev, int K,
+                                double step, double lbda, const double* lbda_dev, const double* betas_dev,
+                                int n_iter, double* J_dev, int64_t ldj, int stop_mode, double tol, int wind,
+                                int32_t* n_done_dev, unsigned flags, void* stream);
+int pb_fista_solve_split_long_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
+                                   const double* taps_dev, int64_t ldt, int K, const double* step_dev, double lbda,
+                                   const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj,
+                                   int stop_mode, double tol, int wind, int32_t* n_done_dev, unsigned flags, void* stream);
 /*
  * pb_fista_solve_d with ONE HRF AND ONE STEP PER PROBLEM, both in device memory: the last step of the reference's per-voxel
  * workflow (bd on every voxel, then deconv of every voxel with its own HRF: examples/icassp_2019/simulation.py:62-72).
@@ -671,6 +697,31 @@ int pb_auto_lbda_long_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int6
                            int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr,
                            double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev,
                            double* work_dev, int64_t work_len, void* stream);
+/*
+ * OPT-IN: the search for HRFs of up to 48 taps on series of 641 .. 1 280 scans, one voxel per workgroup of four waves
+ * (auto_lbda_split_long_kernel / auto_lbda_split_long_pp_kernel, csrc/fista_exact_split_long.h: the taps in one VGPR pair of
+ * every wave).  pb_auto_lbda_split_long_d takes the parameter list of pb_auto_lbda_split_d, pb_auto_lbda_split_long_pp_d that
+ * of pb_auto_lbda_split_pp_d; the workspace (pb_auto_lbda_work_len), the state slots, the order of the validation, the
+ * outer_chunk rule (0: the library's choice -- the four-wave search's budget per launch divided by 1.5; no choice changes a
+ * bit), the launch protocol, the outputs and the traces are theirs.  With K <= 32 every output carries the bits of
+ * pb_auto_lbda_split_d / pb_auto_lbda_split_pp_d.  pb_auto_lbda_split_supported, pb_auto_lbda_split_d and
+ * pb_auto_lbda_split_pp_d keep their limit of 32 taps: this form is asked for by name.
+ * pb_auto_lbda_split_long_supported  1 if both run for (N, K, wind): 641 <= N <= 1280, 1 <= K <= 48, wind = 6; else 0.
+ * Errors (nothing is launched): those of pb_auto_lbda_split_d / pb_auto_lbda_split_pp_d, with K > 48 in the place of K > 32.
+ */
+int pb_auto_lbda_split_long_supported(int N, int K, int wind);
+int pb_auto_lbda_split_long_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                              const double* taps_host, int K, double step, const double* betas_dev,
+                              const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter,
+                              int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldt,
+                              double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev,
+                              double* work_dev, int64_t work_len, void* stream);
+int pb_auto_lbda_split_long_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                                 const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
+                                 const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter,
+                                 int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr,
+                                 double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev,
+                                 double* work_dev, int64_t work_len, void* stream);
 int pb_auto_lbda_split_supported(int N, int K, int wind);
 int pb_auto_lbda_split_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
                          const double* taps_host, int K, double step, const double* betas_dev,

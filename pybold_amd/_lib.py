@@ -33,7 +33,7 @@ PB_FLAG_ONLY_SPARSE = 262144
 PB_FLAG_NO_ILL_GUARD = 524288
 PB_FLAG_PP_SPLIT = 1048576           # pb_fista_solve_pp_d only: the four-wave per-problem-tap form or an error
 PB_FLAG_LONG_HRF = 2097152     # pb_fista_solve_d / pb_fista_solve_pp_d: the 48-tap one-wave register form (opt-in), or an error
-PB_PATH_DENSE_RATIO = 0.19          # include/pybold_hip.h (series of up to 310 scans; 0.22 beyond)
+PB_PATH_DENSE_RATIO = 0.19         # include/pybold_hip.h (series of up to 310 scans; 0.22 beyond)
 PB_STOP_NONE = 0
 PB_STOP_LOOPS = 1
 PB_STOP_WINDOW = 2
@@ -195,6 +195,41 @@ SIGNATURES = {
         _ptr, _ptr, _ptr, _ptr,
         _ptr, _c_i64, _ptr]),
     "pb_auto_lbda_long_pp_d": (_c_int, [                        # (the argument list of pb_auto_lbda_pp_d)
+        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
+        _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr,
+        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,
+        _ptr, _ptr, _ptr, _c_i64,
+        _ptr, _ptr, _ptr, _ptr,
+        _ptr, _c_i64, _ptr]),
+    # opt-in: the same holder over four waves, 641 .. 1 280 scans (csrc/fista_exact_split_long.h)
+    "pb_fista_split_long_hrf_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int]),
+    "pb_fista_solve_split_long_d": (_c_int, [                   # (the argument list of pb_fista_solve_d)
+        _ptr, _c_i64, _c_int,
+        _ptr, _c_i64, _c_int, _c_int,
+        _ptr, _ptr, _c_int,
+        _c_dbl, _c_dbl, _ptr,
+        _ptr, _c_int,
+        _ptr, _c_i64,
+        _c_int, _c_dbl, _c_int, _ptr,
+        ctypes.c_uint, _ptr]),
+    "pb_fista_solve_split_long_pp_d": (_c_int, [                # (the argument list of pb_fista_solve_pp_d)
+        _ptr, _c_i64, _c_int,
+        _ptr, _c_i64, _c_int, _c_int,
+        _ptr, _c_i64, _c_int, _ptr,
+        _c_dbl, _ptr,
+        _ptr, _c_int,
+        _ptr, _c_i64,
+        _c_int, _c_dbl, _c_int, _ptr,
+        ctypes.c_uint, _ptr]),
+    "pb_auto_lbda_split_long_supported": (_c_int, [_c_int, _c_int, _c_int]),
+    "pb_auto_lbda_split_long_d": (_c_int, [                     # (the argument list of pb_auto_lbda_split_d)
+        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
+        _ptr, _c_int, _c_dbl, _ptr, _ptr,
+        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,
+        _ptr, _ptr, _ptr, _c_i64,
+        _ptr, _ptr, _ptr, _ptr,
+        _ptr, _c_i64, _ptr]),
+    "pb_auto_lbda_split_long_pp_d": (_c_int, [                  # (the argument list of pb_auto_lbda_split_pp_d)
         _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
         _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr,
         _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,

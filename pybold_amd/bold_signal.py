@@ -127,8 +127,9 @@ DISPATCH = os.environ.get("PYBOLD_AMD_DISPATCH", "ctypes")
 # waves, `deconv_auto(engine="device_split")`; shapes neither carries keep the host loop).  1-D calls always keep the host
 # loop.  "device_split_pp": everything "device_split" does, and calls with one HRF per voxel (a 2-D `hrf`) of 641 .. 1 280
 # scans on `deconv_auto(engine="device_split_pp")`.  "device_long_hrf": everything "device" does, and HRFs of 33 .. 48 taps
-# (1-D or one per voxel) on series of up to 640 scans on `deconv_auto(engine="device_long_hrf")`.  Initialised from the
-# environment variable PYBOLD_AMD_AUTO_LBDA.
+# (1-D or one per voxel) on series of up to 640 scans on `deconv_auto(engine="device_long_hrf")`.  "device_split_long_hrf":
+# everything "device_split" does, and HRFs of 33 .. 48 taps (1-D or one per voxel) on series of 641 .. 1 280 scans on
+# `deconv_auto(engine="device_split_long_hrf")`.  Initialised from the environment variable PYBOLD_AMD_AUTO_LBDA.
 AUTO_LBDA = os.environ.get("PYBOLD_AMD_AUTO_LBDA", "host")
 
 # Opt-in: the fixed-lambda solves with one HRF per voxel (a 2-D `hrf`: `deconv` with a `lbda`, and the inner solves of the
@@ -146,15 +147,29 @@ PER_VOXEL_SPLIT = os.environ.get("PYBOLD_AMD_PP_SPLIT", "0") == "1"
 LONG_HRF = os.environ.get("PYBOLD_AMD_LONG_HRF", "0") == "1"
 
 
+# Opt-in: the same for series of 641 .. 1 280 scans -- HRFs of 33 .. 48 taps on the four-wave register form with the taps in
+# one VGPR pair of every wave (`force="split_long_hrf"`) instead of the LDS kernel, where `solver.split_long_hrf_supported`
+# says the shape is carried.  Up to 32 taps the switch names nothing: the existing four-wave forms carry those calls and are
+# faster (1.7-1.85x: DESIGN 5.8).  Measured against the LDS kernel at 42 taps, 1 .. 16 384 voxels: 1.2-3.8x faster at 700 scans,
+# 2.2-6.0x at 1 200, the host-loop search 2.1-8.9x; no point slower (profiles/split_long_hrf.txt).  Off by default: no call changes
+# its kernel unless asked.  Initialised from the environment variable PYBOLD_AMD_SPLIT_LONG_HRF ("1" is on).
+SPLIT_LONG_HRF = os.environ.get("PYBOLD_AMD_SPLIT_LONG_HRF", "0") == "1"
+
+
 def _long_hrf_force(n, n_taps, stop, wind):
     """``force`` of a float64 solve: ``"long_hrf"`` when ``LONG_HRF`` is on, the HRF has more than 32 taps (up to 32 the
-    default register form carries the call) and the shape is carried."""
-    return "long_hrf" if LONG_HRF and n_taps > 32 and solver.long_hrf_supported(n, n_taps, stop, wind) else None
+    default register form carries the call) and the shape is carried; ``"split_long_hrf"`` likewise under
+    ``SPLIT_LONG_HRF`` (the two carry disjoint series lengths)."""
+    if LONG_HRF and n_taps > 32 and solver.long_hrf_supported(n, n_taps, stop, wind):
+        return "long_hrf"
+    if SPLIT_LONG_HRF and n_taps > 32 and solver.split_long_hrf_supported(n, n_taps, stop, wind):
+        return "split_long_hrf"
+    return None
 
 
 def _pv_force(n, n_taps, stop, wind):
     """``force`` of a per-voxel-HRF solve: ``"split"`` when ``PER_VOXEL_SPLIT`` is on and the shape is carried,
-    ``"long_hrf"`` likewise under ``LONG_HRF``."""
+    ``"long_hrf"`` / ``"split_long_hrf"`` likewise under ``LONG_HRF`` / ``SPLIT_LONG_HRF``."""
     if PER_VOXEL_SPLIT and solver.pp_split_supported(n, n_taps, stop, wind):
         return "split"
     return _long_hrf_force(n, n_taps, stop, wind)
@@ -178,13 +193,16 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
     """
     per_voxel = _per_voxel_hrf(y, hrf, "deconv")
     if lbda is None:
-        if AUTO_LBDA in ("device", "device_split", "device_split_pp", "device_long_hrf") and _n_dim(y) == 2:
+        if (AUTO_LBDA in ("device", "device_split", "device_split_pp", "device_long_hrf", "device_split_long_hrf")
+                and _n_dim(y) == 2):
             n_taps = int(_shape_of(hrf)[-1]) if per_voxel else np.size(hrf)
-            split = (AUTO_LBDA in ("device_split", "device_split_pp")
+            split = (AUTO_LBDA in ("device_split", "device_split_pp", "device_split_long_hrf")
                      and solver.auto_lbda_split_supported(_n_scans(y), n_taps, wind))
             engine = ("device" if solver.auto_lbda_supported(_n_scans(y), n_taps, wind)
                       else "device_long_hrf" if (AUTO_LBDA == "device_long_hrf" and n_taps > 32
                                                  and solver.auto_lbda_long_supported(_n_scans(y), n_taps, wind))
+                      else "device_split_long_hrf" if (AUTO_LBDA == "device_split_long_hrf" and n_taps > 32
+                                                       and solver.auto_lbda_split_long_supported(_n_scans(y), n_taps, wind))
                       else "device_split" if split and not per_voxel
                       else "device_split_pp" if split and per_voxel and AUTO_LBDA == "device_split_pp"
                       else None)
@@ -279,7 +297,11 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
             required, the same limits -- ``ValueError`` otherwise; no other engine reaches it);
             "device_long_hrf": the one-wave device-resident solve for HRFs of 33 .. 48 taps (``solver.auto_lbda_solve_long`` /
             ``solver.auto_lbda_solve_long_pp``: a 1-D or ``(V, K)`` ``hrf``, series of up to 640 scans, ``wind == 6`` --
-            ``ValueError`` otherwise; no other engine reaches it, ``"device"`` and ``"auto"`` keep their limit of 32 taps)
+            ``ValueError`` otherwise; no other engine reaches it, ``"device"`` and ``"auto"`` keep their limit of 32 taps);
+            "device_split_long_hrf": everything ``"device_split"`` does, and HRFs of 33 .. 48 taps on series of 641 .. 1 280
+            scans on the four-wave search with the taps in one VGPR pair of every wave (``solver.auto_lbda_solve_split_long``;
+            a ``(V, K)`` ``hrf`` on ``solver.auto_lbda_solve_split_long_pp``), ``wind == 6`` -- ``ValueError`` otherwise; no
+            other engine reaches it
     hrf     1-D, or ``(V, K)`` beside a ``(V, N)`` batch: one HRF per voxel (``solver.auto_lbda_solve_pp`` on the device engine,
             the host loop on ``solver.fista_solve_pp_d``; ``"device_split"`` takes one HRF for all voxels, ``ValueError``;
             ``"device_split_pp"`` takes one per voxel)
@@ -290,9 +312,9 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     same input (lists for a 1-D ``y``; ``(n_outer, V)`` arrays padded with NaN for a batch, trimmed to the longest
     row's outer iterations; CUDA in -> ``x, z, diff_z`` CUDA); ``info`` holds ``alpha``, ``lbda`` (final, per
     voxel), ``n_outer``, ``n_inner`` (outer / summed inner iterations per voxel), ``sigma`` and ``engine``."""
-    if engine not in ("auto", "device", "host", "device_split", "device_split_pp", "device_long_hrf"):
-        raise ValueError("deconv_auto: engine must be 'auto', 'device', 'host', 'device_split', 'device_split_pp' or "
-                         "'device_long_hrf', got %r" % (engine,))
+    if engine not in ("auto", "device", "host", "device_split", "device_split_pp", "device_long_hrf", "device_split_long_hrf"):
+        raise ValueError("deconv_auto: engine must be 'auto', 'device', 'host', 'device_split', 'device_split_pp', "
+                         "'device_split_long_hrf' or 'device_long_hrf', got %r" % (engine,))
     per_voxel = _per_voxel_hrf(y, hrf, "deconv_auto")
     n, n_taps = _n_scans(y), (int(_shape_of(hrf)[-1]) if per_voxel else int(np.size(hrf)))
     if engine == "device_split":
@@ -319,6 +341,15 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
             raise ValueError("deconv_auto(engine='device_long_hrf'): the device-resident lambda search for long HRFs carries "
                              "HRFs of 33..48 taps, series of up to 640 scans and wind = 6 (up to 32 taps: engine='device'); "
                              "this call has %d scans, %d taps, wind = %d" % (n, n_taps, wind))
+    elif engine == "device_split_long_hrf":
+        if n_taps <= 32 and not per_voxel and solver.auto_lbda_split_supported(n, n_taps, wind):
+            engine = "device_split"                 # (what "device_split" does: the existing four-wave search, faster up to 32 taps)
+        elif not (33 <= n_taps <= 48 and solver.auto_lbda_split_long_supported(n, n_taps, wind)):
+            raise ValueError("deconv_auto(engine='device_split_long_hrf'): the four-wave device-resident lambda search for long "
+                             "HRFs carries HRFs of 33..48 taps (1-D, or one per voxel), series of 641..1280 scans and wind = 6 "
+                             "(up to 32 taps with one HRF for all voxels it runs engine='device_split'; one HRF per voxel of up "
+                             "to 32 taps: engine='device_split_pp'; up to 640 scans: engine='device_long_hrf'); this call has "
+                             "%d scans, %d taps, wind = %d" % (n, n_taps, wind))
     elif engine != "host":
         if solver.auto_lbda_supported(n, n_taps, wind):
             engine = "device"
@@ -346,7 +377,8 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
         Y, T, one_d = _pv_to_device(y, hrf)
         V = Y.shape[0]
         solve = {"device_split_pp": solver.auto_lbda_solve_split_pp,
-                 "device_long_hrf": solver.auto_lbda_solve_long_pp}.get(engine, solver.auto_lbda_solve_pp)
+                 "device_long_hrf": solver.auto_lbda_solve_long_pp,
+                 "device_split_long_hrf": solver.auto_lbda_solve_split_long_pp}.get(engine, solver.auto_lbda_solve_pp)
         W, res = solve(Y, T, _pv_steps(T, n), sigma, early_stopping=early_stopping, tol=tol, wind=wind,
                        nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
         X, Z = solver.fista_outputs_pp(W, T)
@@ -363,7 +395,8 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     H = ConvAndLinear(DiscretInteg(), hrf, dim_in=n, dim_out=n)
     step = 1.0 / (0.9 * spectral_radius_est(H, (n,)))
     solve = {"device_split": solver.auto_lbda_solve_split,
-             "device_long_hrf": solver.auto_lbda_solve_long}.get(engine, solver.auto_lbda_solve)
+             "device_long_hrf": solver.auto_lbda_solve_long,
+             "device_split_long_hrf": solver.auto_lbda_solve_split_long}.get(engine, solver.auto_lbda_solve)
     W, res = solve(Y, hrf, step, sigma, early_stopping=early_stopping, tol=tol, wind=wind,
                    nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
     X, Z = solver.fista_outputs(W, hrf)

@@ -87,6 +87,18 @@ inline int auto_long_outer_chunk(int V, int nb_sub_iter) {
   return (int)(c < 1 ? 1 : c);
 }
 
+// the same for the four-wave search with up to 48 taps (fista_exact_split_long.h): the residency of the four-wave search (two
+// workgroups per compute unit by its register reports), and a pass that carries 48 taps for 32: 1.5x the multiply-adds, the
+// reasoning of AUTO_LONG_LAUNCH_ITERS -- that search's budget divided by 1.5, rounded down to a multiple of 1 024
+// (32768 / 1.5 = 21845 -> 21504)
+constexpr int AUTO_SPLIT_LONG_LAUNCH_ITERS = 21504;
+inline int auto_split_long_outer_chunk(int V, int nb_sub_iter) {
+  const int64_t rounds = ((int64_t)V + AUTO_SPLIT_RESIDENT_WGS - 1) / AUTO_SPLIT_RESIDENT_WGS;
+  const int64_t per = (int64_t)(nb_sub_iter > 0 ? nb_sub_iter : 1) * (rounds > 0 ? rounds : 1);
+  const int64_t c = AUTO_SPLIT_LONG_LAUNCH_ITERS / per;
+  return (int)(c < 1 ? 1 : c);
+}
+
 constexpr int MAD_DAUB_NMAX = 8192;
 template <typename TY>
 int mad_daub_impl(const TY* y_dev, int64_t ldy, int V, int N, double c, double* sigma_dev, void* stream, const char* name) {
@@ -859,9 +871,84 @@ int long_hrf_entry(const char* name, int N, int K, int stop_mode, int wind, unsi
   if (!*le) return fail(PB_ERR_INVALID, "%s: no 48-tap specialisation for N=%d K=%d", name, N, K);
   return PB_OK;
 }
+// pb_fista_solve_split_long_d / pb_fista_solve_split_long_pp_d: the entry of the four-wave 48-tap form (641 .. 1 280 scans), or
+// the error of a call it does not carry (nothing is launched).  The form is named by the entry point, so the flags that name
+// another form are refused
+int split_long_hrf_entry(const char* name, int N, int K, int stop_mode, int wind, unsigned flags, const ExactLongEntry** le) {
+  if (flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_FAST | PB_FLAG_PP_SPLIT | PB_FLAG_LONG_HRF))
+    return fail(PB_ERR_INVALID, "%s: the entry point names the four-wave 48-tap register form; it excludes PB_FLAG_FORCE_GENERIC, PB_FLAG_FORCE_FAST, PB_FLAG_PP_SPLIT and PB_FLAG_LONG_HRF", name);
+  if (N < SPLIT_LONG_NMIN || N > SPLIT_LONG_NMAX) return fail(PB_ERR_INVALID, "%s: N=%d outside 641..1280 scans", name, N);
+  if (K > LONG_HRF_KMAX) return fail(PB_ERR_INVALID, "%s: K=%d outside 1..48 taps", name, K);
+  if (stop_mode == PB_STOP_WINDOW && wind != 6)
+    return fail(PB_ERR_INVALID, "%s: wind=%d (the four-wave 48-tap register form carries wind = 6)", name, wind);
+  *le = pick_exact_split_long(N, K, stop_mode, wind);
+  if (!*le) return fail(PB_ERR_INVALID, "%s: no four-wave 48-tap specialisation for N=%d K=%d", name, N, K);
+  return PB_OK;
+}
 }  // namespace
 
 int pb_fista_long_hrf_supported(int N, int K, int stop_mode, int wind) { return pick_exact_long(N, K, stop_mode, wind) ? 1 : 0; }
+
+int pb_fista_split_long_hrf_supported(int N, int K, int stop_mode, int wind) {
+  return pick_exact_split_long(N, K, stop_mode, wind) ? 1 : 0;
+}
+
+// pb_fista_solve_d on the four-wave form for HRFs of up to 48 taps (fista_exact_split_long.h), or an error: opt-in by name --
+// pb_fista_solve_d itself is what it was.  The validation is that function's, in its order
+int pb_fista_solve_split_long_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
+                                const double* taps_host, const double* taps_dev, int K, double step, double lbda,
+                                const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj, int stop_mode, double tol,
+                                int wind, int32_t* n_done_dev, unsigned flags, void* stream) {
+  const char* name = "pb_fista_solve_split_long_d";
+  (void)taps_dev;                                       // (the parameter list of pb_fista_solve_d: only the LDS kernel reads it)
+  if (P < 0 || N < 1 || K < 1 || n_iter < 0 || y_rep < 1)
+    return fail(PB_ERR_INVALID, "%s: bad size (P=%d N=%d K=%d n_iter=%d y_rep=%d)", name, P, N, K, n_iter, y_rep);
+  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "%s: leading dimension < N", name);
+  if (J_dev && ldj < n_iter) return fail(PB_ERR_INVALID, "%s: ldj < n_iter", name);
+  if (!(step > 0.0)) return fail(PB_ERR_INVALID, "%s: step must be positive", name);
+  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return fail(PB_ERR_INVALID, "%s: unknown stop_mode %d", name, stop_mode);
+  if (stop_mode == PB_STOP_WINDOW && wind < 2) return fail(PB_ERR_INVALID, "%s: wind must be >= 2", name);
+  const ExactLongEntry* le = nullptr;
+  const int rc = split_long_hrf_entry(name, N, K, stop_mode, wind, flags, &le);
+  if (rc != PB_OK) return rc;
+  if (P == 0) return PB_OK;
+  if (!y_dev || !w_dev || !taps_host || (n_iter > 0 && !betas_dev)) return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
+  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 problems per launch", name);
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, step, lbda, lbda_dev, betas_dev, stop_mode, tol,
+                               n_done_dev, flags);
+  a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj;
+  if (le->fn(a, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
+    return fail(PB_ERR_INVALID, "%s: launch rejected", name);
+  return check_launch("fista_exact_split_long_kernel");
+}
+
+// ... and pb_fista_solve_pp_d on it: one HRF and one step per problem, both in device memory
+int pb_fista_solve_split_long_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
+                                   const double* taps_dev, int64_t ldt, int K, const double* step_dev, double lbda,
+                                   const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj,
+                                   int stop_mode, double tol, int wind, int32_t* n_done_dev, unsigned flags, void* stream) {
+  const char* name = "pb_fista_solve_split_long_pp_d";
+  if (P < 0 || N < 1 || K < 1 || n_iter < 0 || y_rep < 1)
+    return fail(PB_ERR_INVALID, "%s: bad size (P=%d N=%d K=%d n_iter=%d y_rep=%d)", name, P, N, K, n_iter, y_rep);
+  if (ldt < K) return fail(PB_ERR_INVALID, "%s: ldt < K", name);
+  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "%s: leading dimension too small (< N)", name);
+  if (J_dev && ldj < n_iter) return fail(PB_ERR_INVALID, "%s: leading dimension too small (ldj < n_iter)", name);
+  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return fail(PB_ERR_INVALID, "%s: unknown stop_mode %d", name, stop_mode);
+  if (stop_mode == PB_STOP_WINDOW && wind < 2) return fail(PB_ERR_INVALID, "%s: wind must be >= 2", name);
+  const ExactLongEntry* le = nullptr;
+  const int rc = split_long_hrf_entry(name, N, K, stop_mode, wind, flags, &le);
+  if (rc != PB_OK) return rc;
+  if (P == 0) return PB_OK;
+  if (!y_dev || !w_dev || !taps_dev || !step_dev || (n_iter > 0 && !betas_dev)) return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
+  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 problems per launch", name);
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, stop_mode, tol,
+                               n_done_dev, flags);
+  a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj; a.wind = wind;
+  a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = 0;
+  if (le->fn_pp(a, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
+    return fail(PB_ERR_INVALID, "%s: launch rejected", name);
+  return check_launch("fista_exact_split_long_pp_kernel");
+}
 
 int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw,
                      int P, int N, const double* taps_host, const double* taps_dev, int K,
@@ -1016,17 +1103,20 @@ int64_t pb_auto_lbda_work_len(int V) { return (int64_t)pb::AUTO_STATE * (V > 0 ?
 namespace {
 // pb_auto_lbda_d (split = false: one voxel per wave, up to 640 scans) and pb_auto_lbda_split_d (one voxel per workgroup of
 // four waves, 641 .. 1 280 scans): one validation in one order, one launch protocol; the kernels and the library's chunk differ
-enum AutoForm { AUTO_ONE_WAVE = 0, AUTO_FOUR_WAVES = 1, AUTO_LONG_HRF = 2 };   // (the long-HRF form: one wave, up to 48 taps, opt-in)
+// (the long-HRF forms: up to 48 taps, one wave up to 640 scans, four waves for 641 .. 1 280, both opt-in)
+enum AutoForm { AUTO_ONE_WAVE = 0, AUTO_FOUR_WAVES = 1, AUTO_LONG_HRF = 2, AUTO_FOUR_WAVES_LONG_HRF = 3 };
 inline const char* auto_kernel_name(int form, bool pp, bool final_solve) {
-  static const char* const names[3][2][2] = {
+  static const char* const names[4][2][2] = {
       {{"auto_lbda_kernel", "auto_lbda_kernel(final solve)"}, {"auto_lbda_pp_kernel", "auto_lbda_pp_kernel(final solve)"}},
       {{"auto_lbda_split_kernel", "auto_lbda_split_kernel(final solve)"}, {"auto_lbda_split_pp_kernel", "auto_lbda_split_pp_kernel(final solve)"}},
-      {{"auto_lbda_long_kernel", "auto_lbda_long_kernel(final solve)"}, {"auto_lbda_long_pp_kernel", "auto_lbda_long_pp_kernel(final solve)"}}};
+      {{"auto_lbda_long_kernel", "auto_lbda_long_kernel(final solve)"}, {"auto_lbda_long_pp_kernel", "auto_lbda_long_pp_kernel(final solve)"}},
+      {{"auto_lbda_split_long_kernel", "auto_lbda_split_long_kernel(final solve)"}, {"auto_lbda_split_long_pp_kernel", "auto_lbda_split_long_pp_kernel(final solve)"}}};
   return names[form][pp][final_solve];
 }
 inline int auto_form_chunk(int form, int V, int nb_sub_iter) {
   return form == AUTO_FOUR_WAVES ? auto_split_outer_chunk(V, nb_sub_iter)
-         : form == AUTO_LONG_HRF ? auto_long_outer_chunk(V, nb_sub_iter) : auto_outer_chunk(V, nb_sub_iter);
+         : form == AUTO_LONG_HRF ? auto_long_outer_chunk(V, nb_sub_iter)
+         : form == AUTO_FOUR_WAVES_LONG_HRF ? auto_split_long_outer_chunk(V, nb_sub_iter) : auto_outer_chunk(V, nb_sub_iter);
 }
 int auto_lbda_impl(const char* name, int form, const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
                    const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
@@ -1035,14 +1125,15 @@ int auto_lbda_impl(const char* name, int form, const double* y_dev, int64_t ldy,
                    int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
   if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "%s: bad size (V=%d N=%d K=%d)", name, V, N, K);
   if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "%s: wind=%d (the device-resident search carries wind = 6)", name, wind);
-  const bool split = form == AUTO_FOUR_WAVES;
-  const int k_max = form == AUTO_LONG_HRF ? LONG_HRF_KMAX : 32;
+  const bool split = form == AUTO_FOUR_WAVES || form == AUTO_FOUR_WAVES_LONG_HRF;
+  const int k_max = (form == AUTO_LONG_HRF || form == AUTO_FOUR_WAVES_LONG_HRF) ? LONG_HRF_KMAX : 32;
   if (!split && N > 640) return fail(PB_ERR_INVALID, "%s: N=%d exceeds 640 scans", name, N);
   if (split && (N < 641 || N > 1280)) return fail(PB_ERR_INVALID, "%s: N=%d outside 641..1280 scans", name, N);
   if (K > k_max) return fail(PB_ERR_INVALID, "%s: K=%d exceeds %d taps", name, K, k_max);
   auto_launch_fn fn_auto = nullptr;
-  if (form == AUTO_LONG_HRF) {
-    const ExactLongEntry* le = pick_exact_long(N, K, PB_STOP_WINDOW, wind);
+  if (form == AUTO_LONG_HRF || form == AUTO_FOUR_WAVES_LONG_HRF) {
+    const ExactLongEntry* le = form == AUTO_LONG_HRF ? pick_exact_long(N, K, PB_STOP_WINDOW, wind)
+                                                     : pick_exact_split_long(N, K, PB_STOP_WINDOW, wind);
     fn_auto = le ? le->fn_auto : nullptr;
   } else {
     const ExactEntry* ae = split ? pick_auto_split(N, K) : pick_auto(N, K);
@@ -1103,14 +1194,15 @@ int auto_lbda_pp_impl(const char* name, int form, const double* y_dev, int64_t l
                       void* stream) {
   if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "%s: bad size (V=%d N=%d K=%d)", name, V, N, K);
   if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "%s: wind=%d (the device-resident search carries wind = 6)", name, wind);
-  const bool split = form == AUTO_FOUR_WAVES;
-  const int k_max = form == AUTO_LONG_HRF ? LONG_HRF_KMAX : 32;
+  const bool split = form == AUTO_FOUR_WAVES || form == AUTO_FOUR_WAVES_LONG_HRF;
+  const int k_max = (form == AUTO_LONG_HRF || form == AUTO_FOUR_WAVES_LONG_HRF) ? LONG_HRF_KMAX : 32;
   if (!split && N > 640) return fail(PB_ERR_INVALID, "%s: N=%d exceeds 640 scans", name, N);
   if (split && (N < 641 || N > 1280)) return fail(PB_ERR_INVALID, "%s: N=%d outside 641..1280 scans", name, N);
   if (K > k_max) return fail(PB_ERR_INVALID, "%s: K=%d exceeds %d taps", name, K, k_max);
   auto_pp_launch_fn fn_auto = nullptr;
-  if (form == AUTO_LONG_HRF) {
-    const ExactLongEntry* le = pick_exact_long(N, K, PB_STOP_WINDOW, wind);
+  if (form == AUTO_LONG_HRF || form == AUTO_FOUR_WAVES_LONG_HRF) {
+    const ExactLongEntry* le = form == AUTO_LONG_HRF ? pick_exact_long(N, K, PB_STOP_WINDOW, wind)
+                                                     : pick_exact_split_long(N, K, PB_STOP_WINDOW, wind);
     fn_auto = le ? le->fn_auto_pp : nullptr;
   } else if (split) {
     const ExactSplitPPEntry* se = pick_auto_split(N, K) ? pick_exact_split_pp(N, K, PB_STOP_WINDOW, wind) : nullptr;
@@ -1197,6 +1289,31 @@ int pb_auto_lbda_long_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int6
   return auto_lbda_pp_impl("pb_auto_lbda_long_pp_d", AUTO_LONG_HRF, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev,
                            betas_dev, sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev,
                            ldtr, alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
+}
+
+int pb_auto_lbda_split_long_supported(int N, int K, int wind) {
+  return (wind == pb::AUTO_WIND && pick_exact_split_long(N, K, PB_STOP_WINDOW, wind)) ? 1 : 0;
+}
+
+int pb_auto_lbda_split_long_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                              const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
+                              int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
+                              double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
+                              int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
+  return auto_lbda_impl("pb_auto_lbda_split_long_d", AUTO_FOUR_WAVES_LONG_HRF, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step,
+                        betas_dev, sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt,
+                        alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
+}
+
+int pb_auto_lbda_split_long_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+                                 const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
+                                 const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
+                                 int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
+                                 double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
+                                 void* stream) {
+  return auto_lbda_pp_impl("pb_auto_lbda_split_long_pp_d", AUTO_FOUR_WAVES_LONG_HRF, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt,
+                           K, step_dev, betas_dev, sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev,
+                           J_dev, ldtr, alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
 }
 
 int pb_auto_lbda_split_supported(int N, int K, int wind) { return (wind == pb::AUTO_WIND && pick_auto_split(N, K)) ? 1 : 0; }

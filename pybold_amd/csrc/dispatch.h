@@ -14,6 +14,7 @@
 #include "fista_auto_split.h"
 #include "fista_exact_pp.h"
 #include "fista_exact_long.h"
+#include "fista_exact_split_long.h"
 #include "fista_mfma.h"
 #include "fista_mfma2.h"
 #include "fista_mfma4.h"
@@ -297,6 +298,36 @@ const ExactLongEntry* pick_exact_long(int N, int K, int stop_mode, int wind) {
   if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return nullptr;
   if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
   return pick_cheapest(kExactLong, N, K, 64);
+}
+
+// ... and the same holder over the four waves of a workgroup (fista_exact_split_long.h): 641 .. 1 280 scans, up to 48 taps,
+// the pairs of exact_split_long_table.inc.  OPT-IN: no picker above falls through to it -- pb_fista_solve_split_long_d,
+// pb_auto_lbda_split_long_d and pb_auto_lbda_split_long_pp_d name it
+}  // namespace
+namespace pb {
+#define PB_EXACT_SPLIT_LONG(S, KT)                                                                                  \
+  extern template int launch_exact_split_long<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t); \
+  extern template int launch_auto_split_long<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);        \
+  extern template int launch_exact_split_long_pp<S, KT>(const FistaArgs&, bool, int, hipStream_t);                  \
+  extern template int launch_auto_split_long_pp<S, KT>(const AutoArgsPP&, bool, hipStream_t);
+#include "exact_split_long_table.inc"
+#undef PB_EXACT_SPLIT_LONG
+}  // namespace pb
+namespace {
+#define PB_EXACT_SPLIT_LONG(S, KT)                                                                                          \
+  {S, KT, &pb::launch_exact_split_long<S, KT>, &pb::launch_auto_split_long<S, KT>, &pb::launch_exact_split_long_pp<S, KT>, \
+   &pb::launch_auto_split_long_pp<S, KT>},
+const ExactLongEntry kExactSplitLong[] = {
+#include "exact_split_long_table.inc"
+};
+#undef PB_EXACT_SPLIT_LONG
+constexpr int SPLIT_LONG_NMIN = 641, SPLIT_LONG_NMAX = 1280;
+// the window rule is wind = 6
+const ExactLongEntry* pick_exact_split_long(int N, int K, int stop_mode, int wind) {
+  if (N < SPLIT_LONG_NMIN || N > SPLIT_LONG_NMAX || K < 1 || K > LONG_HRF_KMAX) return nullptr;
+  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return nullptr;
+  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
+  return pick_cheapest(kExactSplitLong, N, K, 64 * pb::SPLIT_WAVES);
 }
 
 template <int S, int KT>

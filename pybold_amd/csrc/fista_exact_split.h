@@ -44,11 +44,14 @@ struct SplitLds {
   double num[SPLIT_WAVES], den[SPLIT_WAVES];   // D: partial sums of the stop criterion
 };
 
+// Both halves read the taps through a HOLDER (fista_exact.h: TapsD, the by-value argument in scalar registers; TapsLane of
+// fista_exact_long.h, one VGPR pair of every wave, for the 48-tap kernels of fista_exact_split_long.h).
+//
 // forward half: z = cumsum(w) over the whole series, r = (h * z - y) on the samples of this wave; leaves the head of r in
 // LDS for the wave below.  Holds barrier A; the caller places barrier B behind it.
-template <int S, int KT>
+template <int S, int KT, class TAPS>
 __device__ __forceinline__ void split_forward(const double (&w)[S], const double (&y)[S], const double (&mk)[S],
-                                              const TapsD<KT>& taps, double (&r)[S], SplitLds<KT>& lds, int q, int lane) {
+                                              const TAPS& taps, double (&r)[S], SplitLds<KT>& lds, int q, int lane) {
   constexpr int H = KT - 1;
   constexpr int D = (H + S - 1) / S;
   static_assert(H >= 1 && H <= 64 * S, "the halo comes from the neighbour wave alone");
@@ -105,8 +108,8 @@ __device__ __forceinline__ void split_forward(const double (&w)[S], const double
 // backward half (behind barrier B): g = revcumsum(K^T r) over the whole series, gradient step, prox, momentum; with a stop
 // rule the two sums of its criterion over the WHOLE series come back in num / den, the same bits in every wave.  Holds
 // barrier C and, with a stop rule, D.
-template <int S, int KT, int STOP>
-__device__ __forceinline__ void split_backward(const double (&r)[S], double (&w)[S], const TapsD<KT>& taps, double nstep,
+template <int S, int KT, int STOP, class TAPS>
+__device__ __forceinline__ void split_backward(const double (&r)[S], double (&w)[S], const TAPS& taps, double nstep,
                                                double th, const double* beta_k, double (&uprev)[STOP == 2 ? S : 1],
                                                double (&d1)[STOP == 2 ? S : 1], double (&d2)[STOP == 2 ? S : 1],
                                                double (&d3)[STOP == 2 ? S : 1], double& num, double& den, SplitLds<KT>& lds,

@@ -5,7 +5,8 @@
 //   deconv / _loops_deconv loops   pybold/bold_signal.py:62-72, :259-276   -> fista_solve
 //   outputs z, x                   pybold/bold_signal.py:74-75, :97        -> fista_outputs
 //   H.op / H.adj                   pybold/linear.py:73-113                 -> op_forward / op_adjoint
-//   deconv, lbda=None (noise-driven search)   pybold/bold_signal.py:99-214    -> auto_lbda_solve, auto_lbda_solve_split, auto_lbda_solve_long
+//   deconv, lbda=None (noise-driven search)   pybold/bold_signal.py:99-214    -> auto_lbda_solve, auto_lbda_solve_split, auto_lbda_solve_long,
+//                                                                             auto_lbda_solve_split_long
 //   mad_daub_noise_est             pybold/utils.py:10-25                   -> mad_daub_noise_est
 //   hrf_fit_err as normal equations + its 1-D fit   pybold/bold_signal.py:217-222, :329-333
 //                                                                          -> hrf_normal_eq, theta_fit
@@ -163,8 +164,8 @@ Tensor mad_daub_noise_est(const Tensor& Y, double c) {
 // The noise-driven lambda search, device-resident.  W (in: warm start unless cold, out: diff_z) and the traces R, G, J
 // (V, >= nb_iter; or undefined) are written in place; returns (alpha, lbda, n_outer int32, n_inner int64).
 // (auto_lbda_solve: pb_auto_lbda_d, one voxel per wave; auto_lbda_solve_split: pb_auto_lbda_split_d, one voxel per workgroup of
-// four waves, 641 .. 1 280 scans; auto_lbda_solve_long: pb_auto_lbda_long_d, one voxel per wave, HRFs of up to 48 taps -- one
-// argument list, one body)
+// four waves, 641 .. 1 280 scans; auto_lbda_solve_long: pb_auto_lbda_long_d, one voxel per wave, HRFs of up to 48 taps;
+// auto_lbda_solve_split_long: pb_auto_lbda_split_long_d, four waves and up to 48 taps -- one argument list, one body)
 template <typename Entry>
 std::tuple<Tensor, Tensor, Tensor, Tensor> auto_lbda_impl(Entry entry, const char* name, const Tensor& Y, Tensor W, bool cold,
                                                           const Tensor& taps_host, double step, const Tensor& betas, const Tensor& sigma,
@@ -233,6 +234,15 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> auto_lbda_solve_long(const Tensor& Y,
                         tol, wind, nb_iter, nb_sub_iter, outer_chunk, R, G, J);
 }
 
+std::tuple<Tensor, Tensor, Tensor, Tensor> auto_lbda_solve_split_long(const Tensor& Y, Tensor W, bool cold, const Tensor& taps_host,
+                                                                      double step, const Tensor& betas, const Tensor& sigma,
+                                                                      bool early_stopping, double tol, int64_t wind, int64_t nb_iter,
+                                                                      int64_t nb_sub_iter, int64_t outer_chunk, c10::optional<Tensor> R,
+                                                                      c10::optional<Tensor> G, c10::optional<Tensor> J) {
+  return auto_lbda_impl(&pb_auto_lbda_split_long_d, "pb_auto_lbda_split_long_d", Y, W, cold, taps_host, step, betas, sigma,
+                        early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R, G, J);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(pybold_hip, m) {
@@ -243,6 +253,9 @@ TORCH_LIBRARY(pybold_hip, m) {
         "bool early_stopping, float tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk, Tensor(b!)? R, "
         "Tensor(c!)? G, Tensor(d!)? J) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("auto_lbda_solve_long(Tensor Y, Tensor(a!) W, bool cold, Tensor taps_host, float step, Tensor betas, Tensor sigma, "
+        "bool early_stopping, float tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk, Tensor(b!)? R, "
+        "Tensor(c!)? G, Tensor(d!)? J) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("auto_lbda_solve_split_long(Tensor Y, Tensor(a!) W, bool cold, Tensor taps_host, float step, Tensor betas, Tensor sigma, "
         "bool early_stopping, float tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk, Tensor(b!)? R, "
         "Tensor(c!)? G, Tensor(d!)? J) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("mad_daub_noise_est(Tensor Y, float c) -> Tensor");
@@ -261,6 +274,7 @@ TORCH_LIBRARY_IMPL(pybold_hip, CUDA, m) {
   m.impl("auto_lbda_solve", &auto_lbda_solve);
   m.impl("auto_lbda_solve_split", &auto_lbda_solve_split);
   m.impl("auto_lbda_solve_long", &auto_lbda_solve_long);
+  m.impl("auto_lbda_solve_split_long", &auto_lbda_solve_split_long);
   m.impl("mad_daub_noise_est", &mad_daub_noise_est);
   m.impl("fista_outputs", &fista_outputs);
   m.impl("op_forward", &op_forward);

@@ -252,7 +252,9 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
           reference's arithmetic -- what the 1-D calls of the API use.  ``force="long_hrf"`` (opt-in,
           ``PB_FLAG_LONG_HRF``): the one-wave register form for HRFs of up to 48 taps, ``N <= 640``, window rule at
           ``wind == 6`` -- :func:`long_hrf_supported`; any other shape is an error.  Without it 33+ taps run on the
-          LDS kernel
+          LDS kernel.  ``force="split_long_hrf"`` (opt-in, ``pb_fista_solve_split_long_d``): the same holder with one problem per
+          workgroup of four waves, ``641 <= N <= 1280``, ``K <= 48`` -- :func:`split_long_hrf_supported`; any other shape
+          is an error
     hrf   1-D array of K taps (host)
     lbda  scalar, or array/tensor of ``V * y_rep`` per-problem values
     step  ``1 / L``
@@ -271,6 +273,9 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
     f64 = torch.is_tensor(Y) and Y.dtype == torch.float64
     if force == "long_hrf" and not f64:
         raise ValueError("force='long_hrf' names the float64 register form for HRFs of up to 48 taps: float64 Y only")
+    if force == "split_long_hrf" and not f64:
+        raise ValueError("force='split_long_hrf' names the four-wave float64 register form for HRFs of up to 48 taps: "
+                         "float64 Y only")
     Y = _rows(Y, torch.float64 if f64 else torch.float32, "Y")
     dev = Y.device
     V, N = Y.shape
@@ -304,13 +309,16 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
         J.fill_(float("nan"))
     n_done = torch.empty((P,), dtype=torch.int32, device=dev)
     if f64:
-        if force not in (None, "generic", "fast", "long_hrf"):
+        if force not in (None, "generic", "fast", "long_hrf", "split_long_hrf"):
             raise ValueError("float64 y: force must be None, 'fast' (register-resident float64 "
-                             "kernel, one problem per wave), 'generic' (LDS kernel) or 'long_hrf' (the register form "
-                             "for HRFs of up to 48 taps, up to 640 scans)")
-        flags = _lib.PB_FLAG_LONG_HRF if force == "long_hrf" else _FORCE[force]
+                             "kernel, one problem per wave), 'generic' (LDS kernel), 'long_hrf' (the register form "
+                             "for HRFs of up to 48 taps, up to 640 scans) or 'split_long_hrf' (the same over four waves, "
+                             "641..1280 scans)")
+        flags = _lib.PB_FLAG_LONG_HRF if force == "long_hrf" else _FORCE.get(force, 0)
+        # (the four-wave form for long HRFs has an entry point of its own, with this parameter list, in the place of a flag)
+        entry = "pb_fista_solve_split_long_d" if force == "split_long_hrf" else "pb_fista_solve_d"
         with torch.cuda.device(dev):
-            rc = lib.pb_fista_solve_d(
+            rc = getattr(lib, entry)(
                 Y.data_ptr(), _ld(Y), int(y_rep), W.data_ptr(), _ld(W), P, N,
                 taps.ctypes.data, taps_dev.data_ptr(), taps.size, float(step), lbda_scalar,
                 lbda_dev.data_ptr() if lbda_dev is not None else None,
@@ -318,7 +326,7 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
                 J.data_ptr() if J is not None else None, _ld(J) if J is not None else 0,
                 _STOP[stop], float(tol), int(wind), n_done.data_ptr(), flags | cold,
                 _stream_ptr(dev))
-        _lib.check(rc, "pb_fista_solve_d")
+        _lib.check(rc, entry)
         return W, J, n_done
     # Every float32 call goes through pb_fista_solve_ex with a workspace: where the matrix-pipe form can carry the call
     # (129..310 scans, >= 4 096 problems) the problems are partitioned on the device -- dense class on the matrix
@@ -791,6 +799,9 @@ def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=N
            | "long_hrf" (opt-in, ``PB_FLAG_LONG_HRF``: one problem per wave, ``N <= 640``, ``K <= 48``, window rule at
            ``wind == 6`` -- :func:`long_hrf_supported`; any other shape is an error.  Without it 33+ taps run on the
            LDS kernel)
+           | "split_long_hrf" (opt-in, ``pb_fista_solve_split_long_pp_d``: one problem per workgroup of four waves,
+           ``641 <= N <= 1280``, ``K <= 48``, window rule at ``wind == 6`` -- :func:`split_long_hrf_supported`; any
+           other shape is an error)
     Returns ``(W float64 (V, N), J float64 (V, n_iter) or None, n_done int32 (V,))``."""
     lib = _lib.load()
     Y = _rows(Y, torch.float64, "Y")
@@ -802,11 +813,13 @@ def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=N
     steps = torch.as_tensor(steps, dtype=torch.float64).to(dev).contiguous().ravel()
     if steps.numel() != V:
         raise ValueError("steps must have one entry per voxel (%d)" % V)
-    if force not in (None, "generic", "fast", "split", "long_hrf"):
+    if force not in (None, "generic", "fast", "split", "long_hrf", "split_long_hrf"):
         raise ValueError("float64 y: force must be None, 'fast' (register-resident float64 kernel, one problem per "
-                         "wave), 'split' (the same over four waves, 641..1280 scans), 'generic' (LDS kernel) or "
-                         "'long_hrf' (one problem per wave, HRFs of up to 48 taps)")
+                         "wave), 'split' (the same over four waves, 641..1280 scans), 'generic' (LDS kernel), "
+                         "'long_hrf' (one problem per wave, HRFs of up to 48 taps) or 'split_long_hrf' (four waves, "
+                         "641..1280 scans, HRFs of up to 48 taps)")
     flags = {"split": _lib.PB_FLAG_PP_SPLIT, "long_hrf": _lib.PB_FLAG_LONG_HRF}.get(force, _FORCE.get(force, 0))
+    entry = "pb_fista_solve_split_long_pp_d" if force == "split_long_hrf" else "pb_fista_solve_pp_d"
     cold = 0
     if W0 is None:
         W = torch.empty((V, N), dtype=torch.float64, device=dev)
@@ -826,12 +839,12 @@ def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=N
     J = torch.full((V, max(n_iter, 1)), float("nan"), dtype=torch.float64, device=dev) if want_J else None
     n_done = torch.empty((V,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.pb_fista_solve_pp_d(
+        rc = getattr(lib, entry)(
             Y.data_ptr(), _ld(Y), 1, W.data_ptr(), _ld(W), V, N, taps.data_ptr(), _ld(taps), taps.shape[1],
             steps.data_ptr(), lbda_scalar, lbda_dev.data_ptr() if lbda_dev is not None else None,
             betas.data_ptr(), int(n_iter), J.data_ptr() if J is not None else None, _ld(J) if J is not None else 0,
             _STOP[stop], float(tol), int(wind), n_done.data_ptr(), flags | cold, _stream_ptr(dev))
-    _lib.check(rc, "pb_fista_solve_pp_d")
+    _lib.check(rc, entry)
     return W, J, n_done
 
 
@@ -845,6 +858,12 @@ def long_hrf_supported(n_scans, n_taps, stop=None, wind=6):
     """Whether :func:`fista_solve` (float64 ``Y``) and :func:`fista_solve_pp_d` with ``force="long_hrf"`` carry this
     shape (``pb_fista_long_hrf_supported``: ``N <= 640``, ``K <= 48``, the window rule at ``wind == 6``)."""
     return bool(_lib.load().pb_fista_long_hrf_supported(int(n_scans), int(n_taps), _STOP[stop], int(wind)))
+
+
+def split_long_hrf_supported(n_scans, n_taps, stop=None, wind=6):
+    """Whether :func:`fista_solve` (float64 ``Y``) and :func:`fista_solve_pp_d` with ``force="split_long_hrf"`` carry this
+    shape (``pb_fista_split_long_hrf_supported``: ``641 <= N <= 1280``, ``K <= 48``, the window rule at ``wind == 6``)."""
+    return bool(_lib.load().pb_fista_split_long_hrf_supported(int(n_scans), int(n_taps), _STOP[stop], int(wind)))
 
 
 def fista_stats_pp(W, Y, taps):
@@ -978,6 +997,12 @@ def auto_lbda_long_supported(n_scans, n_taps, wind=6):
     return bool(_lib.load().pb_auto_lbda_long_supported(int(n_scans), int(n_taps), int(wind)))
 
 
+def auto_lbda_split_long_supported(n_scans, n_taps, wind=6):
+    """Whether :func:`auto_lbda_solve_split_long` and :func:`auto_lbda_solve_split_long_pp` carry this shape
+    (``641 <= N <= 1280``, ``K <= 48``, ``wind == 6``)."""
+    return bool(_lib.load().pb_auto_lbda_split_long_supported(int(n_scans), int(n_taps), int(wind)))
+
+
 def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
                     outer_chunk=0, W0=None, want_trace=True):
     """The noise-driven lambda search of ``deconv(lbda=None)`` (pybold/bold_signal.py:99-214) for every row of ``Y``
@@ -1008,6 +1033,15 @@ def auto_lbda_solve_long(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, w
     VGPR pair; :func:`auto_lbda_long_supported`): the same arguments, the same return value; with ``K <= 32`` the same
     bits.  Opt-in: :func:`auto_lbda_solve` keeps its limit of 32 taps."""
     return _auto_lbda_solve("pb_auto_lbda_long_d", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+                            outer_chunk, W0, want_trace)
+
+
+def auto_lbda_solve_split_long(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                               outer_chunk=0, W0=None, want_trace=True):
+    """:func:`auto_lbda_solve_split` for HRFs of up to 48 taps (``pb_auto_lbda_split_long_d``: one voxel per workgroup of
+    four waves, the taps in one VGPR pair of every wave; :func:`auto_lbda_split_long_supported`): the same arguments, the
+    same return value; with ``K <= 32`` the same bits.  Opt-in: :func:`auto_lbda_solve_split` keeps its limit of 32 taps."""
+    return _auto_lbda_solve("pb_auto_lbda_split_long_d", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
                             outer_chunk, W0, want_trace)
 
 
@@ -1044,12 +1078,22 @@ def auto_lbda_solve_long_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e
                               want_trace, _entry="pb_auto_lbda_long_pp_d")
 
 
+def auto_lbda_solve_split_long_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000,
+                                  nb_sub_iter=1000, outer_chunk=0, W0=None, want_trace=True):
+    """:func:`auto_lbda_solve_split_pp` for HRFs of up to 48 taps (``pb_auto_lbda_split_long_pp_d``;
+    :func:`auto_lbda_split_long_supported` answers for its shapes): the same arguments, the same return value.  Opt-in:
+    :func:`auto_lbda_solve_split_pp` keeps its limit of 32 taps."""
+    return auto_lbda_solve_pp(Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0,
+                              want_trace, _entry="pb_auto_lbda_split_long_pp_d")
+
+
 def _auto_lbda_solve(entry, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0, want_trace):
     lib = _lib.load()
     Y = _rows(Y, torch.float64, "Y")
     dev = Y.device
     V, N = Y.shape
-    pp = entry in ("pb_auto_lbda_pp_d", "pb_auto_lbda_split_pp_d", "pb_auto_lbda_long_pp_d")     # hrf: CUDA (V, K), step: CUDA (V,)
+    pp = entry in ("pb_auto_lbda_pp_d", "pb_auto_lbda_split_pp_d", "pb_auto_lbda_long_pp_d",
+                   "pb_auto_lbda_split_long_pp_d")     # hrf: CUDA (V, K), step: CUDA (V,)
     taps = None if pp else _as_taps(hrf)
     nb_iter, nb_sub_iter = int(nb_iter), int(nb_sub_iter)
     if W0 is None:

@@ -70,6 +70,14 @@ def auto_lbda_solve_long(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, w
                             outer_chunk, W0, want_trace)
 
 
+def auto_lbda_solve_split_long(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                               outer_chunk=0, W0=None, want_trace=True):
+    """The same contract as :func:`pybold_amd.solver.auto_lbda_solve_split_long` through
+    ``torch.ops.pybold_hip.auto_lbda_solve_split_long``."""
+    return _auto_lbda_solve("auto_lbda_solve_split_long", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter,
+                            nb_sub_iter, outer_chunk, W0, want_trace)
+
+
 def _auto_lbda_solve(op, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0, want_trace):
     import numpy as np
     from . import solver
