@@ -80,6 +80,11 @@ extern "C" {
 #define PB_FLAG_PP_SPLIT 1048576u   /* pb_fista_solve_pp_d only: the four-wave form with per-problem taps (641 .. 1 280 scans), or an error */
 #define PB_FLAG_LONG_HRF 2097152u   /* pb_fista_solve_d / pb_fista_solve_pp_d only: the one-wave float64 register form for HRFs of up to
                                      * 48 taps (csrc/fista_exact_long.h: up to 640 scans, the taps in one VGPR pair), or an error */
+/* One more flag, bit 22, as an enumerator: one-wave matrix-pipe form, plain solves with up to 32 taps (pb_fista_solve and
+ * its kin, and pb_fista_solve_pp with one shared HRF in device memory): the two dense near
+ * tiles (fista_mfma_kernel, 12 matrix instructions per block and pass) instead of the 2:4-sparse joined tile
+ * (fista_mfma_sparse_kernel, 6).  For A/B runs and as a fallback. */
+enum { PB_FLAG_MFMA_DENSE_TILES = 4194304 };
 #define PB_FLAG_ONE_LAUNCH 32u    /* never split a plain solve into a full-rounds launch and a
                                      remainder launch (see pb_fista_solve) */
 
@@ -270,6 +275,17 @@ int64_t pb_fista_work_len(int P, int y_rep);
 #define PB_CAND_COUNT 10
 int pb_fista_list_plan(int kind, int n, int n_max, int has_pair, int has_wide, int one_stream, int has_mfma2,
                        int beside_chunks, int32_t* ranges, int32_t* bounds);
+/* Host-only query: one 2:4-sparse near tile of the one-wave matrix-pipe form for v_smfmac_f32_16x16x64_f16
+ * (csrc/mfma_sparse_tiles.h: the joined tile [C0 | -E] of a block and its neighbour, K <= 32 taps), as the kernel's lanes
+ * would hold it.  pass 0: forward, 1: adjoint; parity: of the block whose products use the tile; row_half 0 / 1.
+ * hi, lo: [16][32] float16 bit patterns of the split kept values (row, 8 kg + j: value j of lane group kg); idx: [16][4]
+ * words of 2-bit positions (row, lane group kg): values 2p, 2p+1 sit at positions bits [4p+1:4p] and [4p+3:4p+2] of the
+ * group of four that the B operand holds in lane group g = 2 (kg & 1) + (p >> 1), registers 2t, 2t+1 with
+ * t = 2 (kg >> 1) + (p & 1); position 2e + s of that group is slot 8 g + 2 t + s of the block of parity e; tile row
+ * 4 gp + i of row half r is output slot 8 gp + 4 r + i.  c64 (may be NULL): the 64 scaled cumulative taps the tile was
+ * built from.  -1 for K outside 1..32. */
+int pb_mfma_sparse_tile(const double* taps_host, int K, int pass, int parity, int row_half, unsigned short* hi,
+                        unsigned short* lo, unsigned short* idx, float* c64);
 int pb_fista_solve_ex(const float* y_dev, int64_t ldy, int y_rep,
                       double* w_dev, int64_t ldw, int P, int N,
                       const double* taps_host, const double* taps_dev, int K,

@@ -32,6 +32,7 @@ PB_FLAG_ONLY_DENSE = 131072
 PB_FLAG_ONLY_SPARSE = 262144
 PB_FLAG_NO_ILL_GUARD = 524288
 PB_FLAG_PP_SPLIT = 1048576           # pb_fista_solve_pp_d only: the four-wave per-problem-tap form or an error
+PB_FLAG_MFMA_DENSE_TILES = 4194304   # one-wave matrix-pipe form: the dense near tiles instead of the 2:4-sparse joined tile
 PB_FLAG_LONG_HRF = 2097152     # pb_fista_solve_d / pb_fista_solve_pp_d: the 48-tap one-wave register form (opt-in), or an error
 PB_PATH_DENSE_RATIO = 0.19         # include/pybold_hip.h (series of up to 310 scans; 0.22 beyond)
 PB_STOP_NONE = 0
@@ -63,6 +64,7 @@ SIGNATURES = {
         ctypes.c_uint, _ptr]),           # flags, stream
     "pb_fista_work_len": (_c_i64, [_c_int, _c_int]),
     "pb_fista_list_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),
+    "pb_mfma_sparse_tile": (_c_int, [_ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr]),
     "pb_fista_solve_ex": (_c_int, [
         _ptr, _c_i64, _c_int,            # y_dev, ldy, y_rep
         _ptr, _c_i64, _c_int, _c_int,    # w_dev, ldw, P, N

@@ -22,6 +22,7 @@
 #include "fista_exact_split_pp.h"
 #include "blind.h"
 #include "fista_mfma.h"
+#include "fista_mfma_sparse.h"
 #include "fista_mfma2.h"
 #include "fista_mfma4.h"
 #include "path.h"
@@ -821,6 +822,22 @@ int pb_fista_list_plan(int kind, int n, int n_max, int has_pair, int has_wide, i
     if (bounds) bounds[c] = pb::cand_max_slots(c, n_max, slots);
   }
   if (rc != 0) return fail(PB_ERR_INVALID, "pb_fista_list_plan: a piece of the plan found its candidate launch taken (n=%d)", n);
+  g_err[0] = 0;
+  return PB_OK;
+}
+
+int pb_mfma_sparse_tile(const double* taps_host, int K, int pass, int parity, int row_half, unsigned short* hi,
+                        unsigned short* lo, unsigned short* idx, float* c64) {
+  if (!taps_host || !hi || !lo || !idx) return fail(PB_ERR_INVALID, "pb_mfma_sparse_tile: NULL pointer");
+  if (pass < 0 || pass > 1 || parity < 0 || parity > 1 || row_half < 0 || row_half > 1)
+    return fail(PB_ERR_INVALID, "pb_mfma_sparse_tile: pass, parity and row_half are 0 or 1");
+  if (K < 1 || K > pb::SPARSE_TILE_KMAX)
+    return fail(PB_ERR_INVALID, "pb_mfma_sparse_tile: K=%d outside 1..%d taps (33 taps put three nonzeros in a group of four)", K,
+                pb::SPARSE_TILE_KMAX);
+  const pb::MfmaTaps tp = pb::make_mfma_taps(taps_host, K);
+  if (pb::build_sparse_tile_host(tp, K, pass, parity, row_half, hi, lo, idx) != 0)
+    return fail(PB_ERR_INVALID, "pb_mfma_sparse_tile: a group of four holds more than two nonzeros (K=%d)", K);
+  if (c64) memcpy(c64, tp.c, 64 * sizeof(float));
   g_err[0] = 0;
   return PB_OK;
 }

@@ -62,6 +62,10 @@ namespace pb {
 #define PB_MFMA(NB) extern template int launch_mfma<NB>(const FistaArgs&, const double*, int, bool, hipStream_t);
 PB_MFMA(5) PB_MFMA(6) PB_MFMA(7) PB_MFMA(8) PB_MFMA(9) PB_MFMA(10)
 #undef PB_MFMA
+// (fista_mfma_sparse.h: the plain solve with K <= 32 on the 2:4-sparse near tiles, every other call on launch_mfma<NB>)
+#define PB_MFMA(NB) extern template int launch_mfma_st<NB>(const FistaArgs&, const double*, int, bool, hipStream_t);
+PB_MFMA(5) PB_MFMA(6) PB_MFMA(7) PB_MFMA(8) PB_MFMA(9) PB_MFMA(10)
+#undef PB_MFMA
 }
 namespace pb {
 #define PB_MFMA2(A, B) extern template int launch_mfma2<A, B>(const FistaArgs&, const double*, int, bool, hipStream_t);
@@ -106,12 +110,15 @@ launch_fn pick_mfma4(int N, int K, bool two_tiles_only) {
 // window-rule certificate or the _loops_deconv rule rides the kernel)
 constexpr int MFMA_K2 = 33, MFMA_K3 = 64;
 constexpr int MFMA1_NMAX = 10 * pb::MFMA_SPAN;   // longer series (up to 640 scans) run on the split form (fista_mfma2.h)
-launch_fn pick_mfma(int N, int K, bool stop_rule) {
+// `dense_tiles` (PB_FLAG_MFMA_DENSE_TILES): the plain solve with K <= 32 keeps its two dense near tiles too
+launch_fn pick_mfma(int N, int K, bool stop_rule, bool dense_tiles = false) {
   static const launch_fn tab[] = {&pb::launch_mfma<5>, &pb::launch_mfma<6>, &pb::launch_mfma<7>,
                                   &pb::launch_mfma<8>, &pb::launch_mfma<9>, &pb::launch_mfma<10>};
+  static const launch_fn tab_st[] = {&pb::launch_mfma_st<5>, &pb::launch_mfma_st<6>, &pb::launch_mfma_st<7>,
+                                     &pb::launch_mfma_st<8>, &pb::launch_mfma_st<9>, &pb::launch_mfma_st<10>};
   const int nb = (N + pb::MFMA_SPAN - 1) / pb::MFMA_SPAN;
   if (K < 1 || K > MFMA_K3 || (K > MFMA_K2 && stop_rule) || N <= 128 || nb > 10) return nullptr;   // (129 .. 310 scans: 5 .. 10 blocks)
-  return tab[nb - 5];
+  return (dense_tiles ? tab : tab_st)[nb - 5];
 }
 }  // namespace
 namespace pb {
@@ -617,7 +624,7 @@ Route route(const Call& c) {
     // rule is evaluated exactly inside it (no cost trace, K <= 33).
     r.mfma_cert = r.cert && ((fl & PB_FLAG_FORCE_MFMA) || c.tol_iters < CERT_TN_MATRIX_PIPE);
     const bool mfma_rule = plain || r.mfma_cert || (stop == PB_STOP_LOOPS && !c.cost_trace && K <= MFMA_K2);
-    const launch_fn mfma_shape = mfma_rule ? pick_mfma(N, K, !plain) : nullptr;
+    const launch_fn mfma_shape = mfma_rule ? pick_mfma(N, K, !plain, (fl & PB_FLAG_MFMA_DENSE_TILES) != 0) : nullptr;
     const launch_fn mfma = (mfma_shape && c.n_done && (!c.lbda_vec || (fl & PB_FLAG_FORCE_MFMA)) && !(fl & FLAGS_PAIR_PIN_OR_NO_MFMA))
                                ? mfma_shape : nullptr;
     r.has_pair = (fe->fn_pair && plain) || r.cert;
@@ -651,7 +658,7 @@ Route route(const Call& c) {
   }
   // 305..310 scans with more than 32 taps: no single-row entry, but ten blocks of 31 samples fit the matrix-pipe form --
   // whole rounds (or everything) on it, a small remainder and the problems its guards hand back on the one-problem-per-wave form
-  const launch_fn mf = mfma_plain ? pick_mfma(N, K, false) : nullptr;
+  const launch_fn mf = mfma_plain ? pick_mfma(N, K, false, (fl & PB_FLAG_MFMA_DENSE_TILES) != 0) : nullptr;
   if (mf && we1) {
     r.path = PATH_MFMA_WIDE;
     r.mfma = mf;
@@ -705,7 +712,7 @@ Route route_pp(int N, int K, int P, bool shared, int stop_mode, bool n_done, uns
         r.one_form = FORM_PAIR;
         return r;
       }
-      r.mfma = (n_done && !(fl & PB_FLAG_NO_MFMA)) ? pick_mfma(N, K, false) : nullptr;
+      r.mfma = (n_done && !(fl & PB_FLAG_NO_MFMA)) ? pick_mfma(N, K, false, (fl & PB_FLAG_MFMA_DENSE_TILES) != 0) : nullptr;
       r.split = (r.mfma && K <= MFMA_K2) ? pick_mfma2(N, K, false) : nullptr;
       r.has_mfma2 = r.split != nullptr;
       return r;

@@ -34,6 +34,11 @@ _FORCE = {None: 0, "generic": PB_FLAG_FORCE_GENERIC, "fast": PB_FLAG_FORCE_FAST,
           # "valu": library dispatch without the matrix-pipe form; "mfma": everything on it, one launch
           "valu": _lib.PB_FLAG_NO_MFMA, "valuseq": _lib.PB_FLAG_NO_MFMA | PB_FLAG_ONE_STREAM,
           "mfma": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA,
+          # the same on the two dense near tiles (plain solves with up to 32 taps take the 2:4-sparse joined tile otherwise);
+          # "dense_tiles": library dispatch with that kernel
+          "mfma_dense": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | _lib.PB_FLAG_MFMA_DENSE_TILES,
+          "dense_tiles": _lib.PB_FLAG_MFMA_DENSE_TILES,
+          "mfma_denseonly": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | _lib.PB_FLAG_MFMA_DENSE_TILES | _lib.PB_FLAG_CERT_NO_RESOLVE,
           # "mfma2": everything on the matrix-pipe form with each series split over two waves, one launch
           # a partitioned call, measurement aids: only the dense class is solved / only the sparse class
           "path_dense": _lib.PB_FLAG_ONLY_DENSE, "path_sparse": _lib.PB_FLAG_ONLY_SPARSE,
