@@ -187,6 +187,7 @@ int pb_fista_plan_ex(int N, int K, int P, int stop_mode, int wind, unsigned flag
  *   <= 128       <= 32     (a)                  (a) certificate          (a)                   two problems per row / single row
  *   129 .. 310   <= 33     (b)                  (b) certificate          (b) in full           fista_mfma_kernel, one wave per 16 problems
  *   129 .. 310   34 .. 48  (b)                  (b) from 225 scans on    (b) from 225 scans on ... with three near tiles (stop rules: split form)
+ *   129 .. 310   <= 33     (b) one HRF per parcel, rows contiguous by parcel (pb_fista_solve_grouped, plain only):   the same kernels, a wave's 16 problems of one parcel; other shapes: (a), per problem
  *   311 .. 640   <= 33     (b)                  (b) certificate          (b) in full           fista_mfma2_kernel, two waves per 16 problems
  *   311 .. 640   34 .. 48  (b)                  (b) certificate          (b) in full           ... with three near tiles
  *   641 .. 1280  <= 33     (b)                  (b) certificate          (b) in full           fista_mfma4_kernel, four waves per 16 problems
@@ -827,6 +828,60 @@ int pb_theta_fit_step(const double* msg_dev, int K, const double* t_dev,
                       double lo, double hi, int n_refine, int N, double lbda, double* theta_dev,
                       double* cost_dev, double* taps_dev, double* step_dev, double* jcost_dev,
                       void* stream);
+
+/*
+ * One HRF per PARCEL (blind deconvolution with one dilation per region of an atlas: the model between
+ * one HRF per voxel, pb_fista_solve_pp with ldt != 0, and one for every voxel, ldt = 0).  The rows of a
+ * grouped call are CONTIGUOUS BY PARCEL: parcel g owns the rows offsets[g] .. offsets[g + 1] - 1, with
+ * 0 = offsets[0] <= ... <= offsets[G] = P (an empty parcel is allowed).  The offsets are given twice:
+ * offsets_host (int32 [G + 1], host memory) is checked and sizes the launches; offsets_dev (the same
+ * numbers in device memory) is what the kernels' unit table is built from, on the device, in the call
+ * itself -- so neither call allocates, copies from the host or synchronises with it, both run on the
+ * caller's stream, and a loop of them can be captured into a graph.  (Every range read from
+ * offsets_dev is clamped into the batch, so a device copy that differs from the host copy gives wrong
+ * groupings, never an access outside the arrays.)
+ *
+ * pb_fista_solve_grouped   the arguments of pb_fista_solve_pp (no stop rule, no cost trace) with
+ *                     taps_dev float64 [G][ldt] (K used), step_dev float64 [G], the offsets and an int32
+ *                     work buffer of pb_fista_grouped_work_len(P, G, K) words (8-byte aligned).
+ *                     129 .. 310 scans, K <= 33, n_done_dev given: the matrix-pipe kernels of the
+ *                     shared-HRF z-step (fista_mfma_sparse_kernel for K <= 32, fista_mfma_kernel for
+ *                     K = 33; GROUPED instantiations), a wave's 16 problems all of one parcel and its
+ *                     tiles built from that parcel's taps and step: a parcel of n rows costs
+ *                     ceil(n / 16) waves, the last one with 16 ceil(n / 16) - n dead slots
+ *                     (pb_fista_grouped_waves counts them).  Range, scale and accuracy guards hand
+ *                     problems back (n_done = -1) exactly as the shared form does; they are re-solved
+ *                     in the same call on the exact vector forms with their parcel's taps.  Calls of
+ *                     fewer than 4 096 rows, every other shape, and PB_FLAG_NO_MFMA: every row on the
+ *                     per-problem vector route of pb_fista_solve_pp with its parcel's taps (copied per
+ *                     row into the work buffer).  PB_FLAG_FORCE_MFMA: the matrix pipe whatever the
+ *                     number of rows, PB_ERR_INVALID for a shape it does not serve;
+ *                     PB_FLAG_NO_RHO_GUARD, _CERT_NO_RESOLVE, _COLD_START, _ONE_LAUNCH as for
+ *                     pb_fista_solve_pp (the grouped matrix-pipe solve is one launch as it is).
+ * pb_fista_grouped_plan    host-only: the unit table of a grouped solve for offsets in host memory --
+ *                     table_out [3 * units] = (first row, rows <= per, parcel) per unit, first_out [G + 1]
+ *                     = first unit of every parcel (either may be NULL); per = 16 is the wave table.
+ *                     Returns the number of units, -1 for offsets the entry points refuse.
+ * pb_hrf_normal_eq_w_grouped   pb_hrf_normal_eq_w with one set per parcel: out_dev [G][ldo], row g =
+ *                     the normal equations (G, b, yy) of parcel g's rows followed by their sum of
+ *                     ||w_v||_1 (len + 1 values, ldo >= len + 1).  ONE pass over (w, y), cumulative sum
+ *                     by pb_integ_op's tree inside it; workgroups sum units of one parcel each into
+ *                     work_dev, a second stage adds a parcel's units in a fixed order (no atomics:
+ *                     results are reproducible); no per-voxel set is written.  work_dev: float64,
+ *                     pb_hrf_normal_eq_w_grouped_work_len(V, G, K) values.
+ */
+int64_t pb_fista_grouped_work_len(int P, int G, int K);
+int pb_fista_grouped_waves(const int32_t* offsets_host, int G, int P);
+int pb_fista_grouped_plan(const int32_t* offsets_host, int G, int P, int per, int32_t* table_out, int32_t* first_out);
+int pb_fista_solve_grouped(const float* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int P, int N,
+                           const double* taps_dev, int64_t ldt, int K, const double* step_dev, int G,
+                           const int32_t* offsets_host, const int32_t* offsets_dev, double lbda,
+                           const double* lbda_dev, const double* betas_dev, int n_iter, int32_t* n_done_dev,
+                           int32_t* work_dev, int64_t work_len, unsigned flags, void* stream);
+int64_t pb_hrf_normal_eq_w_grouped_work_len(int V, int G, int K);
+int pb_hrf_normal_eq_w_grouped(const double* w_dev, int64_t ldw, const float* y_dev, int64_t ldy, int V,
+                               int N, int K, int G, const int32_t* offsets_host, const int32_t* offsets_dev,
+                               double* work_dev, int64_t work_len, double* out_dev, int64_t ldo, void* stream);
 
 #ifdef __cplusplus
 }

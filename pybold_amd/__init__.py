@@ -11,6 +11,7 @@ from .convolution import (kernel_from_toeplitz, simple_convolve, simple_retro_co
                           spectral_retro_convolve, spectral_retro_deconvolve, toeplitz_from_kernel)
 from .hrf_model import MAX_DELTA, MIN_DELTA, spm_hrf  # noqa: F401
 from .linear import ConvAndLinear, DiscretInteg, SpectralConvAndLinear  # noqa: F401
+from .parcels import bd_parcels  # noqa: F401
 from .padding import custom_padd, custom_padd_layout, padd, unpadd  # noqa: F401
 from .utils import gram_frobenius, spectral_radius_est  # noqa: F401
 

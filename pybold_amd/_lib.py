@@ -252,6 +252,18 @@ SIGNATURES = {
                                     _ptr, _ptr]),
     "pb_theta_fit_step": (_c_int, [_ptr, _c_int, _ptr, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_dbl,
                                    _c_dbl, _c_int, _c_int, _c_dbl, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    # one HRF per parcel (rows contiguous by parcel)
+    "pb_fista_grouped_work_len": (_c_i64, [_c_int, _c_int, _c_int]),
+    "pb_fista_grouped_waves": (_c_int, [_ptr, _c_int, _c_int]),
+    "pb_fista_grouped_plan": (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr, _ptr]),
+    "pb_fista_solve_grouped": (_c_int, [
+        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int,     # y, ldy, w, ldw, P, N
+        _ptr, _c_i64, _c_int, _ptr, _c_int,             # taps_dev, ldt, K, step_dev, G
+        _ptr, _ptr, _c_dbl, _ptr, _ptr, _c_int,         # offsets_host, offsets_dev, lbda, lbda_dev, betas_dev, n_iter
+        _ptr, _ptr, _c_i64, ctypes.c_uint, _ptr]),      # n_done, work_dev, work_len, flags, stream
+    "pb_hrf_normal_eq_w_grouped_work_len": (_c_i64, [_c_int, _c_int, _c_int]),
+    "pb_hrf_normal_eq_w_grouped": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr,
+                                            _ptr, _c_i64, _ptr, _c_i64, _ptr]),
 }
 
 _lib = None

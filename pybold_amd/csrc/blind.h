@@ -20,6 +20,7 @@
 #pragma once
 #include "common.h"
 #include "generic.h"
+#include "plan.h"
 
 namespace pb {
 
@@ -131,13 +132,18 @@ __host__ __device__ inline int ne_sum_lds_doubles(int N, int K) {
 // summation tree of block_cumsum in generic.h: same z, bit for bit, as pb_integ_op gives) and
 // also sums |w| -- part[ne] = ||w||_1 of the block's voxels, one entry more per block -- so
 // that an outer iteration of the shared-HRF loop needs no pass of its own for either.
-template <typename TY, bool FROM_W = false>
-__global__ __launch_bounds__(NE_THREADS) void normal_eq_sum_kernel(const double* z, int64_t ldz,
-                                                                   const TY* y, int64_t ldy, int V,
-                                                                   int N, int K, double* part_out) {
+// (the body sums its workgroup's voxels into ONE set: the workgroups of normal_eq_sum_kernel deal the whole batch among
+// themselves, those of the grouped form take a unit of one parcel each)
+// UNIT: the voxels u_first, u_first + u_stride, ... < V into part_out[unit] (the grouped form); else the kernel's own
+// statement -- blockIdx.x, + gridDim.x, ... into part_out[blockIdx.x] -- with the types it always had.
+template <typename TY, bool FROM_W, bool UNIT>
+__device__ __forceinline__ void normal_eq_sum_body(const double* z, int64_t ldz, const TY* y, int64_t ldy, int V, int N, int K,
+                                                   double* part_out, int unit, int u_first, int u_stride) {
+  const auto v_first = [&] { if constexpr (UNIT) return u_first; else return blockIdx.x; }();
+  const auto v_stride = [&] { if constexpr (UNIT) return u_stride; else return gridDim.x; }();
+  const int ne_out = ne_len(K) + (FROM_W ? 1 : 0);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int ne = ne_len(K);
-  const int ne_out = ne + (FROM_W ? 1 : 0);
   double l1 = 0.0;
   static_assert(NE_JB == 8 && NE_LB == 8, "ne_sk() pads every 8 samples");
   const int nz = N + NE_LB + NE_JB, ny = N + K + NE_LB + NE_JB;      // logical lengths
@@ -192,8 +198,8 @@ __global__ __launch_bounds__(NE_THREADS) void normal_eq_sum_kernel(const double*
       if (i < N) { pz[q] = zr[i]; py[q] = yr[i]; }
     }
   };
-  if (prefetch && (int)blockIdx.x < V) fetch(blockIdx.x);
-  for (int v = blockIdx.x; v < V; v += gridDim.x) {
+  if (prefetch && (int)v_first < V) fetch(v_first);
+  for (int v = v_first; v < V; v += v_stride) {
     __syncthreads();                           // previous voxel fully consumed
     if (prefetch) {
 #pragma unroll
@@ -201,7 +207,7 @@ __global__ __launch_bounds__(NE_THREADS) void normal_eq_sum_kernel(const double*
         const int i = t + q * NE_THREADS;
         if (i < N) { lz[ne_sk(i)] = pz[q]; ly[ne_sk(i)] = (double)py[q]; }
       }
-      if (v + (int)gridDim.x < V) fetch(v + gridDim.x);            // in flight during the sums below
+      if (v + (int)v_stride < V) fetch(v + v_stride);              // in flight during the sums below
     } else {
       const double* zr = z + (int64_t)v * ldz;
       const TY* yr = y + (int64_t)v * ldy;
@@ -292,7 +298,7 @@ __global__ __launch_bounds__(NE_THREADS) void normal_eq_sum_kernel(const double*
   }
   yy = block_sum(yy, red8);                    // (syncs inside: bulk[] is visible afterwards)
   if constexpr (FROM_W) l1 = block_sum(l1, red8);
-  double* part = part_out + (int64_t)blockIdx.x * ne_out;
+  double* part = part_out + (int64_t)(UNIT ? unit : blockIdx.x) * ne_out;
   for (int e = t; e < ne; e += NE_THREADS) part[e] = 0.0;            // entries with no sample
   if (FROM_W && t == 0) part[ne] = l1;
   __syncthreads();
@@ -312,6 +318,13 @@ __global__ __launch_bounds__(NE_THREADS) void normal_eq_sum_kernel(const double*
   } else if (t == 2 * K) {
     part[K * K + K] = yy;
   }
+}
+
+template <typename TY, bool FROM_W = false>
+__global__ __launch_bounds__(NE_THREADS) void normal_eq_sum_kernel(const double* z, int64_t ldz,
+                                                                   const TY* y, int64_t ldy, int V,
+                                                                   int N, int K, double* part_out) {
+  normal_eq_sum_body<TY, FROM_W, false>(z, ldz, y, ldy, V, N, K, part_out, 0, 0, 0);
 }
 
 // The same sums with ONE WAVE PER VOXEL (K <= 32): normal_eq_sum_kernel stages one voxel per
@@ -337,13 +350,13 @@ __host__ __device__ inline int ne_wave_lds_doubles(int N, int K) {
   return GEN_WAVES * ne_wave_doubles(N, K) + K * K + 2 * K + 2;
 }
 
-template <typename TY, bool FROM_W, int NEW_PE = 16, int NEW_PF = 8>
-__global__ __launch_bounds__(NE_THREADS) void normal_eq_wave_kernel(const double* z, int64_t ldz,
-                                                                    const TY* y, int64_t ldy, int V,
-                                                                    int N, int K, double* part_out) {
+// (the body: every wave sums its voxels, the four waves fold into ONE set; UNIT as in normal_eq_sum_body)
+template <typename TY, bool FROM_W, int NEW_PE, int NEW_PF, bool UNIT>
+__device__ __forceinline__ void normal_eq_wave_body(const double* z, int64_t ldz, const TY* y, int64_t ldy, int V, int N, int K,
+                                                    double* part_out, int unit, int u_first) {
+  const int ne_out = ne_len(K) + (FROM_W ? 1 : 0);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int ne = ne_len(K);
-  const int ne_out = ne + (FROM_W ? 1 : 0);
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int nz = N + NE_LB + NE_JB, ny = N + K + NE_LB + NE_JB;
   double* lz = reinterpret_cast<double*>(smem) + wv * ne_wave_doubles(N, K);
@@ -395,7 +408,7 @@ __global__ __launch_bounds__(NE_THREADS) void normal_eq_wave_kernel(const double
       if (i < N) { pz[q] = zr[i]; py[q] = yr[i]; }
     }
   };
-  const int v0 = blockIdx.x * GEN_WAVES + wv, vstride = gridDim.x * GEN_WAVES;
+  const int v0 = UNIT ? u_first + wv : blockIdx.x * GEN_WAVES + wv, vstride = UNIT ? GEN_WAVES : gridDim.x * GEN_WAVES;
   if (prefetch && v0 < V) fetch(v0);
   const int chunk = (N + NE_THREADS - 1) / NE_THREADS;
   for (int v = v0; v < V; v += vstride) {
@@ -541,7 +554,7 @@ __global__ __launch_bounds__(NE_THREADS) void normal_eq_wave_kernel(const double
   __syncthreads();
   const double* bulk = fold;
   const double* Pf = fold + 2 * K;
-  double* part = part_out + (int64_t)blockIdx.x * ne_out;
+  double* part = part_out + (int64_t)(UNIT ? unit : blockIdx.x) * ne_out;
   for (int e = t; e < ne; e += NE_THREADS) part[e] = 0.0;            // entries with no sample
   if (FROM_W && t == 0) part[ne] = fold[2 * K + K * K + 1];
   __syncthreads();
@@ -561,6 +574,64 @@ __global__ __launch_bounds__(NE_THREADS) void normal_eq_wave_kernel(const double
   } else if (t == 2 * K) {
     part[K * K + K] = fold[2 * K + K * K];
   }
+}
+
+template <typename TY, bool FROM_W, int NEW_PE = 16, int NEW_PF = 8>
+__global__ __launch_bounds__(NE_THREADS) void normal_eq_wave_kernel(const double* z, int64_t ldz,
+                                                                    const TY* y, int64_t ldy, int V,
+                                                                    int N, int K, double* part_out) {
+  normal_eq_wave_body<TY, FROM_W, NEW_PE, NEW_PF, false>(z, ldz, y, ldy, V, N, K, part_out, 0, 0);
+}
+
+// ---- one set PER PARCEL (pb_hrf_normal_eq_w_grouped): rows contiguous by parcel -------------------------------------
+// The unit table of plan.h cuts every parcel into units of at most `per` rows; workgroup u sums the rows of unit u with
+// the body of the kernels above (FROM_W: cumulative sum by pb_integ_op's tree and ||w||_1 inside the pass) into
+// part[u], and normal_eq_reduce_grouped_kernel adds the units first[g] .. first[g + 1] of parcel g in a fixed order
+// (no atomics: the result depends on the offsets and on `per` only).  A parcel of one voxel is one unit with three
+// idle waves, a parcel of tens of thousands ceil(n / per) workgroups; no per-voxel set is ever written.
+template <typename TY, int NEW_PE = 16, int NEW_PF = 8>
+__global__ __launch_bounds__(NE_THREADS) void normal_eq_wave_grouped_kernel(const double* w, int64_t ldw, const TY* y, int64_t ldy,
+                                                                            const int32_t* table, const int32_t* n_units, int N,
+                                                                            int K, double* part_out) {
+  const int unit = blockIdx.x;
+  if (unit >= *n_units) return;                  // (the whole workgroup: the grid covers the host's bound)
+  const int32_t* ut = table + GROUPED_WORDS * (int64_t)unit;
+  normal_eq_wave_body<TY, true, NEW_PE, NEW_PF, true>(w, ldw, y, ldy, ut[0] + ut[1], N, K, part_out, unit, ut[0]);
+}
+template <typename TY>
+__global__ __launch_bounds__(NE_THREADS) void normal_eq_sum_grouped_kernel(const double* w, int64_t ldw, const TY* y, int64_t ldy,
+                                                                           const int32_t* table, const int32_t* n_units, int N,
+                                                                           int K, double* part_out) {
+  const int unit = blockIdx.x;
+  if (unit >= *n_units) return;
+  const int32_t* ut = table + GROUPED_WORDS * (int64_t)unit;
+  normal_eq_sum_body<TY, true, true>(w, ldw, y, ldy, ut[0] + ut[1], N, K, part_out, unit, ut[0], 1);
+}
+
+// out[g][e] = sum of part[u][e] over the units u of parcel g.  A workgroup takes E = 2^e_log2 entries of one parcel, its
+// 256 / E slices deal the parcel's units among themselves (stride 256 / E, in order) and are folded by a fixed tree: the
+// summation order depends on the units of the parcel and on E only, never on timing.  The host picks E from the
+// largest parcel: many small parcels -> wide workgroups that copy a unit or two, one large parcel -> a tree per entry
+// as in normal_eq_reduce_kernel.  An empty parcel gives zeros.
+__global__ __launch_bounds__(NE_THREADS) void normal_eq_reduce_grouped_kernel(const double* part, const int32_t* first, int G, int ne,
+                                                                              int e_log2, double* out, int64_t ldo) {
+  __shared__ double red[NE_THREADS];
+  const int E = 1 << e_log2, S = NE_THREADS >> e_log2;
+  const int chunks = (ne + E - 1) / E;
+  const int t = threadIdx.x;
+  const int g = blockIdx.x / chunks, e = (blockIdx.x % chunks) * E + (t & (E - 1)), slice = t >> e_log2;
+  double s = 0.0;
+  if (g < G && e < ne) {
+    const int u1 = first[g + 1];
+    for (int u = first[g] + slice; u < u1; u += S) s += part[(int64_t)u * ne + e];
+  }
+  red[t] = s;
+  __syncthreads();
+  for (int h = S >> 1; h >= 1; h >>= 1) {
+    if (slice < h) red[t] += red[t + h * E];
+    __syncthreads();
+  }
+  if (slice == 0 && g < G && e < ne) out[(int64_t)g * ldo + e] = red[t];
 }
 
 // out[e] = sum_b part[b][e]: one workgroup per entry e, the blocks dealt over its threads

@@ -23,6 +23,8 @@
 #include "blind.h"
 #include "fista_mfma.h"
 #include "fista_mfma_sparse.h"
+#include "fista_mfma_grouped.h"
+#include "grouped.h"
 #include "fista_mfma2.h"
 #include "fista_mfma4.h"
 #include "path.h"
@@ -1648,6 +1650,204 @@ int pb_fista_solve_pp(const float* y_dev, int64_t ldy, double* w_dev, int64_t ld
   if (gen_lds_doubles(N, K, stop_mode, 0) > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "pb_fista_solve_pp: N=%d K=%d exceeds LDS", N, K);
   launch_generic(a, taps_dev, K, 0, false, false, P, user);
   return check_launch("fista_generic_kernel(pp)");
+}
+
+// ---- one HRF per parcel (rows contiguous by parcel; plan.h: the unit table, grouped.h: its device side) ----
+}  // extern "C"
+namespace {
+// Below this many rows a grouped call stays on the per-problem vector route: a matrix-pipe pass costs the same whatever
+// it carries (one wave per SIMD: 1.74 ms per 500 iterations at 300 scans), one problem per wave finishes up to 2 048 rows
+// in 0.37 ms, and the per-problem route runs at 0.45 .. 0.6e9 row-iterations/s beyond: the pass wins from
+// ~4 000 rows on.  (From those figures; not measured for grouped calls.)
+constexpr int GROUPED_MFMA_MIN_P = 4096;
+constexpr int NE_GROUPED_UNITS = 1024, NE_GROUPED_MIN_ROWS = 16;     // normal equations: ~1 024 workgroups, 16 rows at least each
+
+struct GroupedWork { int64_t taps, steps, first, table, total; };    // offsets in int32 words (the float64 parts first)
+GroupedWork grouped_work(int P, int G, int K) {
+  GroupedWork w;
+  w.taps = 0;
+  w.steps = w.taps + 2 * (int64_t)P * K;
+  w.first = w.steps + 2 * (int64_t)P;
+  w.table = w.first + (((int64_t)G + 2) & ~(int64_t)1);
+  w.total = w.table + pb::GROUPED_WORDS * pb::grouped_max_units(P, G, pb::GROUPED_WAVE_ROWS);
+  return w;
+}
+// first [G + 1] and table [3 * units] of a grouped call from the offsets in device memory (grouped.h)
+void launch_grouped_table(const int32_t* offsets_dev, int G, int P, int per, int u_max, int32_t* first, int32_t* table, hipStream_t st) {
+  hipLaunchKernelGGL(pb::grouped_first_kernel, dim3(1), dim3(pb::GROUPED_TABLE_THREADS), 0, st, offsets_dev, G, P, per, u_max, first);
+  if (u_max > 0)
+    hipLaunchKernelGGL(pb::grouped_units_kernel, dim3((unsigned)((u_max + pb::GROUPED_TABLE_THREADS - 1) / pb::GROUPED_TABLE_THREADS)),
+                       dim3(pb::GROUPED_TABLE_THREADS), 0, st, offsets_dev, G, P, per, first, table);
+}
+int ne_grouped_rows(int V) {
+  const int per = (V + NE_GROUPED_UNITS - 1) / NE_GROUPED_UNITS;
+  return per < NE_GROUPED_MIN_ROWS ? NE_GROUPED_MIN_ROWS : per;
+}
+// float64 work buffer of the grouped normal equations: first [G + 1] and the unit table (int32), then the units' sets
+struct NeGroupedWork { int64_t max_units, part, total; };            // `part`, `total` in doubles
+NeGroupedWork ne_grouped_work(int V, int G, int K) {
+  NeGroupedWork w;
+  w.max_units = pb::grouped_max_units(V, G, ne_grouped_rows(V));
+  w.part = ((int64_t)G + 2 + pb::GROUPED_WORDS * w.max_units + 1) / 2;
+  w.total = w.part + w.max_units * (pb::ne_len(K) + 1);
+  return w;
+}
+}  // namespace
+extern "C" {
+
+int64_t pb_fista_grouped_work_len(int P, int G, int K) { return (P >= 0 && G >= 0 && K >= 1) ? grouped_work(P, G, K).total : 0; }
+
+int pb_fista_grouped_plan(const int32_t* offsets_host, int G, int P, int per, int32_t* table_out, int32_t* first_out) {
+  if (P < 0 || per < 1 || !pb::grouped_offsets_ok(offsets_host, G, P)) return -1;
+  return pb::grouped_table(offsets_host, G, P, per, table_out, first_out);
+}
+
+int pb_fista_grouped_waves(const int32_t* offsets_host, int G, int P) {
+  return pb_fista_grouped_plan(offsets_host, G, P, pb::GROUPED_WAVE_ROWS, nullptr, nullptr);
+}
+
+int pb_fista_solve_grouped(const float* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int P, int N,
+                           const double* taps_dev, int64_t ldt, int K, const double* step_dev, int G,
+                           const int32_t* offsets_host, const int32_t* offsets_dev, double lbda,
+                           const double* lbda_dev, const double* betas_dev, int n_iter, int32_t* n_done_dev,
+                           int32_t* work_dev, int64_t work_len, unsigned flags, void* stream) {
+  if (P < 0 || N < 1 || K < 1 || n_iter < 0 || G < 0)
+    return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: bad size (P=%d N=%d K=%d n_iter=%d G=%d)", P, N, K, n_iter, G);
+  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: more than 2^25 problems per launch");
+  if (ldy < N || ldw < N || ldt < K) return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: leading dimension too small");
+  if (!pb::grouped_offsets_ok(offsets_host, G, P))
+    return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: offsets must run 0 = offsets[0] <= ... <= offsets[G] = P (host memory)");
+  if (P == 0) return PB_OK;
+  if (!y_dev || !w_dev || !taps_dev || !step_dev || !offsets_dev || !work_dev || (n_iter > 0 && !betas_dev))
+    return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: NULL pointer");
+  const GroupedWork wl = grouped_work(P, G, K);
+  if (work_len < wl.total || (reinterpret_cast<uintptr_t>(work_dev) & 7) != 0)
+    return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: work buffer must hold %lld int32 words (pb_fista_grouped_work_len), 8-byte aligned",
+                (long long)wl.total);
+  const grouped_launch_fn mf = (n_done_dev && !(flags & FLAGS_VECTOR_ONLY)) ? pick_mfma_grouped(N, K) : nullptr;
+  const bool forced = (flags & PB_FLAG_FORCE_MFMA) != 0;
+  if (forced && !mf)
+    return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: no matrix-pipe form for N=%d K=%d (129 .. 310 scans, K <= 33, n_done_dev given)", N, K);
+  const bool use_mfma = mf && (forced || P >= GROUPED_MFMA_MIN_P);
+  const bool resolve = !(flags & PB_FLAG_CERT_NO_RESOLVE);
+  const hipStream_t user = (hipStream_t)stream;
+  int32_t* first = work_dev + wl.first;
+  int32_t* table = work_dev + wl.table;
+  const int32_t* n_units_dev = first + G;
+  double* taps_rows = reinterpret_cast<double*>(work_dev + wl.taps);
+  double* step_rows = reinterpret_cast<double*>(work_dev + wl.steps);
+  const int units = pb::grouped_table(offsets_host, G, P, pb::GROUPED_WAVE_ROWS, nullptr, nullptr);     // (P > 0: at least one)
+  launch_grouped_table(offsets_dev, G, P, pb::GROUPED_WAVE_ROWS, (int)pb::grouped_max_units(P, G, pb::GROUPED_WAVE_ROWS), first, table, user);
+  // Whole rounds of waves (one per SIMD) go to the matrix pipe; a last partial round costs a whole pass there whatever it
+  // carries, so up to GROUPED_MFMA_MIN_P rows of it go to the vector forms instead, behind the rounds (the split of
+  // plan_pieces_mfma; not under PB_FLAG_ONE_LAUNCH / _FORCE_MFMA).  `row_cut`: the first row of the first wave left out.
+  int main_units = units, row_cut = P;
+  if (use_mfma && !forced && !(flags & PB_FLAG_ONE_LAUNCH)) {
+    const int round = (int)wave_slots() / 2;
+    const int whole = units / round * round;
+    if (whole > 0 && whole < units) {
+      int u = 0, cut = P;
+      for (int g = 0; g < G; ++g) {
+        const int n = (offsets_host[g + 1] - offsets_host[g] + pb::GROUPED_WAVE_ROWS - 1) / pb::GROUPED_WAVE_ROWS;
+        if (u + n > whole) { cut = offsets_host[g] + (whole - u) * pb::GROUPED_WAVE_ROWS; break; }
+        u += n;
+      }
+      if (P - cut <= GROUPED_MFMA_MIN_P) { main_units = whole; row_cut = cut; }
+    }
+  }
+  if (!use_mfma || resolve || row_cut < P)
+    hipLaunchKernelGGL(pb::grouped_expand_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, user, table, n_units_dev, taps_dev,
+                       ldt, K, step_dev, taps_rows, step_rows);
+  int rc = check_launch("pb_fista_solve_grouped: unit table");
+  if (rc != PB_OK) return rc;
+  const unsigned vector_flags = flags & ~(PB_FLAG_FORCE_MFMA | PB_FLAG_NO_MFMA);
+  if (!use_mfma)
+    return pb_fista_solve_pp(y_dev, ldy, w_dev, ldw, P, N, taps_rows, K, K, step_rows, lbda, lbda_dev, betas_dev, n_iter, PB_STOP_NONE,
+                             0.0, n_done_dev, vector_flags, stream);
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, 1, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, PB_STOP_NONE, 0.0, n_done_dev, flags);
+  a.y = y_dev; a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = 0;
+  a.perm = table; a.n_dense = n_units_dev; a.grid_slots = main_units;     // (whole rounds: a multiple of the four waves of a workgroup)
+  if (mf(a, K, user) != 0) return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: the matrix-pipe kernel rejected its launch");
+  rc = check_launch("fista_mfma_kernel(grouped)");
+  if (rc != PB_OK) return rc;
+  // the per-problem vector forms, every row with its parcel's taps: the rows behind the whole rounds, then what the
+  // guards handed back (n_done = -1)
+  pb::FistaArgs b = fista_args(P, N, K, n_iter, 1, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, PB_STOP_NONE, 0.0, n_done_dev, flags);
+  b.y = y_dev; b.taps_pp = taps_rows; b.ldt = K; b.step_vec = step_rows; b.step_shared = 0;
+  if (row_cut < P) {
+    const Route rr = route_pp(N, K, P - row_cut, false, PB_STOP_NONE, true, 0u);
+    if (rr.path != PATH_PIECES && rr.path != PATH_WIDE)
+      return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: no vector form for N=%d K=%d", N, K);
+    pb::FistaArgs c = b;
+    c.p0 = row_cut;
+    rc = launch(DeviceTapsForms{rr, "pb_fista_solve_grouped", K, PB_STOP_NONE}, rr.path == PATH_WIDE ? FORM_WIDE : rr.one_form, c, user);
+    if (rc != PB_OK) return rc;
+  }
+  if (!resolve) return rc;
+  b.P = row_cut;
+  b.only_flagged = 1;
+  const Route r = route_pp(N, K, row_cut, false, PB_STOP_NONE, true, 0u);
+  const DeviceTapsForms lf{r, "pb_fista_solve_grouped", K, PB_STOP_NONE};
+  if (r.fe) return launch(lf, FORM_FAST1, b, user, true);
+  if (r.we) return launch(lf, FORM_WIDE, b, user, true);
+  return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: no vector form re-solves N=%d K=%d", N, K);
+}
+
+int64_t pb_hrf_normal_eq_w_grouped_work_len(int V, int G, int K) {
+  return (V >= 0 && G >= 0 && K >= 1) ? ne_grouped_work(V, G, K).total : 0;
+}
+
+int pb_hrf_normal_eq_w_grouped(const double* w_dev, int64_t ldw, const float* y_dev, int64_t ldy, int V,
+                               int N, int K, int G, const int32_t* offsets_host, const int32_t* offsets_dev,
+                               double* work_dev, int64_t work_len, double* out_dev, int64_t ldo, void* stream) {
+  if (V < 0 || N < 1 || K < 1 || K > 127 || G < 0 || ldw < N || ldy < N)
+    return fail(PB_ERR_INVALID, "pb_hrf_normal_eq_w_grouped: bad size (V=%d N=%d K=%d G=%d)", V, N, K, G);
+  const int ne = pb::ne_len(K) + 1;
+  if (ldo < ne) return fail(PB_ERR_INVALID, "pb_hrf_normal_eq_w_grouped: ldo < %d", ne);
+  if (!pb::grouped_offsets_ok(offsets_host, G, V))
+    return fail(PB_ERR_INVALID, "pb_hrf_normal_eq_w_grouped: offsets must run 0 = offsets[0] <= ... <= offsets[G] = V (host memory)");
+  if (G == 0) return PB_OK;
+  const bool wave_form = ne_wave_form(N, K);
+  const int64_t nd = wave_form ? (int64_t)pb::ne_wave_lds_doubles(N, K) : (int64_t)pb::ne_sum_lds_doubles(N, K);
+  if (nd > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "pb_hrf_normal_eq_w_grouped: N=%d K=%d exceeds LDS", N, K);
+  if (!out_dev || !offsets_dev || !work_dev || (V > 0 && (!w_dev || !y_dev)))
+    return fail(PB_ERR_INVALID, "pb_hrf_normal_eq_w_grouped: NULL pointer");
+  const NeGroupedWork wl = ne_grouped_work(V, G, K);
+  if (work_len < wl.total)
+    return fail(PB_ERR_INVALID, "pb_hrf_normal_eq_w_grouped: work buffer must hold %lld doubles (pb_hrf_normal_eq_w_grouped_work_len)",
+                (long long)wl.total);
+  const hipStream_t user = (hipStream_t)stream;
+  const int per = ne_grouped_rows(V);
+  int32_t* first = reinterpret_cast<int32_t*>(work_dev);
+  int32_t* table = first + (((int64_t)G + 2) & ~(int64_t)1);
+  double* part = work_dev + wl.part;
+  const int units = pb::grouped_table(offsets_host, G, V, per, nullptr, nullptr);
+  launch_grouped_table(offsets_dev, G, V, per, (int)wl.max_units, first, table, user);
+  if (units > 0) {
+    const size_t lds = (size_t)nd * sizeof(double);
+    if (wave_form && K * K <= 64 * 12 && N <= 64 * 5)
+      hipLaunchKernelGGL((pb::normal_eq_wave_grouped_kernel<float, 12, 5>), dim3(units), dim3(pb::NE_THREADS), lds, user, w_dev, ldw,
+                         y_dev, ldy, table, first + G, N, K, part);
+    else if (wave_form)
+      hipLaunchKernelGGL((pb::normal_eq_wave_grouped_kernel<float>), dim3(units), dim3(pb::NE_THREADS), lds, user, w_dev, ldw, y_dev,
+                         ldy, table, first + G, N, K, part);
+    else
+      hipLaunchKernelGGL((pb::normal_eq_sum_grouped_kernel<float>), dim3(units), dim3(pb::NE_THREADS), lds, user, w_dev, ldw, y_dev,
+                         ldy, table, first + G, N, K, part);
+  }
+  // second stage: entries per workgroup from the largest parcel (few units: wide workgroups; many: a tree per entry),
+  // raised until the grid stays below 2^16 workgroups
+  int max_units = 0;
+  for (int g = 0; g < G; ++g) {
+    const int n = (offsets_host[g + 1] - offsets_host[g] + per - 1) / per;
+    max_units = n > max_units ? n : max_units;
+  }
+  int e_log2 = max_units <= 4 ? 8 : (max_units <= 16 ? 6 : (max_units <= 64 ? 4 : (max_units <= 256 ? 2 : 0)));
+  while (e_log2 < 8 && (int64_t)G * ((ne + (1 << e_log2) - 1) >> e_log2) > 65536) ++e_log2;
+  const int64_t chunks = (ne + (1 << e_log2) - 1) >> e_log2;
+  hipLaunchKernelGGL(pb::normal_eq_reduce_grouped_kernel, dim3((unsigned)(G * chunks)), dim3(pb::NE_THREADS), 0, user, part, first, G,
+                     ne, e_log2, out_dev, ldo);
+  return check_launch("pb_hrf_normal_eq_w_grouped");
 }
 
 int64_t pb_fista_path_work_len(int P) { return P >= 0 ? work_layout(P, P).total : 0; }     // (enough for any y_rep)

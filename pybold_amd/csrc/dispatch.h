@@ -66,6 +66,10 @@ PB_MFMA(5) PB_MFMA(6) PB_MFMA(7) PB_MFMA(8) PB_MFMA(9) PB_MFMA(10)
 #define PB_MFMA(NB) extern template int launch_mfma_st<NB>(const FistaArgs&, const double*, int, bool, hipStream_t);
 PB_MFMA(5) PB_MFMA(6) PB_MFMA(7) PB_MFMA(8) PB_MFMA(9) PB_MFMA(10)
 #undef PB_MFMA
+// (fista_mfma_grouped.h: the same two kernels with one HRF per parcel, pb_fista_solve_grouped)
+#define PB_MFMA(NB) extern template int launch_mfma_grouped<NB>(const FistaArgs&, int, hipStream_t);
+PB_MFMA(5) PB_MFMA(6) PB_MFMA(7) PB_MFMA(8) PB_MFMA(9) PB_MFMA(10)
+#undef PB_MFMA
 }
 namespace pb {
 #define PB_MFMA2(A, B) extern template int launch_mfma2<A, B>(const FistaArgs&, const double*, int, bool, hipStream_t);
@@ -119,6 +123,15 @@ launch_fn pick_mfma(int N, int K, bool stop_rule, bool dense_tiles = false) {
   const int nb = (N + pb::MFMA_SPAN - 1) / pb::MFMA_SPAN;
   if (K < 1 || K > MFMA_K3 || (K > MFMA_K2 && stop_rule) || N <= 128 || nb > 10) return nullptr;   // (129 .. 310 scans: 5 .. 10 blocks)
   return (dense_tiles ? tab : tab_st)[nb - 5];
+}
+// the grouped z-step (one HRF per parcel): 129 .. 310 scans, K <= 33 (two near tiles), plain solves
+typedef int (*grouped_launch_fn)(const pb::FistaArgs&, int K, hipStream_t);
+grouped_launch_fn pick_mfma_grouped(int N, int K) {
+  static const grouped_launch_fn tab[] = {&pb::launch_mfma_grouped<5>, &pb::launch_mfma_grouped<6>, &pb::launch_mfma_grouped<7>,
+                                          &pb::launch_mfma_grouped<8>, &pb::launch_mfma_grouped<9>, &pb::launch_mfma_grouped<10>};
+  const int nb = (N + pb::MFMA_SPAN - 1) / pb::MFMA_SPAN;
+  if (K < 1 || K > MFMA_K2 || N <= 128 || nb > 10) return nullptr;
+  return tab[nb - 5];
 }
 }  // namespace
 namespace pb {

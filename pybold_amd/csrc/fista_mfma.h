@@ -47,6 +47,7 @@
 // Reference: pybold/bold_signal.py:62-72, pybold/linear.py:73-113, pybold/convolution.py:105-132.
 #pragma once
 #include "mfma_core.h"
+#include "plan.h"                                // (GROUPED: the unit table)
 #ifndef PB_MFMA_CHECKS
 #define PB_MFMA_CHECKS 1
 #endif
@@ -104,22 +105,38 @@ constexpr int MFMA_SSHIFT = 9;      // the sums ride scaled by 2^-9: below the l
 //   (1 + beta) ||d||: two float64 multiply-adds per sample next to the update.  A problem that meets the rule is
 //   written out at that moment (after a range / accuracy check of its own) and its lanes keep iterating, results
 //   discarded -- as in fista_fast.h.  Plain variant only (no cost trace, taps as kernel arguments, two near tiles).
-template <int NB, bool WITH_J = false, bool TAPS_DEV = false, bool CERT = false, int NT = 2, bool LOOPS = false>
+// GROUPED (pb_fista_solve_grouped; with TAPS_DEV, plain variant): rows contiguous by parcel, one HRF and one step per
+//   parcel (a.taps_pp + g a.ldt, a.step_vec[g]).  A wave's 16 problems share a parcel: wave u takes its first row, its
+//   number of rows and its parcel from the unit table (plan.h: a.perm[3 u ..], built on the device; *a.n_dense units),
+//   slots beyond its rows are dead (they read the wave's first row and store nothing), waves beyond the table leave.
+__device__ __forceinline__ int grouped_problem(const FistaArgs& a, int wave, int v, bool& live, int& parcel) {
+  const int32_t* ut = a.perm + GROUPED_WORDS * (int64_t)__builtin_amdgcn_readfirstlane(wave);
+  live = v < ut[1];
+  parcel = ut[2];
+  return ut[0] + (live ? v : 0);
+}
+template <int NB, bool WITH_J = false, bool TAPS_DEV = false, bool CERT = false, int NT = 2, bool LOOPS = false, bool GROUPED = false>
 __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs a, MfmaTaps tp) {
   static_assert(NT == 2 || NT == 3, "two near tiles (K <= 33) or three (K <= 64)");
+  static_assert(!GROUPED || (TAPS_DEV && !WITH_J && !CERT && !LOOPS), "parcels ride the plain variant with taps in device memory");
   static_assert(!LOOPS || (!WITH_J && !TAPS_DEV && !CERT && NT == 2), "the stop rule rides the plain variant");
   constexpr int LCW = NT == 2 ? 64 : 96;           // cumulative taps kept per wave: lags 0 .. 32 NT - 1
   static_assert(!CERT || (WITH_J && !TAPS_DEV), "the certificate runs in the rotated (cost trace) loop");
   const int lane = threadIdx.x & 63;
   const int v = lane & 15, g = lane >> 4;
   const int wave = (int)((blockIdx.x * 256 + threadIdx.x) >> 6);
-  int s0, n_list;                                 // this launch's slots [s0, n_list) of its list (the batch itself without a partition)
+  int s0 = 0, n_list = 0;                         // this launch's slots [s0, n_list) of its list (the batch itself without a partition)
+  if constexpr (!GROUPED) {
   launch_slots(a, s0, n_list);
   // the whole wave lies beyond the list: leave (no workgroup barrier anywhere below; a SCALAR branch -- the wave index is
   // the same in every lane -- so that the body does not run under a saved exec mask)
   if (__builtin_amdgcn_readfirstlane(wave) * 16 + s0 >= n_list) return;
+  } else {
+    if (__builtin_amdgcn_readfirstlane(wave) >= *a.n_dense) return;      // (beyond the unit table: a scalar branch too)
+  }
   bool live;
-  const int p = slot_to_problem(a, wave * 16 + v + s0, n_list, live);
+  int parcel = 0;                                 // GROUPED: this wave's parcel (the same in every lane: scalar loads)
+  const int p = GROUPED ? grouped_problem(a, wave, v, live, parcel) : slot_to_problem(a, wave * 16 + v + s0, n_list, live);
   const int tb = 8 * g;                          // this lane's first slot inside a block of 32 slots
   const bool g3 = g == 3;                        // lane group 3 holds the sum slot (slot 31 = its j = 7)
 
@@ -140,12 +157,13 @@ __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs
   double step = a.step, g_scale = tp.g_scale;
   float y_scale = tp.y_scale;
   if constexpr (TAPS_DEV) {
+    const double* taps_w = GROUPED ? a.taps_pp + (int64_t)parcel * a.ldt : a.taps_pp;     // this wave's HRF
     double run = 0.0, run2 = 0.0;
-    for (int k = 0; k <= lane && k < a.K; ++k) run += (double)(float)a.taps_pp[k];
+    for (int k = 0; k <= lane && k < a.K; ++k) run += (double)(float)taps_w[k];
     float cm = fabsf((float)run);
     if constexpr (NT == 3) {                       // lags 64 .. 95 (K <= 64: sum of the first lane + 65 taps)
       run2 = run;
-      for (int k = lane + 1; k <= lane + 64 && k < a.K; ++k) run2 += (double)(float)a.taps_pp[k];
+      for (int k = lane + 1; k <= lane + 64 && k < a.K; ++k) run2 += (double)(float)taps_w[k];
       cm = fmaxf(cm, fabsf((float)run2));
     }
 #pragma unroll
@@ -157,7 +175,7 @@ __global__ __launch_bounds__(256) PB_MFMA_KATTR void fista_mfma_kernel(FistaArgs
     if constexpr (NT == 3) { if (lane < 32) lc[64 + lane] = (float)ldexp(run2, sa); }
     g_scale = ldexp(1.0, -2 * sa);
     y_scale = ldexpf(1.0f, sa);
-    step = a.step_vec[0];
+    step = a.step_vec[GROUPED ? parcel : 0];
   } else {
     lc[lane] = tp.c[lane];
     if constexpr (NT == 3) lc[64 + (lane & 31)] = tp.c[64 + (lane & 31)];      // (every lane: no exec-masked region here, fista_mfma4.h says why)

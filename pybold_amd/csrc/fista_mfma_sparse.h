@@ -31,16 +31,23 @@ __device__ __forceinline__ f4 smfmac_part(const Frag& A, int idx, const u8& bh, 
 
 // TAPS_DEV: the HRF and the step are read from device memory (a.taps_pp: K float64 shared by every problem,
 // a.step_vec[0]), as in fista_mfma_kernel: the shared-HRF z-step computes what the host-taps solve computes, bit for bit.
-template <int NB, bool TAPS_DEV = false>
+// GROUPED: one HRF and one step per parcel, a wave's problems from the unit table -- fista_mfma_kernel's GROUPED, restated.
+template <int NB, bool TAPS_DEV = false, bool GROUPED = false>
 __global__ __launch_bounds__(256) void fista_mfma_sparse_kernel(FistaArgs a, MfmaTaps tp) {
+  static_assert(!GROUPED || TAPS_DEV, "parcels take their taps from device memory");
   const int lane = threadIdx.x & 63;
   const int v = lane & 15, g = lane >> 4;
   const int wave = (int)((blockIdx.x * 256 + threadIdx.x) >> 6);
-  int s0, n_list;
+  int s0 = 0, n_list = 0;
+  if constexpr (!GROUPED) {
   launch_slots(a, s0, n_list);
   if (__builtin_amdgcn_readfirstlane(wave) * 16 + s0 >= n_list) return;      // (a scalar branch, as in fista_mfma_kernel)
+  } else {
+    if (__builtin_amdgcn_readfirstlane(wave) >= *a.n_dense) return;
+  }
   bool live;
-  const int p = slot_to_problem(a, wave * 16 + v + s0, n_list, live);
+  int parcel = 0;
+  const int p = GROUPED ? grouped_problem(a, wave, v, live, parcel) : slot_to_problem(a, wave * 16 + v + s0, n_list, live);
   const int tb = 8 * g;
   const bool g3 = g == 3;
 
@@ -50,8 +57,9 @@ __global__ __launch_bounds__(256) void fista_mfma_sparse_kernel(FistaArgs a, Mfm
   double step = a.step, g_scale = tp.g_scale;
   float y_scale = tp.y_scale;
   if constexpr (TAPS_DEV) {                       // (fista_mfma_kernel's prologue for two near tiles, restated)
+    const double* taps_w = GROUPED ? a.taps_pp + (int64_t)parcel * a.ldt : a.taps_pp;
     double run = 0.0;
-    for (int k = 0; k <= lane && k < a.K; ++k) run += (double)(float)a.taps_pp[k];
+    for (int k = 0; k <= lane && k < a.K; ++k) run += (double)(float)taps_w[k];
     float cm = fabsf((float)run);
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) cm = fmaxf(cm, __shfl_xor(cm, o, 64));
@@ -61,7 +69,7 @@ __global__ __launch_bounds__(256) void fista_mfma_sparse_kernel(FistaArgs a, Mfm
     lc[lane] = (float)ldexp(run, sa);
     g_scale = ldexp(1.0, -2 * sa);
     y_scale = ldexpf(1.0f, sa);
-    step = a.step_vec[0];
+    step = a.step_vec[GROUPED ? parcel : 0];
   } else {
     lc[lane] = tp.c[lane];
   }

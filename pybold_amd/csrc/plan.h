@@ -313,4 +313,69 @@ PB_HD int plan_to_candidates(const Piece* pc, int npc, int32_t* ranges) {
   return rc;
 }
 
+// ---- grouped calls: rows contiguous by parcel, offsets[G + 1] their ranges ---------------------------------------
+// A grouped call cuts every parcel into UNITS of at most `per` consecutive rows that never cross a parcel: the 16
+// problems of a matrix-pipe wave (pb_fista_solve_grouped: a wave builds its operator tiles from ONE HRF, so its problems
+// share a parcel), or the rows one workgroup of pb_hrf_normal_eq_w_grouped sums.  The unit table holds three words per
+// unit -- first row, rows (1 .. per), parcel -- and first[g] the first unit of parcel g (first[G]: units in all).  Only
+// the last unit of a parcel can be short: its missing rows are the dead slots of its wave.  An empty parcel has no
+// unit.  Every range is clamped into [0, P] and made non-decreasing on the way, so a table built from ANY offsets
+// addresses rows of the batch only (the entry points check the host copy of the offsets; the device copy is the
+// caller's word).  The functions compile for the host (pb_fista_grouped_plan, tests/test_grouped_host.py) and for the
+// device: grouped.h builds the table there in two small launches -- grouped_first_kernel numbers every parcel's first
+// unit with grouped_fill behind a scan of 256 chunk counts, grouped_units_kernel writes one unit per thread -- so the
+// offsets never pass through the host inside a captured loop.
+constexpr int GROUPED_WORDS = 3;
+constexpr int GROUPED_WAVE_ROWS = 16;
+
+PB_HD void grouped_range(const int32_t* offsets, int g, int P, int& lo, int& hi) {
+  lo = offsets[g];
+  hi = offsets[g + 1];
+  lo = lo < 0 ? 0 : (lo > P ? P : lo);
+  hi = hi < lo ? lo : (hi > P ? P : hi);
+}
+
+// the most units any offsets can give: sum ceil(n_g / per) <= floor(P / per) + G
+PB_HD int64_t grouped_max_units(int P, int G, int per) { return (int64_t)P / per + G; }
+
+// units of the parcels [g0, g1), numbered from u0 on; `table` / `first` may be nullptr (count only).  Returns the
+// number of the unit behind the last one.  No unit from u_max on is written and every number saturates there: with
+// offsets that pass grouped_offsets_ok the bound grouped_max_units is never reached, with any others (ranges that
+// overlap) the table still ends where its buffer does.
+PB_HD int grouped_fill(const int32_t* offsets, int g0, int g1, int P, int per, int u0, int u_max, int32_t* table, int32_t* first) {
+  int u = u0 < u_max ? u0 : u_max;
+  for (int g = g0; g < g1; ++g) {
+    int lo, hi;
+    grouped_range(offsets, g, P, lo, hi);
+    if (first) first[g] = u;
+    const int n = (hi - lo + per - 1) / per;
+    const int m = n < u_max - u ? n : u_max - u;
+    if (table) {
+      for (int i = 0; i < m; ++i) {
+        const int r = lo + i * per;
+        table[GROUPED_WORDS * (int64_t)(u + i)] = r;
+        table[GROUPED_WORDS * (int64_t)(u + i) + 1] = hi - r < per ? hi - r : per;
+        table[GROUPED_WORDS * (int64_t)(u + i) + 2] = g;
+      }
+    }
+    u += m;
+  }
+  return u;
+}
+
+// the whole table in one go (host; checked offsets); returns the number of units
+inline int grouped_table(const int32_t* offsets, int G, int P, int per, int32_t* table, int32_t* first) {
+  const int u = grouped_fill(offsets, 0, G, P, per, 0, (int)grouped_max_units(P, G, per), table, first);
+  if (first) first[G] = u;
+  return u;
+}
+
+// offsets a grouped entry point accepts: 0 = offsets[0] <= offsets[1] <= ... <= offsets[G] = P
+inline bool grouped_offsets_ok(const int32_t* offsets, int G, int P) {
+  if (G < 0 || !offsets || offsets[0] != 0 || offsets[G] != P) return false;
+  for (int g = 0; g < G; ++g)
+    if (offsets[g + 1] < offsets[g]) return false;
+  return true;
+}
+
 }  // namespace pb

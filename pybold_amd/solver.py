@@ -1275,3 +1275,124 @@ def theta_fit_step(msg, t_r, dur, bounds, n_scans, lbda, n_refine=3, dt=0.001, p
                                    taps.data_ptr(), step.data_ptr(), jc.data_ptr(), _stream_ptr(dev))
     _lib.check(rc, "pb_theta_fit_step")
     return theta, cost, taps, step, jc
+
+
+# ---- one HRF per parcel: rows contiguous by parcel (pb_fista_solve_grouped, pb_hrf_normal_eq_w_grouped) -------------
+class ParcelOffsets:
+    """Row ranges of the parcels of a grouped call, once on the host (checked, sizes the launches) and once on the
+    device (what the kernels' unit table is built from): parcel ``g`` owns the rows ``offsets[g] .. offsets[g + 1] - 1``,
+    ``0 = offsets[0] <= ... <= offsets[G] = V``.  Built once per batch, so that a loop of grouped calls uploads nothing."""
+
+    def __init__(self, offsets, dev):
+        host = np.ascontiguousarray(np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets).ravel(), dtype=np.int64)
+        if host.size < 1 or host[0] != 0 or np.any(np.diff(host) < 0) or host[-1] >= 2 ** 31:
+            raise ValueError("offsets must run 0 = offsets[0] <= offsets[1] <= ... <= offsets[G] = number of rows")
+        self.host = host.astype(np.int32)
+        self.dev = torch.from_numpy(self.host).to(dev)
+        self.G = int(host.size - 1)
+        self.rows = int(host[-1])
+        self.sizes = np.diff(host)
+
+    def waves(self):
+        """Matrix-pipe waves of a grouped solve: ``sum ceil(n_g / 16)``."""
+        return int(_lib.load().pb_fista_grouped_waves(self.host.ctypes.data, self.G, self.rows))
+
+
+def _parcel_offsets(offsets, dev, rows):
+    po = offsets if isinstance(offsets, ParcelOffsets) else ParcelOffsets(offsets, dev)
+    if po.rows != rows or po.dev.device != dev:
+        raise ValueError("offsets end at row %d on %s, the batch has %d rows on %s" % (po.rows, po.dev.device, rows, dev))
+    return po
+
+
+def grouped_wave_table(offsets, per=16):
+    """The unit table of a grouped call from the host build of its planner (``pb_fista_grouped_plan``; no GPU):
+    ``(table (units, 3) int32 -- first row, rows <= per, parcel --, first (G + 1,) int32 -- first unit of every parcel)``.
+    ``per = 16``: the wave table of :func:`fista_solve_grouped`."""
+    lib = _lib.load()
+    host = np.ascontiguousarray(np.asarray(offsets).ravel(), dtype=np.int32)
+    G, rows = host.size - 1, int(host[-1]) if host.size else -1
+    n = lib.pb_fista_grouped_plan(host.ctypes.data, G, rows, int(per), None, None) if host.size else -1
+    if n < 0:
+        raise ValueError("offsets must run 0 = offsets[0] <= offsets[1] <= ... <= offsets[G] = number of rows")
+    table = np.full((n, 3), -1, dtype=np.int32)
+    first = np.full((G + 1,), -1, dtype=np.int32)
+    assert lib.pb_fista_grouped_plan(host.ctypes.data, G, rows, int(per), table.ctypes.data, first.ctypes.data) == n
+    return table, first
+
+
+def fista_solve_grouped(Y, taps, steps, offsets, lbda, n_iter, W0=None, force=None, inplace=False, work=None):
+    """:func:`fista_solve_pp` with one HRF and one step per PARCEL: the rows of ``Y`` (float32 CUDA ``(V, N)``) are
+    contiguous by parcel, ``offsets`` (``G + 1`` integers or a :class:`ParcelOffsets`) their ranges, ``taps`` float64
+    CUDA ``(G, K)``, ``steps`` float64 CUDA ``(G,)``.  129 .. 310 scans with up to 33 taps run on the matrix pipe, a
+    wave's 16 problems all of one parcel (calls of 4 096 rows or more; ``force="mfma"`` / ``"mfmaonly"``: whatever the
+    number of rows, an error for other shapes), everything else -- and ``force="valu"`` -- on the per-problem vector
+    forms with each row's parcel's taps.  ``force`` may also be raw ``PB_FLAG_*`` bits.  No stop rule.  ``work``: an int32 CUDA buffer of
+    ``pb_fista_grouped_work_len(V, G, K)`` words to reuse.  Returns ``(W, n_done)``."""
+    lib = _lib.load()
+    Y = _rows(Y, torch.float32, "Y")
+    dev = Y.device
+    V, N = Y.shape
+    taps = _rows(taps, torch.float64, "taps")
+    po = _parcel_offsets(offsets, dev, V)
+    G, K = taps.shape
+    if G != po.G:
+        raise ValueError("taps must have one row per parcel (%d), got %d" % (po.G, G))
+    steps = steps.to(device=dev, dtype=torch.float64).contiguous().ravel()
+    if steps.numel() != G:
+        raise ValueError("steps must have one entry per parcel")
+    cold = 0
+    if W0 is None:
+        W = torch.empty((V, N), dtype=torch.float64, device=dev)
+        cold = PB_FLAG_COLD_START
+    else:
+        W = _rows(W0, torch.float64, "W0")
+        if not inplace or W.data_ptr() != W0.data_ptr():
+            W = W.clone()
+        if W.shape != (V, N):
+            raise ValueError("W0 must be %s, got %s" % ((V, N), tuple(W.shape)))
+    lbda_dev, lbda_scalar = None, 0.0
+    if np.ndim(lbda) == 0 and not torch.is_tensor(lbda):
+        lbda_scalar = float(lbda)
+    else:
+        lbda_dev = torch.as_tensor(lbda, dtype=torch.float64).to(dev).contiguous().ravel()
+    betas = _betas_on(dev, n_iter)
+    n_done = torch.empty((V,), dtype=torch.int32, device=dev)
+    need = int(lib.pb_fista_grouped_work_len(V, G, K))
+    if work is None or work.dtype != torch.int32 or work.numel() < need or work.device != dev:
+        work = torch.empty((max(need, 2),), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.pb_fista_solve_grouped(
+            Y.data_ptr(), _ld(Y) if V else N, W.data_ptr(), _ld(W) if V else N, V, N, taps.data_ptr(), _ld(taps) if G else K, K,
+            steps.data_ptr(), G, po.host.ctypes.data, po.dev.data_ptr(), lbda_scalar,
+            lbda_dev.data_ptr() if lbda_dev is not None else None, betas.data_ptr(), int(n_iter), n_done.data_ptr(),
+            work.data_ptr(), work.numel(), (force if isinstance(force, int) else _FORCE[force]) | cold, _stream_ptr(dev))
+    _lib.check(rc, "pb_fista_solve_grouped")
+    return W, n_done
+
+
+def hrf_normal_eq_w_grouped(W, Y, n_taps, offsets, work=None, out=None):
+    """:func:`hrf_normal_eq_w` with one set per parcel (rows contiguous by parcel, ``offsets`` as in
+    :func:`fista_solve_grouped`): float64 ``(G, K*K + K + 2)``, row ``g`` = the normal equations of parcel ``g``'s rows
+    followed by their ``sum ||w_v||_1``, from ONE pass over ``(W, Y)`` with a fixed summation order."""
+    lib = _lib.load()
+    W = _rows(W, torch.float64, "W")
+    Y = _rows(Y, torch.float32, "Y")
+    dev = W.device
+    V, N = W.shape
+    K = int(n_taps)
+    po = _parcel_offsets(offsets, dev, V)
+    ne = int(lib.pb_hrf_normal_eq_len(K)) + 1
+    if out is None:
+        out = torch.empty((po.G, ne), dtype=torch.float64, device=dev)
+    if out.shape != (po.G, ne) or out.dtype != torch.float64 or out.stride(-1) != 1:
+        raise ValueError("out must be float64 %s with contiguous rows" % ((po.G, ne),))
+    need = int(lib.pb_hrf_normal_eq_w_grouped_work_len(V, po.G, K))
+    if work is None or work.dtype != torch.float64 or work.numel() < need or work.device != dev:
+        work = torch.empty((max(need, 1),), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.pb_hrf_normal_eq_w_grouped(W.data_ptr(), _ld(W) if V else N, Y.data_ptr(), _ld(Y) if V else N, V, N, K, po.G,
+                                            po.host.ctypes.data, po.dev.data_ptr(), work.data_ptr(), work.numel(),
+                                            out.data_ptr(), _ld(out) if po.G else ne, _stream_ptr(dev))
+    _lib.check(rc, "pb_hrf_normal_eq_w_grouped")
+    return out
