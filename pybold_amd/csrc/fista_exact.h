@@ -22,6 +22,7 @@
 #include "../../include/pybold_hip.h"
 #include "common.h"
 #include "fista_fast.h"
+#include <type_traits>
 
 namespace pb {
 
@@ -370,21 +371,27 @@ __global__ __launch_bounds__(256) void fista_exact_kernel(FistaArgs a, TapsD<KT>
   }
 }
 
+// the six compiled variants of a solver (cost trace x stop rule), one switch for every form of the float64 register family:
+// k(with_j, stop, grid, block, stream) launches the variant the two compile-time constants name
+template <class KERNELS>
+int launch_solve_variants(dim3 grid, dim3 block, bool with_j, int stop, hipStream_t st, const KERNELS& k) {
+  const auto with = [&](auto sm) {
+    if (with_j) k(std::true_type{}, sm, grid, block, st);
+    else k(std::false_type{}, sm, grid, block, st);
+  };
+  if (stop == PB_STOP_NONE) with(std::integral_constant<int, 0>{});
+  else if (stop == PB_STOP_LOOPS) with(std::integral_constant<int, 1>{});
+  else with(std::integral_constant<int, 2>{});
+  return 0;
+}
+
 template <int S, int KT>
 int launch_exact(const FistaArgs& a, const double* taps, int K, bool with_j, int stop, hipStream_t st) {
   const auto td = make_taps_d<KT>(taps, K);
   const dim3 grid((unsigned)((launch_count(a) + 3) / 4)), block(256);
-  if (stop == PB_STOP_NONE) {
-    if (with_j) hipLaunchKernelGGL((fista_exact_kernel<S, KT, true, 0>), grid, block, 0, st, a, td);
-    else hipLaunchKernelGGL((fista_exact_kernel<S, KT, false, 0>), grid, block, 0, st, a, td);
-  } else if (stop == PB_STOP_LOOPS) {
-    if (with_j) hipLaunchKernelGGL((fista_exact_kernel<S, KT, true, 1>), grid, block, 0, st, a, td);
-    else hipLaunchKernelGGL((fista_exact_kernel<S, KT, false, 1>), grid, block, 0, st, a, td);
-  } else {
-    if (with_j) hipLaunchKernelGGL((fista_exact_kernel<S, KT, true, 2>), grid, block, 0, st, a, td);
-    else hipLaunchKernelGGL((fista_exact_kernel<S, KT, false, 2>), grid, block, 0, st, a, td);
-  }
-  return 0;
+  return launch_solve_variants(grid, block, with_j, stop, st, [&](auto wj, auto sm, dim3 g, dim3 b, hipStream_t s) {
+    hipLaunchKernelGGL((fista_exact_kernel<S, KT, decltype(wj)::value, decltype(sm)::value>), g, b, 0, s, a, td);
+  });
 }
 
 }  // namespace pb

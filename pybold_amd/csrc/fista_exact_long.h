@@ -16,7 +16,6 @@
 #include "fista_auto.h"
 #include "fista_exact.h"
 #include "fista_exact_pp.h"
-#include <type_traits>
 
 namespace pb {
 
@@ -163,28 +162,12 @@ __global__ __launch_bounds__(256) void fista_exact_long_pp_kernel(FistaArgs a) {
   long_solve_wave<S, KT, WITH_J, STOP>(a, p, live, a.step_vec[p], taps_lane_from_row(a.taps_pp, a.ldt, a.K, p, threadIdx.x & 63));
 }
 
-template <int S, int KT, class KERNELS>
-int launch_long_variants(const dim3 grid, bool with_j, int stop, hipStream_t st, const KERNELS& k) {
-  const dim3 block(256);
-  if (stop == PB_STOP_NONE) {
-    if (with_j) k(std::integral_constant<bool, true>{}, std::integral_constant<int, 0>{}, grid, block, st);
-    else k(std::integral_constant<bool, false>{}, std::integral_constant<int, 0>{}, grid, block, st);
-  } else if (stop == PB_STOP_LOOPS) {
-    if (with_j) k(std::integral_constant<bool, true>{}, std::integral_constant<int, 1>{}, grid, block, st);
-    else k(std::integral_constant<bool, false>{}, std::integral_constant<int, 1>{}, grid, block, st);
-  } else {
-    if (with_j) k(std::integral_constant<bool, true>{}, std::integral_constant<int, 2>{}, grid, block, st);
-    else k(std::integral_constant<bool, false>{}, std::integral_constant<int, 2>{}, grid, block, st);
-  }
-  return 0;
-}
-
 template <int S, int KT>
 int launch_exact_long(const FistaArgs& a, const double* taps, int K, bool with_j, int stop, hipStream_t st) {
   if (!taps || K > KT) return 1;
   const auto td = make_taps_d<KT>(taps, K);
   const dim3 grid((unsigned)((launch_count(a) + 3) / 4));
-  return launch_long_variants<S, KT>(grid, with_j, stop, st, [&](auto wj, auto sm, dim3 g, dim3 b, hipStream_t s) {
+  return launch_solve_variants(grid, dim3(256), with_j, stop, st, [&](auto wj, auto sm, dim3 g, dim3 b, hipStream_t s) {
     hipLaunchKernelGGL((fista_exact_long_kernel<S, KT, decltype(wj)::value, decltype(sm)::value>), g, b, 0, s, a, td);
   });
 }
@@ -193,7 +176,7 @@ template <int S, int KT>
 int launch_exact_long_pp(const FistaArgs& a, bool with_j, int stop, hipStream_t st) {
   if (!a.taps_pp || !a.step_vec || a.K > KT) return 1;
   const dim3 grid((unsigned)((launch_count(a) + 3) / 4));
-  return launch_long_variants<S, KT>(grid, with_j, stop, st, [&](auto wj, auto sm, dim3 g, dim3 b, hipStream_t s) {
+  return launch_solve_variants(grid, dim3(256), with_j, stop, st, [&](auto wj, auto sm, dim3 g, dim3 b, hipStream_t s) {
     hipLaunchKernelGGL((fista_exact_long_pp_kernel<S, KT, decltype(wj)::value, decltype(sm)::value>), g, b, 0, s, a);
   });
 }

@@ -258,17 +258,9 @@ template <int S, int KT>
 int launch_exact_split(const FistaArgs& a, const double* taps, int K, bool with_j, int stop, hipStream_t st) {
   const auto td = make_taps_d<KT>(taps, K);
   const dim3 grid((unsigned)launch_count(a)), block(64 * SPLIT_WAVES);
-  if (stop == PB_STOP_NONE) {
-    if (with_j) hipLaunchKernelGGL((fista_exact_split_kernel<S, KT, true, 0>), grid, block, 0, st, a, td);
-    else hipLaunchKernelGGL((fista_exact_split_kernel<S, KT, false, 0>), grid, block, 0, st, a, td);
-  } else if (stop == PB_STOP_LOOPS) {
-    if (with_j) hipLaunchKernelGGL((fista_exact_split_kernel<S, KT, true, 1>), grid, block, 0, st, a, td);
-    else hipLaunchKernelGGL((fista_exact_split_kernel<S, KT, false, 1>), grid, block, 0, st, a, td);
-  } else {
-    if (with_j) hipLaunchKernelGGL((fista_exact_split_kernel<S, KT, true, 2>), grid, block, 0, st, a, td);
-    else hipLaunchKernelGGL((fista_exact_split_kernel<S, KT, false, 2>), grid, block, 0, st, a, td);
-  }
-  return 0;
+  return launch_solve_variants(grid, block, with_j, stop, st, [&](auto wj, auto sm, dim3 g, dim3 b, hipStream_t s) {
+    hipLaunchKernelGGL((fista_exact_split_kernel<S, KT, decltype(wj)::value, decltype(sm)::value>), g, b, 0, s, a, td);
+  });
 }
 
 }  // namespace pb

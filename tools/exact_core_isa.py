@@ -1,9 +1,12 @@
-"""Instruction-count comparison of fista_exact_kernel (and, where both builds have its listings, auto_lbda_kernel) between two
-builds, from the ISA listings `make build/exact_5_32.s build/exact_10_32.s [build/auto_5_32.s build/auto_10_32.s]` leaves in
-pybold_amd/csrc/build (hipcc for gfx950, no GPU needed):
+"""Instruction-level comparison of the float64 register-resident kernels (pybold_amd/csrc/fista_exact*.h, fista_auto*.h)
+between two builds, from the ISA listings `make build/<name>.s` leaves in pybold_amd/csrc/build
+(hipcc for gfx950, no GPU needed):
 
-    python tools/exact_core_isa.py <dir with the parent's exact_*.s / .res> <dir with this tree's> > profiles/exact_core_isa.txt
+    python tools/exact_core_isa.py <dir with the parent's *.s / *.res> <dir with this tree's> > profiles/<file>.txt
     python tools/exact_core_isa.py <parent's dir> <this tree's dir> exact_5_32 exactpp_10_32 autosplit_5_32 ...   (listings by name)
+
+With no names: every listing of the family -- the sixteen object prefixes on the pairs of their exact*_table.inc, 24 listings
+and 96 kernels (`python tools/exact_core_isa.py --names` prints them).
 
 Per kernel: the resource report, the instruction count, the opcode histogram's differences, and whether the instruction
 text is identical / identical up to register names / identical as a multiset (scheduling order only)."""
@@ -11,6 +14,23 @@ import collections
 import os
 import re
 import sys
+
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pybold_amd", "csrc")
+# table -> (its macro, the object prefixes built on its pairs)
+FAMILY = (("exact_table.inc", "PB_EXACT", ("exact", "auto", "exactpp", "autopp")),
+          ("exact_split_table.inc", "PB_EXACT_SPLIT", ("exactsplit", "autosplit", "exactsplitpp", "autosplitpp")),
+          ("exact_long_table.inc", "PB_EXACT_LONG", ("exactlong", "autolong", "exactlongpp", "autolongpp")),
+          ("exact_split_long_table.inc", "PB_EXACT_SPLIT_LONG",
+           ("exactsplitlong", "autosplitlong", "exactsplitlongpp", "autosplitlongpp")))
+
+
+def family_listings():
+    names = []
+    for table, macro, prefixes in FAMILY:
+        pairs = re.findall(r"^%s\((\d+), *(\d+)\)" % macro, open(os.path.join(CSRC, table)).read(), re.M)
+        names += ["%s_%s_%s" % (p, s, kt) for s, kt in pairs for p in prefixes]
+    return names
 
 
 def kernels(path):
@@ -45,17 +65,21 @@ def anonymise(ins):
 
 
 def main():
+    if sys.argv[1:] == ["--names"]:
+        print(" ".join(family_listings()))
+        return
     old, new = sys.argv[1], sys.argv[2]
     names = sys.argv[3:]
     if names:
         print("tools/exact_core_isa.py: the kernels of %s of this tree against a build of the parent commit." % ", ".join(names))
-        print("hipcc for gfx950, no GPU.\n")
     else:
-        print("tools/exact_core_isa.py: fista_exact_kernel of this tree (pass body in exact_forward / exact_backward, shared with")
-        print("auto_lbda_kernel) against a build of the parent commit.  hipcc for gfx950, no GPU.\n")
-    for name in names or ("exact_5_32", "exact_10_32", "auto_5_32", "auto_10_32"):
-        if name.startswith("auto") and not all(os.path.exists(os.path.join(d, name + ".s")) for d in (old, new)):
-            continue
+        names = family_listings()
+        print("tools/exact_core_isa.py: every kernel of the float64 register-resident family (%d listings) of this tree against a"
+              % len(names))
+        print("build of the parent commit.")
+    print("hipcc for gfx950, no GPU.\n")
+    tally = collections.Counter()
+    for name in names:
         ko, kn = kernels(os.path.join(old, name + ".s")), kernels(os.path.join(new, name + ".s"))
         ro, rn = resources(os.path.join(old, name + ".res")), resources(os.path.join(new, name + ".res"))
         assert sorted(ko) == sorted(kn), "symbols differ"
@@ -73,9 +97,12 @@ def main():
                 verdict = "differs: " + ", ".join("%s %+d" % kv for kv in moved.items())
             res = " ".join("%s %s->%s" % (k, ro[sym].get(k), v) if ro[sym].get(k) != v else "%s %s" % (k, v)
                            for k, v in rn[sym].items() if k in ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]",
-                                                                 "Occupancy [waves/SIMD]"))
+                                                                 "Occupancy [waves/SIMD]", "VGPRs Spill",
+                                                                 "LDS Size [bytes/block]"))
             short = re.sub(r"^_ZN2pb\d+", "", sym).split("EEv")[0]
             print("%s %s: %d -> %d instructions | %s | %s" % (name, short, len(a), len(b), res, verdict))
+            tally[verdict.split(":")[0]] += 1
+    print("\n%d kernels: %s" % (sum(tally.values()), ", ".join("%d %s" % (n, v) for v, n in tally.most_common())))
 
 
 if __name__ == "__main__":
