@@ -44,6 +44,41 @@ _c_i64 = ctypes.c_int64
 _c_dbl = ctypes.c_double
 _ptr = ctypes.c_void_p
 
+# the four argument lists of the float64 register family (csrc/dispatch.h: four forms, each with a solve and a lambda search,
+# the taps on the host or one HRF and one step per problem): twelve entry points share them
+_SOLVE_D = [
+    _ptr, _c_i64, _c_int,            # y_dev (float64), ldy, y_rep
+    _ptr, _c_i64, _c_int, _c_int,    # w_dev, ldw, P, N
+    _ptr, _ptr, _c_int,              # taps_host, taps_dev, K
+    _c_dbl, _c_dbl, _ptr,            # step, lbda, lbda_dev
+    _ptr, _c_int,                    # betas_dev, n_iter
+    _ptr, _c_i64,                    # J_dev (float64), ldj
+    _c_int, _c_dbl, _c_int, _ptr,    # stop_mode, tol, wind, n_done_dev
+    ctypes.c_uint, _ptr]             # flags, stream
+_SOLVE_PP_D = [
+    _ptr, _c_i64, _c_int,            # y_dev (float64), ldy, y_rep
+    _ptr, _c_i64, _c_int, _c_int,    # w_dev, ldw, P, N
+    _ptr, _c_i64, _c_int, _ptr,      # taps_dev, ldt, K, step_dev
+    _c_dbl, _ptr,                    # lbda, lbda_dev
+    _ptr, _c_int,                    # betas_dev, n_iter
+    _ptr, _c_i64,                    # J_dev (float64), ldj
+    _c_int, _c_dbl, _c_int, _ptr,    # stop_mode, tol, wind, n_done_dev
+    ctypes.c_uint, _ptr]             # flags, stream
+_AUTO_LBDA_D = [
+    _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,     # y_dev, ldy, w_dev, ldw, cold, V, N
+    _ptr, _c_int, _c_dbl, _ptr, _ptr,                       # taps_host, K, step, betas_dev, sigma_dev
+    _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,         # early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk
+    _ptr, _ptr, _ptr, _c_i64,                               # R_dev, G_dev, J_dev, ldt
+    _ptr, _ptr, _ptr, _ptr,                                 # alpha_dev, lbda_dev, n_outer_dev, n_inner_dev
+    _ptr, _c_i64, _ptr]                                     # work_dev, work_len, stream
+_AUTO_LBDA_PP_D = [
+    _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,     # y_dev, ldy, w_dev, ldw, cold, V, N
+    _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr,                 # taps_dev, ldt, K, step_dev, betas_dev, sigma_dev
+    _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,         # early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk
+    _ptr, _ptr, _ptr, _c_i64,                               # R_dev, G_dev, J_dev, ldtr
+    _ptr, _ptr, _ptr, _ptr,                                 # alpha_dev, lbda_dev, n_outer_dev, n_inner_dev
+    _ptr, _c_i64, _ptr]                                     # work_dev, work_len, stream
+
 # name -> (restype, argtypes); mirrors include/pybold_hip.h one to one
 SIGNATURES = {
     "pb_version": (_c_int, []),
@@ -123,37 +158,15 @@ SIGNATURES = {
     "pb_spm_hrf": (_c_int, [_ptr, _c_int, _ptr, _c_int, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_dbl,
                             _ptr, _ptr]),
     # float64-y forms
-    "pb_fista_solve_d": (_c_int, [
-        _ptr, _c_i64, _c_int,            # y_dev (float64), ldy, y_rep
-        _ptr, _c_i64, _c_int, _c_int,    # w_dev, ldw, P, N
-        _ptr, _ptr, _c_int,              # taps_host, taps_dev, K
-        _c_dbl, _c_dbl, _ptr,            # step, lbda, lbda_dev
-        _ptr, _c_int,                    # betas_dev, n_iter
-        _ptr, _c_i64,                    # J_dev (float64), ldj
-        _c_int, _c_dbl, _c_int, _ptr,    # stop_mode, tol, wind, n_done_dev
-        ctypes.c_uint, _ptr]),           # flags, stream
+    "pb_fista_solve_d": (_c_int, _SOLVE_D),
     "pb_fista_which_kernel_d": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     # one HRF and one step per problem, float64 end to end
     "pb_spectral_radius_pp": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_i64, _c_int,      # x0, ldx, V, N, taps_dev, ldt, K
                                        _c_int, _c_dbl, _ptr, _ptr]),                            # nb_iter, tol, out [V][2], stream
-    "pb_fista_solve_pp_d": (_c_int, [
-        _ptr, _c_i64, _c_int,            # y_dev (float64), ldy, y_rep
-        _ptr, _c_i64, _c_int, _c_int,    # w_dev, ldw, P, N
-        _ptr, _c_i64, _c_int, _ptr,      # taps_dev, ldt, K, step_dev
-        _c_dbl, _ptr,                    # lbda, lbda_dev
-        _ptr, _c_int,                    # betas_dev, n_iter
-        _ptr, _c_i64,                    # J_dev (float64), ldj
-        _c_int, _c_dbl, _c_int, _ptr,    # stop_mode, tol, wind, n_done_dev
-        ctypes.c_uint, _ptr]),           # flags, stream
+    "pb_fista_solve_pp_d": (_c_int, _SOLVE_PP_D),
     "pb_fista_which_kernel_pp_d": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "pb_fista_pp_split_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int]),
-    "pb_auto_lbda_pp_d": (_c_int, [
-        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,     # y_dev, ldy, w_dev, ldw, cold, V, N
-        _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr,                 # taps_dev, ldt, K, step_dev, betas_dev, sigma_dev
-        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,         # early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk
-        _ptr, _ptr, _ptr, _c_i64,                               # R_dev, G_dev, J_dev, ldtr
-        _ptr, _ptr, _ptr, _ptr,                                 # alpha_dev, lbda_dev, n_outer_dev, n_inner_dev
-        _ptr, _c_i64, _ptr]),                                   # work_dev, work_len, stream
+    "pb_auto_lbda_pp_d": (_c_int, _AUTO_LBDA_PP_D),
     "pb_fista_stats_d": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int, _ptr,
                                   _c_int, _ptr, _ptr, _ptr]),
     "pb_hrf_cost_d": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _ptr,
@@ -164,80 +177,22 @@ SIGNATURES = {
     "pb_lambda_max_d": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr]),
     "pb_auto_lbda_supported": (_c_int, [_c_int, _c_int, _c_int]),
     "pb_auto_lbda_work_len": (_c_i64, [_c_int]),
-    "pb_auto_lbda_d": (_c_int, [
-        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,     # y_dev, ldy, w_dev, ldw, cold, V, N
-        _ptr, _c_int, _c_dbl, _ptr, _ptr,                       # taps_host, K, step, betas_dev, sigma_dev
-        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,         # early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk
-        _ptr, _ptr, _ptr, _c_i64,                               # R_dev, G_dev, J_dev, ldt
-        _ptr, _ptr, _ptr, _ptr,                                 # alpha_dev, lbda_dev, n_outer_dev, n_inner_dev
-        _ptr, _c_i64, _ptr]),                                   # work_dev, work_len, stream
-    "pb_auto_lbda_split_pp_d": (_c_int, [                       # (the argument list of pb_auto_lbda_pp_d)
-        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
-        _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr,
-        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,
-        _ptr, _ptr, _ptr, _c_i64,
-        _ptr, _ptr, _ptr, _ptr,
-        _ptr, _c_i64, _ptr]),
+    "pb_auto_lbda_d": (_c_int, _AUTO_LBDA_D),
+    "pb_auto_lbda_split_pp_d": (_c_int, _AUTO_LBDA_PP_D),
     "pb_auto_lbda_split_supported": (_c_int, [_c_int, _c_int, _c_int]),
-    "pb_auto_lbda_split_d": (_c_int, [                          # (the argument list of pb_auto_lbda_d)
-        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
-        _ptr, _c_int, _c_dbl, _ptr, _ptr,
-        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,
-        _ptr, _ptr, _ptr, _c_i64,
-        _ptr, _ptr, _ptr, _ptr,
-        _ptr, _c_i64, _ptr]),
+    "pb_auto_lbda_split_d": (_c_int, _AUTO_LBDA_D),
     # opt-in: HRFs of up to 48 taps on the one-wave float64 register form (csrc/fista_exact_long.h)
     "pb_fista_long_hrf_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int]),
     "pb_auto_lbda_long_supported": (_c_int, [_c_int, _c_int, _c_int]),
-    "pb_auto_lbda_long_d": (_c_int, [                           # (the argument list of pb_auto_lbda_d)
-        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
-        _ptr, _c_int, _c_dbl, _ptr, _ptr,
-        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,
-        _ptr, _ptr, _ptr, _c_i64,
-        _ptr, _ptr, _ptr, _ptr,
-        _ptr, _c_i64, _ptr]),
-    "pb_auto_lbda_long_pp_d": (_c_int, [                        # (the argument list of pb_auto_lbda_pp_d)
-        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
-        _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr,
-        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,
-        _ptr, _ptr, _ptr, _c_i64,
-        _ptr, _ptr, _ptr, _ptr,
-        _ptr, _c_i64, _ptr]),
+    "pb_auto_lbda_long_d": (_c_int, _AUTO_LBDA_D),
+    "pb_auto_lbda_long_pp_d": (_c_int, _AUTO_LBDA_PP_D),
     # opt-in: the same holder over four waves, 641 .. 1 280 scans (csrc/fista_exact_split_long.h)
     "pb_fista_split_long_hrf_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int]),
-    "pb_fista_solve_split_long_d": (_c_int, [                   # (the argument list of pb_fista_solve_d)
-        _ptr, _c_i64, _c_int,
-        _ptr, _c_i64, _c_int, _c_int,
-        _ptr, _ptr, _c_int,
-        _c_dbl, _c_dbl, _ptr,
-        _ptr, _c_int,
-        _ptr, _c_i64,
-        _c_int, _c_dbl, _c_int, _ptr,
-        ctypes.c_uint, _ptr]),
-    "pb_fista_solve_split_long_pp_d": (_c_int, [                # (the argument list of pb_fista_solve_pp_d)
-        _ptr, _c_i64, _c_int,
-        _ptr, _c_i64, _c_int, _c_int,
-        _ptr, _c_i64, _c_int, _ptr,
-        _c_dbl, _ptr,
-        _ptr, _c_int,
-        _ptr, _c_i64,
-        _c_int, _c_dbl, _c_int, _ptr,
-        ctypes.c_uint, _ptr]),
+    "pb_fista_solve_split_long_d": (_c_int, _SOLVE_D),
+    "pb_fista_solve_split_long_pp_d": (_c_int, _SOLVE_PP_D),
     "pb_auto_lbda_split_long_supported": (_c_int, [_c_int, _c_int, _c_int]),
-    "pb_auto_lbda_split_long_d": (_c_int, [                     # (the argument list of pb_auto_lbda_split_d)
-        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
-        _ptr, _c_int, _c_dbl, _ptr, _ptr,
-        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,
-        _ptr, _ptr, _ptr, _c_i64,
-        _ptr, _ptr, _ptr, _ptr,
-        _ptr, _c_i64, _ptr]),
-    "pb_auto_lbda_split_long_pp_d": (_c_int, [                  # (the argument list of pb_auto_lbda_split_pp_d)
-        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int,
-        _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr,
-        _c_int, _c_dbl, _c_int, _c_int, _c_int, _c_int,
-        _ptr, _ptr, _ptr, _c_i64,
-        _ptr, _ptr, _ptr, _ptr,
-        _ptr, _c_i64, _ptr]),
+    "pb_auto_lbda_split_long_d": (_c_int, _AUTO_LBDA_D),
+    "pb_auto_lbda_split_long_pp_d": (_c_int, _AUTO_LBDA_PP_D),
     "pb_mad_daub_noise_est": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_dbl, _ptr, _ptr]),
     "pb_mad_daub_noise_est_d": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_dbl, _ptr, _ptr]),
     "pb_inf_norm": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_i64, _ptr]),

@@ -55,50 +55,14 @@ inline int64_t gen_lds_doubles(int N, int K, int stop_mode, int wind) {
   return 3 * (int64_t)N + K + 2 * pb::GEN_WAVES + (stop_mode == PB_STOP_WINDOW ? (int64_t)wind * N : 0);
 }
 
-// outer iterations per launch when the caller leaves the choice to the library: about 65536 inner iterations per wave
-// slot and launch -- 65536 / nb_sub_iter for a batch the machine holds at once (2048 waves: 256 compute units, four
-// SIMDs, two waves of this kernel each), fewer in proportion for a larger one, whose launch runs its waves in rounds
-constexpr int AUTO_LAUNCH_ITERS = 65536, AUTO_RESIDENT_WAVES = 2048;
-inline int auto_outer_chunk(int V, int nb_sub_iter) {
-  const int64_t rounds = ((int64_t)V + AUTO_RESIDENT_WAVES - 1) / AUTO_RESIDENT_WAVES;
+// outer iterations per launch of a lambda search when the caller leaves the choice to the library: the form's budget of inner
+// iterations per resident unit and launch over nb_sub_iter, fewer in proportion for a batch the machine does not hold at
+// once, whose launch runs its units in rounds (the budgets and what they rest on: dispatch.h, kF64)
+inline int auto_outer_chunk(int form, int V, int nb_sub_iter) {
+  const F64FormDesc& d = kF64[form];
+  const int64_t rounds = ((int64_t)V + d.auto_resident - 1) / d.auto_resident;
   const int64_t per = (int64_t)(nb_sub_iter > 0 ? nb_sub_iter : 1) * (rounds > 0 ? rounds : 1);
-  const int64_t c = AUTO_LAUNCH_ITERS / per;
-  return (int)(c < 1 ? 1 : c);
-}
-
-// the same for the search with one voxel per WORKGROUP of four waves (fista_auto_split.h): its register report allows two
-// waves per SIMD, i.e. two workgroups per compute unit, 512 resident at once on 256 compute units; an inner iteration of a
-// workgroup takes about twice that of a wave of the one-wave kernel (3.4 us against 1.5 us alone), so half the budget per
-// slot and launch keeps the longest dispatch under 0.25 s (measured 0.14 s at most: profiles/auto_lbda_split.txt)
-constexpr int AUTO_SPLIT_LAUNCH_ITERS = 32768, AUTO_SPLIT_WGS_PER_CU = 2, AUTO_SPLIT_RESIDENT_WGS = 256 * AUTO_SPLIT_WGS_PER_CU;
-inline int auto_split_outer_chunk(int V, int nb_sub_iter) {
-  const int64_t rounds = ((int64_t)V + AUTO_SPLIT_RESIDENT_WGS - 1) / AUTO_SPLIT_RESIDENT_WGS;
-  const int64_t per = (int64_t)(nb_sub_iter > 0 ? nb_sub_iter : 1) * (rounds > 0 ? rounds : 1);
-  const int64_t c = AUTO_SPLIT_LAUNCH_ITERS / per;
-  return (int)(c < 1 ? 1 : c);
-}
-
-// the same for the one-wave search with up to 48 taps (fista_exact_long.h): its register reports allow the residency of
-// auto_lbda_kernel, but a pass carries 48 taps for 32 (1.5x the multiply-adds, and two lane reads per tap and half): at that
-// kernel's budget its longest dispatch (0.16 s, profiles/auto_lbda_device.txt) would pass 0.25 s -- half the budget here
-// (measured: profiles/long_hrf.txt)
-constexpr int AUTO_LONG_LAUNCH_ITERS = 32768;
-inline int auto_long_outer_chunk(int V, int nb_sub_iter) {
-  const int64_t rounds = ((int64_t)V + AUTO_RESIDENT_WAVES - 1) / AUTO_RESIDENT_WAVES;
-  const int64_t per = (int64_t)(nb_sub_iter > 0 ? nb_sub_iter : 1) * (rounds > 0 ? rounds : 1);
-  const int64_t c = AUTO_LONG_LAUNCH_ITERS / per;
-  return (int)(c < 1 ? 1 : c);
-}
-
-// the same for the four-wave search with up to 48 taps (fista_exact_split_long.h): the residency of the four-wave search (two
-// workgroups per compute unit by its register reports), and a pass that carries 48 taps for 32: 1.5x the multiply-adds, the
-// reasoning of AUTO_LONG_LAUNCH_ITERS -- that search's budget divided by 1.5, rounded down to a multiple of 1 024
-// (32768 / 1.5 = 21845 -> 21504)
-constexpr int AUTO_SPLIT_LONG_LAUNCH_ITERS = 21504;
-inline int auto_split_long_outer_chunk(int V, int nb_sub_iter) {
-  const int64_t rounds = ((int64_t)V + AUTO_SPLIT_RESIDENT_WGS - 1) / AUTO_SPLIT_RESIDENT_WGS;
-  const int64_t per = (int64_t)(nb_sub_iter > 0 ? nb_sub_iter : 1) * (rounds > 0 ? rounds : 1);
-  const int64_t c = AUTO_SPLIT_LONG_LAUNCH_ITERS / per;
+  const int64_t c = d.auto_launch_iters / per;
   return (int)(c < 1 ? 1 : c);
 }
 
@@ -617,7 +581,7 @@ int run_partition(const Route& r, const pb::FistaArgs& a, const LF& lf, hipStrea
   // rule: the register-resident one, one or four waves per series, where the shape has an entry (its window rule is
   // wind = 6; 1.0e9 voxel-iterations/s against 0.17e9), else the LDS one, which needs the taps in device memory and the row
   // in LDS; with neither, or without the guard, no series is marked
-  const ExactEntry* ill_exact = pick_exact_any(N, K, a.stop_mode, a.wind, nullptr);
+  const ExactEntry* ill_exact = pick_f64_default(N, K, a.stop_mode, a.wind, true);
   const bool ill_generic = !ill_exact && taps_dev && gen_lds_doubles(N, K, a.stop_mode, a.wind) <= LDS_DOUBLES_MAX;
   const bool guard = !(flags & PB_FLAG_NO_ILL_GUARD);
   // (the caller's lmax_dev is not needed: the pass also sees max|y| and marks the ill-conditioned series, which the caller's
@@ -876,476 +840,274 @@ int pb_fista_solve(const float* y_dev, int64_t ldy, int y_rep, double* w_dev, in
                     J_dev, ldj, stop_mode, tol, wind, n_done_dev, flags, stream, nullptr, 0.0, work, len);
 }
 
+// ---- the float64 register family (dispatch.h: kF64, pick_f64): four solve and eight search entry points over one
+// validation-and-launch function each ----------------------------------------------------------------------------------------
 namespace {
-// PB_FLAG_LONG_HRF on pb_fista_solve_d / pb_fista_solve_pp_d: the entry of the 48-tap register form, or the error of a call
-// it does not carry (nothing is launched)
-int long_hrf_entry(const char* name, int N, int K, int stop_mode, int wind, unsigned flags, const ExactLongEntry** le) {
-  if (flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_FAST | PB_FLAG_PP_SPLIT))
-    return fail(PB_ERR_INVALID, "%s: PB_FLAG_LONG_HRF names the 48-tap register form; it excludes PB_FLAG_FORCE_GENERIC, PB_FLAG_FORCE_FAST and PB_FLAG_PP_SPLIT", name);
-  if (N > LONG_HRF_NMAX) return fail(PB_ERR_INVALID, "%s: PB_FLAG_LONG_HRF with N=%d outside 1..640 scans", name, N);
-  if (K > LONG_HRF_KMAX) return fail(PB_ERR_INVALID, "%s: PB_FLAG_LONG_HRF with K=%d outside 1..48 taps", name, K);
-  if (stop_mode == PB_STOP_WINDOW && wind != 6)
-    return fail(PB_ERR_INVALID, "%s: PB_FLAG_LONG_HRF with wind=%d (the 48-tap register form carries wind = 6)", name, wind);
-  *le = pick_exact_long(N, K, stop_mode, wind);
-  if (!*le) return fail(PB_ERR_INVALID, "%s: no 48-tap specialisation for N=%d K=%d", name, N, K);
+// How a solve names a form that the default dispatch does not choose: by a flag, or by its entry point
+struct F64Named {
+  int form;
+  const char* who;               // what names the form ...
+  const char* with;              // ... and how the messages of the form's own checks begin
+  unsigned excluded;             // the flags that name another form
+  const char* excluded_names;
+  const char* taps_host_note;    // beside "NULL pointer" of a call with the taps on the host
+};
+const F64Named kByLongHrfFlag = {F64_LONG_HRF, "PB_FLAG_LONG_HRF", "PB_FLAG_LONG_HRF with ",
+                                 PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_FAST | PB_FLAG_PP_SPLIT,
+                                 "PB_FLAG_FORCE_GENERIC, PB_FLAG_FORCE_FAST and PB_FLAG_PP_SPLIT", " (PB_FLAG_LONG_HRF reads taps_host)"};
+const F64Named kByPPSplitFlag = {F64_FOUR_WAVES, "PB_FLAG_PP_SPLIT", "PB_FLAG_PP_SPLIT with ", PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_FAST,
+                                 "PB_FLAG_FORCE_GENERIC and PB_FLAG_FORCE_FAST", ""};
+const F64Named kBySplitLongEntry = {F64_FOUR_WAVES_LONG_HRF, "the entry point", "",
+                                    PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_FAST | PB_FLAG_PP_SPLIT | PB_FLAG_LONG_HRF,
+                                    "PB_FLAG_FORCE_GENERIC, PB_FLAG_FORCE_FAST, PB_FLAG_PP_SPLIT and PB_FLAG_LONG_HRF", ""};
+
+// the words of a form's messages, with its tap limit in them (built where a message needs them only)
+struct F64Words { char label[32], form[64], taps_over[32]; };
+F64Words f64_words(const F64FormDesc& d) {
+  F64Words w;
+  snprintf(w.label, sizeof(w.label), d.label, d.k_max);
+  snprintf(w.form, sizeof(w.form), "%s %s", w.label, d.noun);
+  snprintf(w.taps_over, sizeof(w.taps_over), d.taps_over, d.k_max);
+  return w;
+}
+// check_launch under the kernel's name: <stem><form>[_pp]_kernel[(final solve)]
+int check_f64_launch(const char* stem, int form, bool pp, bool final_solve = false) {
+  char what[64];
+  snprintf(what, sizeof(what), "%s%s%s_kernel%s", stem, kF64[form].kernels, pp ? "_pp" : "", final_solve ? "(final solve)" : "");
+  return check_launch(what);
+}
+
+// the entry of the form a solve names, or the error of a call that form does not carry (nothing is launched)
+int named_f64_entry(const char* name, const F64Named& by, int N, int K, int stop_mode, int wind, unsigned flags, const ExactEntry** e) {
+  const F64FormDesc& d = kF64[by.form];
+  if (flags & by.excluded)
+    return fail(PB_ERR_INVALID, "%s: %s names the %s; it excludes %s", name, by.who, f64_words(d).form, by.excluded_names);
+  if (N < d.n_min || N > d.n_max) return fail(PB_ERR_INVALID, "%s: %sN=%d outside %d..%d scans", name, by.with, N, d.n_min, d.n_max);
+  if (K > d.k_max) return fail(PB_ERR_INVALID, "%s: %sK=%d %s", name, by.with, K, f64_words(d).taps_over);
+  if (stop_mode == PB_STOP_WINDOW && wind != F64_WIND)
+    return fail(PB_ERR_INVALID, "%s: %swind=%d (the %s carries wind = %d)", name, by.with, wind, f64_words(d).form, F64_WIND);
+  *e = pick_f64(by.form, N, K, stop_mode, wind);
+  if (!*e) return fail(PB_ERR_INVALID, "%s: no %s specialisation for N=%d K=%d", name, f64_words(d).label, N, K);
   return PB_OK;
 }
-// pb_fista_solve_split_long_d / pb_fista_solve_split_long_pp_d: the entry of the four-wave 48-tap form (641 .. 1 280 scans), or
-// the error of a call it does not carry (nothing is launched).  The form is named by the entry point, so the flags that name
-// another form are refused
-int split_long_hrf_entry(const char* name, int N, int K, int stop_mode, int wind, unsigned flags, const ExactLongEntry** le) {
-  if (flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_FAST | PB_FLAG_PP_SPLIT | PB_FLAG_LONG_HRF))
-    return fail(PB_ERR_INVALID, "%s: the entry point names the four-wave 48-tap register form; it excludes PB_FLAG_FORCE_GENERIC, PB_FLAG_FORCE_FAST, PB_FLAG_PP_SPLIT and PB_FLAG_LONG_HRF", name);
-  if (N < SPLIT_LONG_NMIN || N > SPLIT_LONG_NMAX) return fail(PB_ERR_INVALID, "%s: N=%d outside 641..1280 scans", name, N);
-  if (K > LONG_HRF_KMAX) return fail(PB_ERR_INVALID, "%s: K=%d outside 1..48 taps", name, K);
-  if (stop_mode == PB_STOP_WINDOW && wind != 6)
-    return fail(PB_ERR_INVALID, "%s: wind=%d (the four-wave 48-tap register form carries wind = 6)", name, wind);
-  *le = pick_exact_split_long(N, K, stop_mode, wind);
-  if (!*le) return fail(PB_ERR_INVALID, "%s: no four-wave 48-tap specialisation for N=%d K=%d", name, N, K);
-  return PB_OK;
+
+// The four float64 solves: `pp` -- one HRF (taps_dev [P][ldt]) and one step (step_dev [P]) per problem instead of taps_host /
+// taps_dev and step; `entry_names` -- the form the entry point names, else the flags name one (PB_FLAG_LONG_HRF; with `pp`,
+// PB_FLAG_PP_SPLIT), else the default dispatch chooses, with the any-size LDS kernel behind it.  One validation in one order;
+// the two argument lists word three checks differently (the leading dimensions, and the step that only one of them has).
+int solve_d(const char* name, bool pp, const F64Named* entry_names, const double* y_dev, int64_t ldy, int y_rep, double* w_dev,
+            int64_t ldw, int P, int N, const double* taps_host, const double* taps_dev, int64_t ldt, int K, double step,
+            const double* step_dev, double lbda, const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev,
+            int64_t ldj, int stop_mode, double tol, int wind, int32_t* n_done_dev, unsigned flags, void* stream) {
+  if (P < 0 || N < 1 || K < 1 || n_iter < 0 || y_rep < 1)
+    return fail(PB_ERR_INVALID, "%s: bad size (P=%d N=%d K=%d n_iter=%d y_rep=%d)", name, P, N, K, n_iter, y_rep);
+  if (pp && ldt < K) return fail(PB_ERR_INVALID, "%s: ldt < K", name);
+  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, pp ? "%s: leading dimension too small (< N)" : "%s: leading dimension < N", name);
+  if (J_dev && ldj < n_iter) return fail(PB_ERR_INVALID, pp ? "%s: leading dimension too small (ldj < n_iter)" : "%s: ldj < n_iter", name);
+  if (!pp && !(step > 0.0)) return fail(PB_ERR_INVALID, "%s: step must be positive", name);
+  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return fail(PB_ERR_INVALID, "%s: unknown stop_mode %d", name, stop_mode);
+  if (stop_mode == PB_STOP_WINDOW && wind < 2) return fail(PB_ERR_INVALID, "%s: wind must be >= 2", name);
+  const F64Named* by = entry_names                          ? entry_names
+                       : (flags & PB_FLAG_LONG_HRF)         ? &kByLongHrfFlag
+                       : (pp && (flags & PB_FLAG_PP_SPLIT)) ? &kByPPSplitFlag
+                                                            : nullptr;
+  const ExactEntry* e = nullptr;
+  int form = F64_ONE_WAVE;
+  if (by) {                                                 // opt-in: that form, or an error
+    form = by->form;
+    const int rc = named_f64_entry(name, *by, N, K, stop_mode, wind, flags, &e);
+    if (rc != PB_OK) return rc;
+  } else {
+    // the register form where the shape has an entry and (taps on the host) the host copy of the taps is given
+    if ((pp || taps_host) && !(flags & PB_FLAG_FORCE_GENERIC)) e = pick_f64_default(N, K, stop_mode, wind, !pp, &form);
+    // PB_FLAG_FORCE_FAST keeps the meaning it had before the four-wave form existed: the one-problem-per-wave form or an
+    // error (callers and tests pin that it fails beyond 640 scans); the four-wave form is reached by the dispatch only
+    if ((!e || form != F64_ONE_WAVE) && (flags & PB_FLAG_FORCE_FAST))
+      return fail(PB_ERR_INVALID, "%s: no register-resident float64 kernel with one problem per wave for N=%d K=%d", name, N, K);
+    if (!e && gen_lds_doubles(N, K, stop_mode, wind) > LDS_DOUBLES_MAX)
+      return fail(PB_ERR_INVALID, "%s: N=%d K=%d wind=%d exceeds LDS", name, N, K, wind);
+  }
+  if (P == 0) return PB_OK;
+  // (taps on the host: a register form reads taps_host, the LDS kernel taps_dev)
+  if (!y_dev || !w_dev || (pp ? !taps_dev || !step_dev : e ? !taps_host : !taps_dev) || (n_iter > 0 && !betas_dev))
+    return fail(PB_ERR_INVALID, "%s: NULL pointer%s", name, (by && !pp) ? by->taps_host_note : "");
+  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 problems per launch", name);
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, pp ? 0.0 : step, lbda, lbda_dev, betas_dev, stop_mode, tol,
+                               n_done_dev, flags);
+  a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj;
+  if (pp) { a.wind = wind; a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = 0; }
+  if (!e) {
+    launch_generic(a, taps_dev, K, wind, J_dev != nullptr, true, P, (hipStream_t)stream);
+    return check_launch(pp ? "fista_generic_kernel(f64, pp)" : "fista_generic_kernel(f64)");
+  }
+  if ((pp ? e->fn_pp(a, J_dev != nullptr, stop_mode, (hipStream_t)stream)
+          : e->fn(a, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream)) != 0)
+    return fail(PB_ERR_INVALID, "%s: launch rejected", name);
+  return check_f64_launch("fista_exact", form, pp);
 }
 }  // namespace
 
-int pb_fista_long_hrf_supported(int N, int K, int stop_mode, int wind) { return pick_exact_long(N, K, stop_mode, wind) ? 1 : 0; }
+int pb_fista_long_hrf_supported(int N, int K, int stop_mode, int wind) { return pick_f64(F64_LONG_HRF, N, K, stop_mode, wind) ? 1 : 0; }
 
 int pb_fista_split_long_hrf_supported(int N, int K, int stop_mode, int wind) {
-  return pick_exact_split_long(N, K, stop_mode, wind) ? 1 : 0;
+  return pick_f64(F64_FOUR_WAVES_LONG_HRF, N, K, stop_mode, wind) ? 1 : 0;
 }
 
-// pb_fista_solve_d on the four-wave form for HRFs of up to 48 taps (fista_exact_split_long.h), or an error: opt-in by name --
-// pb_fista_solve_d itself is what it was.  The validation is that function's, in its order
-int pb_fista_solve_split_long_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
-                                const double* taps_host, const double* taps_dev, int K, double step, double lbda,
-                                const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj, int stop_mode, double tol,
-                                int wind, int32_t* n_done_dev, unsigned flags, void* stream) {
-  const char* name = "pb_fista_solve_split_long_d";
-  (void)taps_dev;                                       // (the parameter list of pb_fista_solve_d: only the LDS kernel reads it)
-  if (P < 0 || N < 1 || K < 1 || n_iter < 0 || y_rep < 1)
-    return fail(PB_ERR_INVALID, "%s: bad size (P=%d N=%d K=%d n_iter=%d y_rep=%d)", name, P, N, K, n_iter, y_rep);
-  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "%s: leading dimension < N", name);
-  if (J_dev && ldj < n_iter) return fail(PB_ERR_INVALID, "%s: ldj < n_iter", name);
-  if (!(step > 0.0)) return fail(PB_ERR_INVALID, "%s: step must be positive", name);
-  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return fail(PB_ERR_INVALID, "%s: unknown stop_mode %d", name, stop_mode);
-  if (stop_mode == PB_STOP_WINDOW && wind < 2) return fail(PB_ERR_INVALID, "%s: wind must be >= 2", name);
-  const ExactLongEntry* le = nullptr;
-  const int rc = split_long_hrf_entry(name, N, K, stop_mode, wind, flags, &le);
-  if (rc != PB_OK) return rc;
-  if (P == 0) return PB_OK;
-  if (!y_dev || !w_dev || !taps_host || (n_iter > 0 && !betas_dev)) return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
-  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 problems per launch", name);
-  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, step, lbda, lbda_dev, betas_dev, stop_mode, tol,
-                               n_done_dev, flags);
-  a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj;
-  if (le->fn(a, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-    return fail(PB_ERR_INVALID, "%s: launch rejected", name);
-  return check_launch("fista_exact_split_long_kernel");
-}
-
-// ... and pb_fista_solve_pp_d on it: one HRF and one step per problem, both in device memory
-int pb_fista_solve_split_long_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
-                                   const double* taps_dev, int64_t ldt, int K, const double* step_dev, double lbda,
-                                   const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj,
-                                   int stop_mode, double tol, int wind, int32_t* n_done_dev, unsigned flags, void* stream) {
-  const char* name = "pb_fista_solve_split_long_pp_d";
-  if (P < 0 || N < 1 || K < 1 || n_iter < 0 || y_rep < 1)
-    return fail(PB_ERR_INVALID, "%s: bad size (P=%d N=%d K=%d n_iter=%d y_rep=%d)", name, P, N, K, n_iter, y_rep);
-  if (ldt < K) return fail(PB_ERR_INVALID, "%s: ldt < K", name);
-  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "%s: leading dimension too small (< N)", name);
-  if (J_dev && ldj < n_iter) return fail(PB_ERR_INVALID, "%s: leading dimension too small (ldj < n_iter)", name);
-  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return fail(PB_ERR_INVALID, "%s: unknown stop_mode %d", name, stop_mode);
-  if (stop_mode == PB_STOP_WINDOW && wind < 2) return fail(PB_ERR_INVALID, "%s: wind must be >= 2", name);
-  const ExactLongEntry* le = nullptr;
-  const int rc = split_long_hrf_entry(name, N, K, stop_mode, wind, flags, &le);
-  if (rc != PB_OK) return rc;
-  if (P == 0) return PB_OK;
-  if (!y_dev || !w_dev || !taps_dev || !step_dev || (n_iter > 0 && !betas_dev)) return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
-  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 problems per launch", name);
-  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, stop_mode, tol,
-                               n_done_dev, flags);
-  a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj; a.wind = wind;
-  a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = 0;
-  if (le->fn_pp(a, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-    return fail(PB_ERR_INVALID, "%s: launch rejected", name);
-  return check_launch("fista_exact_split_long_pp_kernel");
-}
+int pb_fista_pp_split_supported(int N, int K, int stop_mode, int wind) { return pick_f64(F64_FOUR_WAVES, N, K, stop_mode, wind) ? 1 : 0; }
 
 int pb_fista_solve_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw,
                      int P, int N, const double* taps_host, const double* taps_dev, int K,
                      double step, double lbda, const double* lbda_dev, const double* betas_dev,
                      int n_iter, double* J_dev, int64_t ldj, int stop_mode, double tol, int wind,
                      int32_t* n_done_dev, unsigned flags, void* stream) {
-  if (P < 0 || N < 1 || K < 1 || n_iter < 0 || y_rep < 1)
-    return fail(PB_ERR_INVALID, "pb_fista_solve_d: bad size (P=%d N=%d K=%d n_iter=%d y_rep=%d)", P,
-                N, K, n_iter, y_rep);
-  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "pb_fista_solve_d: leading dimension < N");
-  if (J_dev && ldj < n_iter) return fail(PB_ERR_INVALID, "pb_fista_solve_d: ldj < n_iter");
-  if (!(step > 0.0)) return fail(PB_ERR_INVALID, "pb_fista_solve_d: step must be positive");
-  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW)
-    return fail(PB_ERR_INVALID, "pb_fista_solve_d: unknown stop_mode %d", stop_mode);
-  if (stop_mode == PB_STOP_WINDOW && wind < 2)
-    return fail(PB_ERR_INVALID, "pb_fista_solve_d: wind must be >= 2");
-  if (flags & PB_FLAG_LONG_HRF) {               // opt-in: HRFs of up to 48 taps on the one-wave register form, or an error
-    const ExactLongEntry* le = nullptr;
-    const int rc = long_hrf_entry("pb_fista_solve_d", N, K, stop_mode, wind, flags, &le);
-    if (rc != PB_OK) return rc;
-    if (P == 0) return PB_OK;
-    if (!y_dev || !w_dev || !taps_host || (n_iter > 0 && !betas_dev))
-      return fail(PB_ERR_INVALID, "pb_fista_solve_d: NULL pointer (PB_FLAG_LONG_HRF reads taps_host)");
-    if (P > (1 << 25)) return fail(PB_ERR_INVALID, "pb_fista_solve_d: more than 2^25 problems per launch");
-    pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, step, lbda, lbda_dev, betas_dev, stop_mode, tol,
-                                 n_done_dev, flags);
-    a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj;
-    if (le->fn(a, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-      return fail(PB_ERR_INVALID, "pb_fista_solve_d: launch rejected");
-    return check_launch("fista_exact_long_kernel");
-  }
-  // register-resident float64 form (one problem per wave) when the shape has an entry and
-  // the host copy of the taps is given; the window rule there is the reference default wind = 6
-  // (one problem per wave up to 640 scans, one per workgroup of four waves up to 1 280: fista_exact_split.h)
-  bool split = false;
-  const ExactEntry* ee = (taps_host && !(flags & PB_FLAG_FORCE_GENERIC)) ? pick_exact_any(N, K, stop_mode, wind, &split) : nullptr;
-  // PB_FLAG_FORCE_FAST keeps the meaning it had before the four-wave form existed: the one-problem-per-wave form or an
-  // error (callers and tests pin that it fails beyond 640 scans); the four-wave form is reached by the dispatch only
-  if ((!ee || split) && (flags & PB_FLAG_FORCE_FAST))
-    return fail(PB_ERR_INVALID, "pb_fista_solve_d: no register-resident float64 kernel with one problem per wave for N=%d K=%d", N, K);
-  const int64_t nd = gen_lds_doubles(N, K, stop_mode, wind);
-  if (!ee && nd > LDS_DOUBLES_MAX)
-    return fail(PB_ERR_INVALID, "pb_fista_solve_d: N=%d K=%d wind=%d exceeds LDS", N, K, wind);
-  if (P == 0) return PB_OK;
-  if (!y_dev || !w_dev || (!ee && !taps_dev) || (n_iter > 0 && !betas_dev))
-    return fail(PB_ERR_INVALID, "pb_fista_solve_d: NULL pointer");
-  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "pb_fista_solve_d: more than 2^25 problems per launch");
-  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, step, lbda, lbda_dev, betas_dev, stop_mode, tol,
-                               n_done_dev, flags);
-  a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj;
-  if (ee) {
-    if (ee->fn(a, taps_host, K, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-      return fail(PB_ERR_INVALID, "pb_fista_solve_d: launch rejected");
-    return check_launch(split ? "fista_exact_split_kernel" : "fista_exact_kernel");
-  }
-  launch_generic(a, taps_dev, K, wind, J_dev != nullptr, true, P, (hipStream_t)stream);
-  return check_launch("fista_generic_kernel(f64)");
+  return solve_d("pb_fista_solve_d", false, nullptr, y_dev, ldy, y_rep, w_dev, ldw, P, N, taps_host, taps_dev, 0, K, step, nullptr, lbda,
+                 lbda_dev, betas_dev, n_iter, J_dev, ldj, stop_mode, tol, wind, n_done_dev, flags, stream);
 }
 
-int pb_fista_which_kernel_d(int N, int K, int with_cost_trace, int stop_mode, int wind) {
-  (void)with_cost_trace;                                // (every float64 form writes the cost trace)
-  if (N < 1 || K < 1) return 0;
-  bool split = false;
-  if (pick_exact_any(N, K, stop_mode, wind, &split)) return split ? 8 : 7;
-  return gen_lds_doubles(N, K, stop_mode, wind) <= LDS_DOUBLES_MAX ? 0 : -1;
-}
-
-// pb_fista_solve_d with one HRF and one step per problem, both in device memory: the register form with one problem
-// per wave (fista_exact_pp.h) where the shape has an entry, else the LDS kernel with FistaArgs::taps_pp.  The four-wave form
-// (fista_exact_split_pp.h, 641 .. 1 280 scans) runs only when PB_FLAG_PP_SPLIT names it: without the flag nothing changes
+// pb_fista_solve_d with one HRF and one step per problem, both in device memory.  The four-wave form (641 .. 1 280 scans)
+// runs only when PB_FLAG_PP_SPLIT names it: without the flag such series run on the LDS kernel with FistaArgs::taps_pp
 int pb_fista_solve_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
                         const double* taps_dev, int64_t ldt, int K, const double* step_dev, double lbda,
                         const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj,
                         int stop_mode, double tol, int wind, int32_t* n_done_dev, unsigned flags, void* stream) {
-  if (P < 0 || N < 1 || K < 1 || n_iter < 0 || y_rep < 1)
-    return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: bad size (P=%d N=%d K=%d n_iter=%d y_rep=%d)", P, N, K, n_iter, y_rep);
-  if (ldt < K) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: ldt < K");
-  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: leading dimension too small (< N)");
-  if (J_dev && ldj < n_iter) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: leading dimension too small (ldj < n_iter)");
-  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW)
-    return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: unknown stop_mode %d", stop_mode);
-  if (stop_mode == PB_STOP_WINDOW && wind < 2) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: wind must be >= 2");
-  if (flags & PB_FLAG_LONG_HRF) {               // opt-in: HRFs of up to 48 taps on the one-wave register form, or an error
-    const ExactLongEntry* le = nullptr;
-    const int rc = long_hrf_entry("pb_fista_solve_pp_d", N, K, stop_mode, wind, flags, &le);
-    if (rc != PB_OK) return rc;
-    if (P == 0) return PB_OK;
-    if (!y_dev || !w_dev || !taps_dev || !step_dev || (n_iter > 0 && !betas_dev))
-      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: NULL pointer");
-    if (P > (1 << 25)) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: more than 2^25 problems per launch");
-    pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, stop_mode, tol,
-                                 n_done_dev, flags);
-    a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj; a.wind = wind;
-    a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = 0;
-    if (le->fn_pp(a, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: launch rejected");
-    return check_launch("fista_exact_long_pp_kernel");
-  }
-  const ExactSplitPPEntry* se = nullptr;
-  if (flags & PB_FLAG_PP_SPLIT) {
-    if (flags & (PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_FAST))
-      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: PB_FLAG_PP_SPLIT names the four-wave form; it excludes PB_FLAG_FORCE_GENERIC and PB_FLAG_FORCE_FAST");
-    if (N < 641 || N > 1280) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: PB_FLAG_PP_SPLIT with N=%d outside 641..1280 scans", N);
-    if (K > 32) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: PB_FLAG_PP_SPLIT with K=%d exceeds 32 taps", K);
-    if (stop_mode == PB_STOP_WINDOW && wind != 6)
-      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: PB_FLAG_PP_SPLIT with wind=%d (the four-wave form carries wind = 6)", wind);
-    se = pick_exact_split_pp(N, K, stop_mode, wind);
-    if (!se) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: no four-wave specialisation for N=%d K=%d", N, K);
-  }
-  const ExactPPEntry* ee = (se || (flags & PB_FLAG_FORCE_GENERIC)) ? nullptr : pick_exact_pp(N, K, stop_mode, wind);
-  if (!ee && (flags & PB_FLAG_FORCE_FAST))
-    return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: no register-resident float64 kernel with one problem per wave for N=%d K=%d", N, K);
-  if (!ee && !se && gen_lds_doubles(N, K, stop_mode, wind) > LDS_DOUBLES_MAX)
-    return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: N=%d K=%d wind=%d exceeds LDS", N, K, wind);
-  if (P == 0) return PB_OK;
-  if (!y_dev || !w_dev || !taps_dev || !step_dev || (n_iter > 0 && !betas_dev))
-    return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: NULL pointer");
-  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: more than 2^25 problems per launch");
-  pb::FistaArgs a = fista_args(P, N, K, n_iter, y_rep, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, stop_mode, tol,
-                               n_done_dev, flags);
-  a.y64 = y_dev; a.J64 = J_dev; a.ldj = ldj; a.wind = wind;
-  a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = 0;
-  if (se) {
-    if (se->fn(a, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: launch rejected");
-    return check_launch("fista_exact_split_pp_kernel");
-  }
-  if (ee) {
-    if (ee->fn(a, J_dev != nullptr, stop_mode, (hipStream_t)stream) != 0)
-      return fail(PB_ERR_INVALID, "pb_fista_solve_pp_d: launch rejected");
-    return check_launch("fista_exact_pp_kernel");
-  }
-  launch_generic(a, taps_dev, K, wind, J_dev != nullptr, true, P, (hipStream_t)stream);
-  return check_launch("fista_generic_kernel(f64, pp)");
+  return solve_d("pb_fista_solve_pp_d", true, nullptr, y_dev, ldy, y_rep, w_dev, ldw, P, N, nullptr, taps_dev, ldt, K, 0.0, step_dev, lbda,
+                 lbda_dev, betas_dev, n_iter, J_dev, ldj, stop_mode, tol, wind, n_done_dev, flags, stream);
 }
 
-int pb_fista_pp_split_supported(int N, int K, int stop_mode, int wind) {
-  return pick_exact_split_pp(N, K, stop_mode, wind) ? 1 : 0;
+// the two on the four-wave form for HRFs of up to 48 taps, or an error: opt-in by name (the parameter list of
+// pb_fista_solve_d: only its LDS kernel reads taps_dev)
+int pb_fista_solve_split_long_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
+                                const double* taps_host, const double* taps_dev, int K, double step, double lbda,
+                                const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj, int stop_mode, double tol,
+                                int wind, int32_t* n_done_dev, unsigned flags, void* stream) {
+  return solve_d("pb_fista_solve_split_long_d", false, &kBySplitLongEntry, y_dev, ldy, y_rep, w_dev, ldw, P, N, taps_host, taps_dev, 0, K,
+                 step, nullptr, lbda, lbda_dev, betas_dev, n_iter, J_dev, ldj, stop_mode, tol, wind, n_done_dev, flags, stream);
 }
 
-int pb_fista_which_kernel_pp_d(int N, int K, int with_cost_trace, int stop_mode, int wind) {
-  (void)with_cost_trace;                                // (every float64 form writes the cost trace)
+int pb_fista_solve_split_long_pp_d(const double* y_dev, int64_t ldy, int y_rep, double* w_dev, int64_t ldw, int P, int N,
+                                   const double* taps_dev, int64_t ldt, int K, const double* step_dev, double lbda,
+                                   const double* lbda_dev, const double* betas_dev, int n_iter, double* J_dev, int64_t ldj,
+                                   int stop_mode, double tol, int wind, int32_t* n_done_dev, unsigned flags, void* stream) {
+  return solve_d("pb_fista_solve_split_long_pp_d", true, &kBySplitLongEntry, y_dev, ldy, y_rep, w_dev, ldw, P, N, nullptr, taps_dev, ldt, K,
+                 0.0, step_dev, lbda, lbda_dev, betas_dev, n_iter, J_dev, ldj, stop_mode, tol, wind, n_done_dev, flags, stream);
+}
+
+// what pb_fista_solve_d / pb_fista_solve_pp_d run for a call shape without flags (every float64 form writes the cost trace)
+int pb_fista_which_kernel_d(int N, int K, int with_cost_trace, int stop_mode, int wind) {
+  (void)with_cost_trace;
   if (N < 1 || K < 1) return 0;
-  if (pick_exact_pp(N, K, stop_mode, wind)) return 9;
+  int form = F64_ONE_WAVE;
+  if (pick_f64_default(N, K, stop_mode, wind, true, &form)) return form == F64_FOUR_WAVES ? 8 : 7;
   return gen_lds_doubles(N, K, stop_mode, wind) <= LDS_DOUBLES_MAX ? 0 : -1;
 }
 
-int pb_auto_lbda_supported(int N, int K, int wind) { return (wind == pb::AUTO_WIND && pick_auto(N, K)) ? 1 : 0; }
+int pb_fista_which_kernel_pp_d(int N, int K, int with_cost_trace, int stop_mode, int wind) {
+  (void)with_cost_trace;
+  if (N < 1 || K < 1) return 0;
+  if (pick_f64_default(N, K, stop_mode, wind, false)) return 9;
+  return gen_lds_doubles(N, K, stop_mode, wind) <= LDS_DOUBLES_MAX ? 0 : -1;
+}
 
 int64_t pb_auto_lbda_work_len(int V) { return (int64_t)pb::AUTO_STATE * (V > 0 ? V : 0); }
 
 namespace {
-// pb_auto_lbda_d (split = false: one voxel per wave, up to 640 scans) and pb_auto_lbda_split_d (one voxel per workgroup of
-// four waves, 641 .. 1 280 scans): one validation in one order, one launch protocol; the kernels and the library's chunk differ
-// (the long-HRF forms: up to 48 taps, one wave up to 640 scans, four waves for 641 .. 1 280, both opt-in)
-enum AutoForm { AUTO_ONE_WAVE = 0, AUTO_FOUR_WAVES = 1, AUTO_LONG_HRF = 2, AUTO_FOUR_WAVES_LONG_HRF = 3 };
-inline const char* auto_kernel_name(int form, bool pp, bool final_solve) {
-  static const char* const names[4][2][2] = {
-      {{"auto_lbda_kernel", "auto_lbda_kernel(final solve)"}, {"auto_lbda_pp_kernel", "auto_lbda_pp_kernel(final solve)"}},
-      {{"auto_lbda_split_kernel", "auto_lbda_split_kernel(final solve)"}, {"auto_lbda_split_pp_kernel", "auto_lbda_split_pp_kernel(final solve)"}},
-      {{"auto_lbda_long_kernel", "auto_lbda_long_kernel(final solve)"}, {"auto_lbda_long_pp_kernel", "auto_lbda_long_pp_kernel(final solve)"}},
-      {{"auto_lbda_split_long_kernel", "auto_lbda_split_long_kernel(final solve)"}, {"auto_lbda_split_long_pp_kernel", "auto_lbda_split_long_pp_kernel(final solve)"}}};
-  return names[form][pp][final_solve];
+int auto_lbda_supported(int form, int N, int K, int wind) {
+  return (wind == pb::AUTO_WIND && pick_f64(form, N, K, PB_STOP_WINDOW, wind)) ? 1 : 0;
 }
-inline int auto_form_chunk(int form, int V, int nb_sub_iter) {
-  return form == AUTO_FOUR_WAVES ? auto_split_outer_chunk(V, nb_sub_iter)
-         : form == AUTO_LONG_HRF ? auto_long_outer_chunk(V, nb_sub_iter)
-         : form == AUTO_FOUR_WAVES_LONG_HRF ? auto_split_long_outer_chunk(V, nb_sub_iter) : auto_outer_chunk(V, nb_sub_iter);
-}
-int auto_lbda_impl(const char* name, int form, const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
-                   const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
-                   int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
-                   double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
-                   int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
+
+// The eight device-resident lambda searches: the form is the entry point's; `pp` -- one HRF (taps_dev [V][ld_taps]) and one
+// step (step_dev [V]) per voxel instead of taps_host and step.  One validation in one order, one launch protocol: chunks of
+// outer iterations (the caller's outer_chunk, else the form's: auto_outer_chunk), then the final solve.  The launches with the
+// taps on the host receive the arguments as their AutoArgs base.  The argument lists differ where they must: the taps'
+// leading dimension exists with `pp` only, where the traces' is not called ldt; the step's sign is checked where it is a number.
+int auto_lbda(const char* name, int form, bool pp, const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
+              const double* taps_host, const double* taps_dev, int64_t ld_taps, int K, double step, const double* step_dev,
+              const double* betas_dev, const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter,
+              int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ld_traces, double* alpha_dev,
+              double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
+  const F64FormDesc& d = kF64[form];
   if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "%s: bad size (V=%d N=%d K=%d)", name, V, N, K);
-  if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "%s: wind=%d (the device-resident search carries wind = 6)", name, wind);
-  const bool split = form == AUTO_FOUR_WAVES || form == AUTO_FOUR_WAVES_LONG_HRF;
-  const int k_max = (form == AUTO_LONG_HRF || form == AUTO_FOUR_WAVES_LONG_HRF) ? LONG_HRF_KMAX : 32;
-  if (!split && N > 640) return fail(PB_ERR_INVALID, "%s: N=%d exceeds 640 scans", name, N);
-  if (split && (N < 641 || N > 1280)) return fail(PB_ERR_INVALID, "%s: N=%d outside 641..1280 scans", name, N);
-  if (K > k_max) return fail(PB_ERR_INVALID, "%s: K=%d exceeds %d taps", name, K, k_max);
-  auto_launch_fn fn_auto = nullptr;
-  if (form == AUTO_LONG_HRF || form == AUTO_FOUR_WAVES_LONG_HRF) {
-    const ExactLongEntry* le = form == AUTO_LONG_HRF ? pick_exact_long(N, K, PB_STOP_WINDOW, wind)
-                                                     : pick_exact_split_long(N, K, PB_STOP_WINDOW, wind);
-    fn_auto = le ? le->fn_auto : nullptr;
-  } else {
-    const ExactEntry* ae = split ? pick_auto_split(N, K) : pick_auto(N, K);
-    fn_auto = ae ? ae->fn_auto : nullptr;
-  }
-  if (!fn_auto) return fail(PB_ERR_INVALID, "%s: no specialisation for N=%d K=%d", name, N, K);
+  if (wind != pb::AUTO_WIND)
+    return fail(PB_ERR_INVALID, "%s: wind=%d (the device-resident search carries wind = %d)", name, wind, pb::AUTO_WIND);
+  if (N < d.n_min || N > d.n_max)
+    return d.n_min > 1 ? fail(PB_ERR_INVALID, "%s: N=%d outside %d..%d scans", name, N, d.n_min, d.n_max)
+                       : fail(PB_ERR_INVALID, "%s: N=%d exceeds %d scans", name, N, d.n_max);
+  if (K > d.k_max) return fail(PB_ERR_INVALID, "%s: K=%d exceeds %d taps", name, K, d.k_max);
+  const ExactEntry* e = pick_f64(form, N, K, PB_STOP_WINDOW, wind);
+  if (!e) return fail(PB_ERR_INVALID, "%s: no specialisation for N=%d K=%d", name, N, K);
   if (nb_iter < 1 || nb_sub_iter < 0 || outer_chunk < 0)
     return fail(PB_ERR_INVALID, "%s: nb_iter >= 1, nb_sub_iter >= 0 and outer_chunk >= 0 are required (%d, %d, %d)", name,
                 nb_iter, nb_sub_iter, outer_chunk);
   if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "%s: leading dimension < N", name);
-  if ((R_dev || G_dev || J_dev) && ldt < nb_iter) return fail(PB_ERR_INVALID, "%s: ldt < nb_iter", name);
-  if (!(step > 0.0)) return fail(PB_ERR_INVALID, "%s: step must be positive", name);
+  if (pp && ld_taps < K) return fail(PB_ERR_INVALID, "%s: ldt < K", name);
+  if ((R_dev || G_dev || J_dev) && ld_traces < nb_iter)
+    return fail(PB_ERR_INVALID, pp ? "%s: leading dimension of the traces < nb_iter" : "%s: ldt < nb_iter", name);
+  if (!pp && !(step > 0.0)) return fail(PB_ERR_INVALID, "%s: step must be positive", name);
   if (work_len < pb_auto_lbda_work_len(V))
     return fail(PB_ERR_INVALID, "%s: workspace of %lld float64, %lld needed", name, (long long)work_len,
                 (long long)pb_auto_lbda_work_len(V));
   if (V == 0) return PB_OK;
-  if (!y_dev || !w_dev || !taps_host || !sigma_dev || !work_dev || (nb_sub_iter > 0 && !betas_dev))
-    return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
-  if (V > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 voxels per call", name);
-  pb::AutoArgs a;
-  a.y = y_dev; a.ldy = ldy; a.w = w_dev; a.ldw = ldw; a.V = V; a.N = N;
-  a.cold = cold ? 1 : 0; a.nb_sub_iter = nb_sub_iter; a.step = step; a.tol = tol;
-  a.betas = betas_dev; a.sigma = sigma_dev; a.R = R_dev; a.G = G_dev; a.J = J_dev; a.ldt = ldt;
-  a.alpha_out = alpha_dev; a.lbda_out = lbda_dev; a.n_outer = n_outer_dev; a.n_inner = n_inner_dev; a.work = work_dev;
-  const int chunk = outer_chunk > 0 ? outer_chunk : auto_form_chunk(form, V, nb_sub_iter);
-  for (int i0 = 0; i0 < nb_iter; i0 += chunk) {        // outer iterations [i0, i1) of the voxels still searching
-    a.init = i0 == 0; a.i0 = i0; a.i1 = (nb_iter - i0 < chunk) ? nb_iter : i0 + chunk; a.final_solve = 0;
-    fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
-    const int rc = check_launch(auto_kernel_name(form, false, false));
-    if (rc != PB_OK) return rc;
-  }
-  a.init = 0; a.i0 = a.i1 = nb_iter; a.final_solve = 1;   // the last inner solve of every voxel, then the outputs
-  fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
-  return check_launch(auto_kernel_name(form, false, true));
-}
-}  // namespace
-
-int pb_auto_lbda_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
-                   const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
-                   int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
-                   double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
-                   int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
-  return auto_lbda_impl("pb_auto_lbda_d", AUTO_ONE_WAVE, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev, sigma_dev,
-                        early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt, alpha_dev, lbda_dev,
-                        n_outer_dev, n_inner_dev, work_dev, work_len, stream);
-}
-
-// pb_auto_lbda_d with one HRF (taps_dev [V][ldt]) and one step (step_dev [V]) per voxel: its validation in its order (the
-// taps' leading dimension beside the others, the step's sign is the caller's), its chunk, its launch protocol
-// (split = true: pb_auto_lbda_split_pp_d, one voxel per workgroup of four waves, 641 .. 1 280 scans, with the limits and the
-// chunk of pb_auto_lbda_split_d)
-namespace {
-int auto_lbda_pp_impl(const char* name, int form, const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
-                      const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
-                      const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
-                      int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
-                      double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
-                      void* stream) {
-  if (V < 0 || N < 1 || K < 1) return fail(PB_ERR_INVALID, "%s: bad size (V=%d N=%d K=%d)", name, V, N, K);
-  if (wind != pb::AUTO_WIND) return fail(PB_ERR_INVALID, "%s: wind=%d (the device-resident search carries wind = 6)", name, wind);
-  const bool split = form == AUTO_FOUR_WAVES || form == AUTO_FOUR_WAVES_LONG_HRF;
-  const int k_max = (form == AUTO_LONG_HRF || form == AUTO_FOUR_WAVES_LONG_HRF) ? LONG_HRF_KMAX : 32;
-  if (!split && N > 640) return fail(PB_ERR_INVALID, "%s: N=%d exceeds 640 scans", name, N);
-  if (split && (N < 641 || N > 1280)) return fail(PB_ERR_INVALID, "%s: N=%d outside 641..1280 scans", name, N);
-  if (K > k_max) return fail(PB_ERR_INVALID, "%s: K=%d exceeds %d taps", name, K, k_max);
-  auto_pp_launch_fn fn_auto = nullptr;
-  if (form == AUTO_LONG_HRF || form == AUTO_FOUR_WAVES_LONG_HRF) {
-    const ExactLongEntry* le = form == AUTO_LONG_HRF ? pick_exact_long(N, K, PB_STOP_WINDOW, wind)
-                                                     : pick_exact_split_long(N, K, PB_STOP_WINDOW, wind);
-    fn_auto = le ? le->fn_auto_pp : nullptr;
-  } else if (split) {
-    const ExactSplitPPEntry* se = pick_auto_split(N, K) ? pick_exact_split_pp(N, K, PB_STOP_WINDOW, wind) : nullptr;
-    fn_auto = se ? se->fn_auto : nullptr;
-  } else {
-    const ExactPPEntry* ae = pick_auto(N, K) ? pick_exact_pp(N, K, PB_STOP_WINDOW, wind) : nullptr;
-    fn_auto = ae ? ae->fn_auto : nullptr;
-  }
-  if (!fn_auto) return fail(PB_ERR_INVALID, "%s: no specialisation for N=%d K=%d", name, N, K);
-  if (nb_iter < 1 || nb_sub_iter < 0 || outer_chunk < 0)
-    return fail(PB_ERR_INVALID, "%s: nb_iter >= 1, nb_sub_iter >= 0 and outer_chunk >= 0 are required (%d, %d, %d)", name,
-                nb_iter, nb_sub_iter, outer_chunk);
-  if (ldy < N || ldw < N) return fail(PB_ERR_INVALID, "%s: leading dimension < N", name);
-  if (ldt < K) return fail(PB_ERR_INVALID, "%s: ldt < K", name);
-  if ((R_dev || G_dev || J_dev) && ldtr < nb_iter) return fail(PB_ERR_INVALID, "%s: leading dimension of the traces < nb_iter", name);
-  if (work_len < pb_auto_lbda_work_len(V))
-    return fail(PB_ERR_INVALID, "%s: workspace of %lld float64, %lld needed", name, (long long)work_len,
-                (long long)pb_auto_lbda_work_len(V));
-  if (V == 0) return PB_OK;
-  if (!y_dev || !w_dev || !taps_dev || !step_dev || !sigma_dev || !work_dev || (nb_sub_iter > 0 && !betas_dev))
+  if (!y_dev || !w_dev || (pp ? !taps_dev || !step_dev : !taps_host) || !sigma_dev || !work_dev || (nb_sub_iter > 0 && !betas_dev))
     return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
   if (V > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 voxels per call", name);
   pb::AutoArgsPP a;
   a.y = y_dev; a.ldy = ldy; a.w = w_dev; a.ldw = ldw; a.V = V; a.N = N;
-  a.cold = cold ? 1 : 0; a.nb_sub_iter = nb_sub_iter; a.step = 0.0; a.tol = tol;
-  a.betas = betas_dev; a.sigma = sigma_dev; a.R = R_dev; a.G = G_dev; a.J = J_dev; a.ldt = ldtr;
+  a.cold = cold ? 1 : 0; a.nb_sub_iter = nb_sub_iter; a.step = pp ? 0.0 : step; a.tol = tol;
+  a.betas = betas_dev; a.sigma = sigma_dev; a.R = R_dev; a.G = G_dev; a.J = J_dev; a.ldt = ld_traces;
   a.alpha_out = alpha_dev; a.lbda_out = lbda_dev; a.n_outer = n_outer_dev; a.n_inner = n_inner_dev; a.work = work_dev;
-  a.taps_pp = taps_dev; a.ld_taps = ldt; a.step_vec = step_dev; a.K = K;
-  const int chunk = outer_chunk > 0 ? outer_chunk : auto_form_chunk(form, V, nb_sub_iter);
+  a.taps_pp = taps_dev; a.ld_taps = ld_taps; a.step_vec = step_dev; a.K = K;
+  auto launch = [&] {
+    return pp ? e->fn_auto_pp(a, early_stopping != 0, (hipStream_t)stream)
+              : e->fn_auto(a, taps_host, K, early_stopping != 0, (hipStream_t)stream);
+  };
+  const int chunk = outer_chunk > 0 ? outer_chunk : auto_outer_chunk(form, V, nb_sub_iter);
   for (int i0 = 0; i0 < nb_iter; i0 += chunk) {        // outer iterations [i0, i1) of the voxels still searching
     a.init = i0 == 0; a.i0 = i0; a.i1 = (nb_iter - i0 < chunk) ? nb_iter : i0 + chunk; a.final_solve = 0;
-    if (fn_auto(a, early_stopping != 0, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
-    const int rc = check_launch(auto_kernel_name(form, true, false));
+    if (launch() != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
+    const int rc = check_f64_launch("auto_lbda", form, pp);
     if (rc != PB_OK) return rc;
   }
   a.init = 0; a.i0 = a.i1 = nb_iter; a.final_solve = 1;   // the last inner solve of every voxel, then the outputs
-  if (fn_auto(a, early_stopping != 0, (hipStream_t)stream) != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
-  return check_launch(auto_kernel_name(form, true, true));
+  if (launch() != 0) return fail(PB_ERR_INVALID, "%s: launch rejected", name);
+  return check_f64_launch("auto_lbda", form, pp, true);
 }
 }  // namespace
 
-int pb_auto_lbda_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
-                      const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
-                      const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
-                      int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
-                      double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
-                      void* stream) {
-  return auto_lbda_pp_impl("pb_auto_lbda_pp_d", AUTO_ONE_WAVE, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev, betas_dev,
-                           sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldtr,
-                           alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
-}
+int pb_auto_lbda_supported(int N, int K, int wind) { return auto_lbda_supported(F64_ONE_WAVE, N, K, wind); }
+int pb_auto_lbda_split_supported(int N, int K, int wind) { return auto_lbda_supported(F64_FOUR_WAVES, N, K, wind); }
+int pb_auto_lbda_long_supported(int N, int K, int wind) { return auto_lbda_supported(F64_LONG_HRF, N, K, wind); }
+int pb_auto_lbda_split_long_supported(int N, int K, int wind) { return auto_lbda_supported(F64_FOUR_WAVES_LONG_HRF, N, K, wind); }
 
-int pb_auto_lbda_split_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
-                            const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
-                            const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
-                            int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
-                            double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
-                            void* stream) {
-  return auto_lbda_pp_impl("pb_auto_lbda_split_pp_d", AUTO_FOUR_WAVES, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev, betas_dev,
-                           sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldtr,
-                           alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
-}
-
-int pb_auto_lbda_long_supported(int N, int K, int wind) {
-  return (wind == pb::AUTO_WIND && pick_exact_long(N, K, PB_STOP_WINDOW, wind)) ? 1 : 0;
-}
-
-int pb_auto_lbda_long_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
-                        const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
-                        int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
-                        double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
-                        int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
-  return auto_lbda_impl("pb_auto_lbda_long_d", AUTO_LONG_HRF, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev,
-                        sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt, alpha_dev,
-                        lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
-}
-
-int pb_auto_lbda_long_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
-                           const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
-                           const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
-                           int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
-                           double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
-                           void* stream) {
-  return auto_lbda_pp_impl("pb_auto_lbda_long_pp_d", AUTO_LONG_HRF, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt, K, step_dev,
-                           betas_dev, sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev,
-                           ldtr, alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
-}
-
-int pb_auto_lbda_split_long_supported(int N, int K, int wind) {
-  return (wind == pb::AUTO_WIND && pick_exact_split_long(N, K, PB_STOP_WINDOW, wind)) ? 1 : 0;
-}
-
-int pb_auto_lbda_split_long_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
-                              const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
-                              int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
-                              double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
-                              int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
-  return auto_lbda_impl("pb_auto_lbda_split_long_d", AUTO_FOUR_WAVES_LONG_HRF, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step,
-                        betas_dev, sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt,
-                        alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
-}
-
-int pb_auto_lbda_split_long_pp_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
-                                 const double* taps_dev, int64_t ldt, int K, const double* step_dev, const double* betas_dev,
-                                 const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter,
-                                 int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldtr, double* alpha_dev,
-                                 double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len,
-                                 void* stream) {
-  return auto_lbda_pp_impl("pb_auto_lbda_split_long_pp_d", AUTO_FOUR_WAVES_LONG_HRF, y_dev, ldy, w_dev, ldw, cold, V, N, taps_dev, ldt,
-                           K, step_dev, betas_dev, sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev,
-                           J_dev, ldtr, alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);
-}
-
-int pb_auto_lbda_split_supported(int N, int K, int wind) { return (wind == pb::AUTO_WIND && pick_auto_split(N, K)) ? 1 : 0; }
-
-int pb_auto_lbda_split_d(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N,
-                         const double* taps_host, int K, double step, const double* betas_dev, const double* sigma_dev,
-                         int early_stopping, double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk,
-                         double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev, double* lbda_dev,
-                         int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {
-  return auto_lbda_impl("pb_auto_lbda_split_d", AUTO_FOUR_WAVES, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, K, step, betas_dev, sigma_dev,
-                        early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt, alpha_dev, lbda_dev,
-                        n_outer_dev, n_inner_dev, work_dev, work_len, stream);
-}
+// the eight entry points: two parameter lists (taps_host, K, step / taps_dev, ldt, K, step_dev), four forms
+#define PB_AUTO_LBDA_D(fn, form)                                                                                                \
+  int fn(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N, const double* taps_host, int K,    \
+         double step, const double* betas_dev, const double* sigma_dev, int early_stopping, double tol, int wind, int nb_iter,    \
+         int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev, int64_t ldt, double* alpha_dev,           \
+         double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev, int64_t work_len, void* stream) {        \
+    return auto_lbda(#fn, form, false, y_dev, ldy, w_dev, ldw, cold, V, N, taps_host, nullptr, 0, K, step, nullptr, betas_dev,    \
+                     sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldt, alpha_dev, \
+                     lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);                                             \
+  }
+#define PB_AUTO_LBDA_PP_D(fn, form)                                                                                             \
+  int fn(const double* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int cold, int V, int N, const double* taps_dev,            \
+         int64_t ldt, int K, const double* step_dev, const double* betas_dev, const double* sigma_dev, int early_stopping,        \
+         double tol, int wind, int nb_iter, int nb_sub_iter, int outer_chunk, double* R_dev, double* G_dev, double* J_dev,        \
+         int64_t ldtr, double* alpha_dev, double* lbda_dev, int32_t* n_outer_dev, int64_t* n_inner_dev, double* work_dev,         \
+         int64_t work_len, void* stream) {                                                                                        \
+    return auto_lbda(#fn, form, true, y_dev, ldy, w_dev, ldw, cold, V, N, nullptr, taps_dev, ldt, K, 0.0, step_dev, betas_dev,    \
+                     sigma_dev, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, R_dev, G_dev, J_dev, ldtr,          \
+                     alpha_dev, lbda_dev, n_outer_dev, n_inner_dev, work_dev, work_len, stream);                                  \
+  }
+PB_AUTO_LBDA_D(pb_auto_lbda_d, F64_ONE_WAVE)
+PB_AUTO_LBDA_D(pb_auto_lbda_split_d, F64_FOUR_WAVES)
+PB_AUTO_LBDA_D(pb_auto_lbda_long_d, F64_LONG_HRF)
+PB_AUTO_LBDA_D(pb_auto_lbda_split_long_d, F64_FOUR_WAVES_LONG_HRF)
+PB_AUTO_LBDA_PP_D(pb_auto_lbda_pp_d, F64_ONE_WAVE)
+PB_AUTO_LBDA_PP_D(pb_auto_lbda_split_pp_d, F64_FOUR_WAVES)
+PB_AUTO_LBDA_PP_D(pb_auto_lbda_long_pp_d, F64_LONG_HRF)
+PB_AUTO_LBDA_PP_D(pb_auto_lbda_split_long_pp_d, F64_FOUR_WAVES_LONG_HRF)
+#undef PB_AUTO_LBDA_D
+#undef PB_AUTO_LBDA_PP_D
 
 int pb_mad_daub_noise_est(const float* y_dev, int64_t ldy, int V, int N, double c, double* sigma_dev, void* stream) {
   return mad_daub_impl<float>(y_dev, ldy, V, N, c, sigma_dev, stream, "pb_mad_daub_noise_est");

@@ -157,137 +157,36 @@ const WideEntry kWide[] = {
 #undef PB_WIDE
 
 // cheapest entry of a table (by S * KT) that holds N scans at `per_lane` scans per unit of S, and K taps
-template <class Entry, size_t n>
-const Entry* pick_cheapest(const Entry (&tab)[n], int N, int K, int per_lane) {
+template <class Entry>
+const Entry* pick_cheapest(const Entry* tab, size_t n, int N, int K, int per_lane) {
   const Entry* best = nullptr;
   const int s_need = (N + per_lane - 1) / per_lane;
-  for (const Entry& e : tab) {
-    if (e.S < s_need || e.KT < K) continue;
-    if (!best || (int64_t)e.S * e.KT < (int64_t)best->S * best->KT) best = &e;
+  for (const Entry* e = tab; e != tab + n; ++e) {
+    if (e->S < s_need || e->KT < K) continue;
+    if (!best || (int64_t)e->S * e->KT < (int64_t)best->S * best->KT) best = e;
   }
   return best;
 }
+template <class Entry, size_t n>
+const Entry* pick_cheapest(const Entry (&tab)[n], int N, int K, int per_lane) { return pick_cheapest(tab, n, N, K, per_lane); }
 const WideEntry* pick_wide(int N, int K) { return pick_cheapest(kWide, N, K, 64); }
-
-typedef int (*exact_launch_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j, int stop,
-                               hipStream_t);
-typedef int (*auto_launch_fn)(const pb::AutoArgs&, const double* taps, int K, bool early_stopping, hipStream_t);
-struct ExactEntry {
-  int S, KT;
-  exact_launch_fn fn;
-  auto_launch_fn fn_auto;     // the device-resident lambda search on the same (S, KT): fista_auto.h, or fista_auto_split.h with four waves per series
-};
-}  // namespace
-namespace pb {
-#define PB_EXACT(S, KT)                                                                                    \
-  extern template int launch_exact<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t); \
-  extern template int launch_auto<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);
-#include "exact_table.inc"
-#undef PB_EXACT
-#define PB_EXACT_SPLIT(S, KT)                                                                                    \
-  extern template int launch_exact_split<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t); \
-  extern template int launch_auto_split<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);
-#include "exact_split_table.inc"
-#undef PB_EXACT_SPLIT
-}  // namespace pb
-namespace {
-#define PB_EXACT(S, KT) {S, KT, &pb::launch_exact<S, KT>, &pb::launch_auto<S, KT>},
-const ExactEntry kExact[] = {
-#include "exact_table.inc"
-};
-#undef PB_EXACT
-// the same form with one series over the four waves of a workgroup (fista_exact_split.h): S samples per lane of each wave
-#define PB_EXACT_SPLIT(S, KT) {S, KT, &pb::launch_exact_split<S, KT>, &pb::launch_auto_split<S, KT>},
-const ExactEntry kExactSplit[] = {
-#include "exact_split_table.inc"
-};
-#undef PB_EXACT_SPLIT
 
 // window lengths the register-resident forms carry (increment ring of wind - 2 slots in LDS)
 inline bool ring_wind(int wind) { return wind == 4 || wind == 6 || wind == 8; }
 // an entry of S samples per lane carries the call's stop rule: the window rule needs its increment ring (S <= 20)
 inline bool ring_fits(int S, int stop_mode, int wind) { return stop_mode != PB_STOP_WINDOW || (ring_wind(wind) && S <= 20); }
 
-// all-float64 register-resident form (one problem per wave)
-const ExactEntry* pick_exact(int N, int K) { return pick_cheapest(kExact, N, K, 64); }
-// four waves per series: the shapes beyond the one-wave entries (641 .. 1 280 scans)
-const ExactEntry* pick_exact_split(int N, int K) {
-  return pick_exact(N, K) ? nullptr : pick_cheapest(kExactSplit, N, K, 64 * pb::SPLIT_WAVES);
-}
-// the float64 register form that carries a call: one wave per series, else four; the window rule of both is wind = 6
-const ExactEntry* pick_exact_any(int N, int K, int stop_mode, int wind, bool* split) {
-  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
-  const ExactEntry* e = pick_exact(N, K);
-  if (split) *split = !e;
-  return e ? e : pick_exact_split(N, K);
-}
-// the device-resident lambda search (fista_auto.h): the (S, KT) pairs of the all-float64 form
-const ExactEntry* pick_auto(int N, int K) { return (N >= 1 && K >= 1) ? pick_exact(N, K) : nullptr; }
-// ... with one voxel over the four waves of a workgroup (fista_auto_split.h): the shapes of the four-wave float64 form
-const ExactEntry* pick_auto_split(int N, int K) { return (N >= 1 && K >= 1) ? pick_exact_split(N, K) : nullptr; }
-
-// one HRF and one step per problem, in device memory (fista_exact_pp.h): the (S, KT) pairs of the all-float64 form
+// ---- the float64 register-resident family (fista_exact*.h, fista_auto*.h) ------------------------------------------------
+// Four forms (F64Form), each with four kinds of launch on the same (S, KT): the solve and the device-resident lambda search,
+// with the taps on the host or with one HRF and one step per problem in device memory ("pp").  A form is one table of
+// entries (its .inc file) and one descriptor (kF64); pick_f64 is the only picker.  Only the one-wave form, and behind it the
+// four-wave form for calls with the taps on the host, is ever chosen by the library (pick_f64_default): every other route to
+// a form is OPT-IN, by a flag (PB_FLAG_LONG_HRF, PB_FLAG_PP_SPLIT) or by the name of the entry point.
+typedef int (*exact_launch_fn)(const pb::FistaArgs&, const double* taps, int K, bool with_j, int stop, hipStream_t);
+typedef int (*auto_launch_fn)(const pb::AutoArgs&, const double* taps, int K, bool early_stopping, hipStream_t);
 typedef int (*exact_pp_launch_fn)(const pb::FistaArgs&, bool with_j, int stop, hipStream_t);
 typedef int (*auto_pp_launch_fn)(const pb::AutoArgsPP&, bool early_stopping, hipStream_t);
-struct ExactPPEntry {
-  int S, KT;
-  exact_pp_launch_fn fn;
-  auto_pp_launch_fn fn_auto;
-};
-}  // namespace
-namespace pb {
-#define PB_EXACT(S, KT)                                                                  \
-  extern template int launch_exact_pp<S, KT>(const FistaArgs&, bool, int, hipStream_t); \
-  extern template int launch_auto_pp<S, KT>(const AutoArgsPP&, bool, hipStream_t);
-#include "exact_table.inc"
-#undef PB_EXACT
-}  // namespace pb
-namespace {
-#define PB_EXACT(S, KT) {S, KT, &pb::launch_exact_pp<S, KT>, &pb::launch_auto_pp<S, KT>},
-const ExactPPEntry kExactPP[] = {
-#include "exact_table.inc"
-};
-#undef PB_EXACT
-// the window rule of the register form is wind = 6; no four-wave form behind it
-const ExactPPEntry* pick_exact_pp(int N, int K, int stop_mode, int wind) {
-  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
-  return pick_cheapest(kExactPP, N, K, 64);
-}
-
-// ... and with one problem over the four waves of a workgroup (fista_exact_split_pp.h): the pairs of
-// exact_split_table.inc.  OPT-IN: pick_exact_pp above never falls through to it -- PB_FLAG_PP_SPLIT and
-// pb_auto_lbda_split_pp_d name it
-struct ExactSplitPPEntry {
-  int S, KT;
-  exact_pp_launch_fn fn;
-  auto_pp_launch_fn fn_auto;
-};
-}  // namespace
-namespace pb {
-#define PB_EXACT_SPLIT(S, KT)                                                                  \
-  extern template int launch_exact_split_pp<S, KT>(const FistaArgs&, bool, int, hipStream_t); \
-  extern template int launch_auto_split_pp<S, KT>(const AutoArgsPP&, bool, hipStream_t);
-#include "exact_split_table.inc"
-#undef PB_EXACT_SPLIT
-}  // namespace pb
-namespace {
-#define PB_EXACT_SPLIT(S, KT) {S, KT, &pb::launch_exact_split_pp<S, KT>, &pb::launch_auto_split_pp<S, KT>},
-const ExactSplitPPEntry kExactSplitPP[] = {
-#include "exact_split_table.inc"
-};
-#undef PB_EXACT_SPLIT
-// the shapes beyond the one-wave entries only (641 .. 1 280 scans); the window rule is wind = 6
-const ExactSplitPPEntry* pick_exact_split_pp(int N, int K, int stop_mode, int wind) {
-  if (N < 1 || K < 1 || pick_exact(N, K)) return nullptr;
-  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return nullptr;
-  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
-  return N > 640 ? pick_cheapest(kExactSplitPP, N, K, 64 * pb::SPLIT_WAVES) : nullptr;
-}
-
-// ... and HRFs of up to 48 taps with the taps in one VGPR pair of the wave (fista_exact_long.h): the pairs of
-// exact_long_table.inc.  OPT-IN: no picker above falls through to it -- PB_FLAG_LONG_HRF, pb_auto_lbda_long_d and
-// pb_auto_lbda_long_pp_d name it
-struct ExactLongEntry {
+struct ExactEntry {
   int S, KT;
   exact_launch_fn fn;
   auto_launch_fn fn_auto;
@@ -295,59 +194,123 @@ struct ExactLongEntry {
   auto_pp_launch_fn fn_auto_pp;
 };
 }  // namespace
+// the four launches of a pair (S, KT) of a form, instantiated in one translation unit each (Makefile: EXACTFAMILY)
+#define PB_F64_EXTERN(SOLVE, SEARCH, S, KT)                                                           \
+  extern template int SOLVE<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t);    \
+  extern template int SEARCH<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);         \
+  extern template int SOLVE##_pp<S, KT>(const FistaArgs&, bool, int, hipStream_t);                   \
+  extern template int SEARCH##_pp<S, KT>(const AutoArgsPP&, bool, hipStream_t);
+#define PB_F64_ENTRY(SOLVE, SEARCH, S, KT) {S, KT, &pb::SOLVE<S, KT>, &pb::SEARCH<S, KT>, &pb::SOLVE##_pp<S, KT>, &pb::SEARCH##_pp<S, KT>},
 namespace pb {
-#define PB_EXACT_LONG(S, KT)                                                                                  \
-  extern template int launch_exact_long<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t); \
-  extern template int launch_auto_long<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);        \
-  extern template int launch_exact_long_pp<S, KT>(const FistaArgs&, bool, int, hipStream_t);                  \
-  extern template int launch_auto_long_pp<S, KT>(const AutoArgsPP&, bool, hipStream_t);
+#define PB_EXACT(S, KT) PB_F64_EXTERN(launch_exact, launch_auto, S, KT)
+#include "exact_table.inc"
+#undef PB_EXACT
+#define PB_EXACT_SPLIT(S, KT) PB_F64_EXTERN(launch_exact_split, launch_auto_split, S, KT)
+#include "exact_split_table.inc"
+#undef PB_EXACT_SPLIT
+#define PB_EXACT_LONG(S, KT) PB_F64_EXTERN(launch_exact_long, launch_auto_long, S, KT)
 #include "exact_long_table.inc"
 #undef PB_EXACT_LONG
+#define PB_EXACT_SPLIT_LONG(S, KT) PB_F64_EXTERN(launch_exact_split_long, launch_auto_split_long, S, KT)
+#include "exact_split_long_table.inc"
+#undef PB_EXACT_SPLIT_LONG
 }  // namespace pb
 namespace {
-#define PB_EXACT_LONG(S, KT) \
-  {S, KT, &pb::launch_exact_long<S, KT>, &pb::launch_auto_long<S, KT>, &pb::launch_exact_long_pp<S, KT>, &pb::launch_auto_long_pp<S, KT>},
-const ExactLongEntry kExactLong[] = {
+// one problem per wave (fista_exact.h, fista_auto.h, fista_exact_pp.h)
+#define PB_EXACT(S, KT) PB_F64_ENTRY(launch_exact, launch_auto, S, KT)
+const ExactEntry kExact[] = {
+#include "exact_table.inc"
+};
+#undef PB_EXACT
+// one problem over the four waves of a workgroup, S samples per lane of each wave (fista_exact_split.h, fista_auto_split.h,
+// fista_exact_split_pp.h)
+#define PB_EXACT_SPLIT(S, KT) PB_F64_ENTRY(launch_exact_split, launch_auto_split, S, KT)
+const ExactEntry kExactSplit[] = {
+#include "exact_split_table.inc"
+};
+#undef PB_EXACT_SPLIT
+// HRFs of up to 48 taps, the taps in one VGPR pair of the wave (fista_exact_long.h)
+#define PB_EXACT_LONG(S, KT) PB_F64_ENTRY(launch_exact_long, launch_auto_long, S, KT)
+const ExactEntry kExactLong[] = {
 #include "exact_long_table.inc"
 };
 #undef PB_EXACT_LONG
-constexpr int LONG_HRF_NMAX = 640, LONG_HRF_KMAX = 48;
-// the window rule is wind = 6
-const ExactLongEntry* pick_exact_long(int N, int K, int stop_mode, int wind) {
-  if (N < 1 || N > LONG_HRF_NMAX || K < 1 || K > LONG_HRF_KMAX) return nullptr;
-  if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return nullptr;
-  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
-  return pick_cheapest(kExactLong, N, K, 64);
-}
+// ... and the same holder over the four waves of a workgroup (fista_exact_split_long.h)
+#define PB_EXACT_SPLIT_LONG(S, KT) PB_F64_ENTRY(launch_exact_split_long, launch_auto_split_long, S, KT)
+const ExactEntry kExactSplitLong[] = {
+#include "exact_split_long_table.inc"
+};
+#undef PB_EXACT_SPLIT_LONG
+#undef PB_F64_EXTERN
+#undef PB_F64_ENTRY
 
-// ... and the same holder over the four waves of a workgroup (fista_exact_split_long.h): 641 .. 1 280 scans, up to 48 taps,
-// the pairs of exact_split_long_table.inc.  OPT-IN: no picker above falls through to it -- pb_fista_solve_split_long_d,
-// pb_auto_lbda_split_long_d and pb_auto_lbda_split_long_pp_d name it
-}  // namespace
-namespace pb {
-#define PB_EXACT_SPLIT_LONG(S, KT)                                                                                  \
-  extern template int launch_exact_split_long<S, KT>(const FistaArgs&, const double*, int, bool, int, hipStream_t); \
-  extern template int launch_auto_split_long<S, KT>(const AutoArgs&, const double*, int, bool, hipStream_t);        \
-  extern template int launch_exact_split_long_pp<S, KT>(const FistaArgs&, bool, int, hipStream_t);                  \
-  extern template int launch_auto_split_long_pp<S, KT>(const AutoArgsPP&, bool, hipStream_t);
-#include "exact_split_long_table.inc"
-#undef PB_EXACT_SPLIT_LONG
-}  // namespace pb
-namespace {
-#define PB_EXACT_SPLIT_LONG(S, KT)                                                                                          \
-  {S, KT, &pb::launch_exact_split_long<S, KT>, &pb::launch_auto_split_long<S, KT>, &pb::launch_exact_split_long_pp<S, KT>, \
-   &pb::launch_auto_split_long_pp<S, KT>},
-const ExactLongEntry kExactSplitLong[] = {
-#include "exact_split_long_table.inc"
+enum F64Form { F64_ONE_WAVE, F64_FOUR_WAVES, F64_LONG_HRF, F64_FOUR_WAVES_LONG_HRF, F64_FORMS };
+struct F64FormDesc {
+  int n_min, n_max;               // scans
+  int k_max;                      // taps
+  int per_lane;                   // scans per unit of S: the lanes of a wave, or of the four waves of a workgroup
+  const ExactEntry* tab;
+  size_t n_tab;
+  // the search's outer iterations per launch when the caller leaves the choice to the library (capi.hip: auto_outer_chunk):
+  // inner iterations per resident unit and launch, and the units (waves or workgroups) the machine holds at once
+  int auto_launch_iters, auto_resident;
+  const char* kernels;            // what check_launch is told: fista_exact<kernels>[_pp]_kernel, auto_lbda<kernels>[_pp]_kernel
+  const char* label;              // how a message names the form ("%d": k_max) ...
+  const char* noun;               // ... and what it calls it
+  const char* taps_over;          // ... and how a solve words K > k_max
 };
-#undef PB_EXACT_SPLIT_LONG
-constexpr int SPLIT_LONG_NMIN = 641, SPLIT_LONG_NMAX = 1280;
-// the window rule is wind = 6
-const ExactLongEntry* pick_exact_split_long(int N, int K, int stop_mode, int wind) {
-  if (N < SPLIT_LONG_NMIN || N > SPLIT_LONG_NMAX || K < 1 || K > LONG_HRF_KMAX) return nullptr;
+template <size_t n>
+constexpr F64FormDesc f64_form(int n_min, int n_max, int k_max, int per_lane, const ExactEntry (&tab)[n], int launch_iters,
+                               int resident, const char* kernels, const char* label, const char* noun, const char* taps_over) {
+  return F64FormDesc{n_min, n_max, k_max, per_lane, tab, n, launch_iters, resident, kernels, label, noun, taps_over};
+}
+const F64FormDesc kF64[F64_FORMS] = {
+    // one wave: about 65536 inner iterations per wave slot and launch -- 65536 / nb_sub_iter outer iterations for a batch the
+    // machine holds at once (2048 waves: 256 compute units, four SIMDs, two waves of this kernel each), fewer in proportion
+    // for a larger one, whose launch runs its waves in rounds
+    f64_form(1, 640, 32, 64, kExact, 65536, 2048, "", "one-wave", "form", "exceeds %d taps"),
+    // four waves (641 .. 1 280 scans): the register report of the search allows two waves per SIMD, i.e. two workgroups per
+    // compute unit, 512 resident at once on 256 compute units; an inner iteration of a workgroup takes about twice that of a
+    // wave of the one-wave kernel (3.4 us against 1.5 us alone), so half the budget per slot and launch keeps the longest
+    // dispatch under 0.25 s (measured 0.14 s at most: profiles/auto_lbda_split.txt)
+    f64_form(641, 1280, 32, 64 * pb::SPLIT_WAVES, kExactSplit, 32768, 256 * 2, "_split", "four-wave", "form",
+             "exceeds %d taps"),
+    // one wave, up to 48 taps: the register reports allow the residency of the one-wave search, but a pass carries 48 taps
+    // for 32 (1.5x the multiply-adds, and two lane reads per tap and half): at that kernel's budget its longest dispatch
+    // (0.16 s, profiles/auto_lbda_device.txt) would pass 0.25 s -- half the budget here (measured: profiles/long_hrf.txt)
+    f64_form(1, 640, 48, 64, kExactLong, 32768, 2048, "_long", "%d-tap", "register form", "outside 1..%d taps"),
+    // four waves, up to 48 taps: the residency of the four-wave search (two workgroups per compute unit by its register
+    // reports), and a pass that carries 48 taps for 32 -- that search's budget divided by 1.5, rounded down to a multiple of
+    // 1 024 (32768 / 1.5 = 21845 -> 21504)
+    f64_form(641, 1280, 48, 64 * pb::SPLIT_WAVES, kExactSplitLong, 21504, 256 * 2, "_split_long",
+             "four-wave %d-tap", "register form", "outside 1..%d taps"),
+};
+// the window rule of every form is the reference's default (the searches carry no other: pb::AUTO_WIND)
+constexpr int F64_WIND = 6;
+static_assert(F64_WIND == pb::AUTO_WIND, "one window for the solves and the searches");
+
+// the entry of `form` that carries a call, or nullptr: the form's scans and taps, a known stop rule, the window rule at F64_WIND
+const ExactEntry* pick_f64(int form, int N, int K, int stop_mode, int wind) {
+  const F64FormDesc& d = kF64[form];
+  if (N < d.n_min || N > d.n_max || K < 1 || K > d.k_max) return nullptr;
   if (stop_mode < PB_STOP_NONE || stop_mode > PB_STOP_WINDOW) return nullptr;
-  if (stop_mode == PB_STOP_WINDOW && wind != 6) return nullptr;
-  return pick_cheapest(kExactSplitLong, N, K, 64 * pb::SPLIT_WAVES);
+  if (stop_mode == PB_STOP_WINDOW && wind != F64_WIND) return nullptr;
+  return pick_cheapest(d.tab, d.n_tab, N, K, d.per_lane);
+}
+// The default dispatch of pb_fista_solve_d: one wave per series, else four (`four_waves`: calls with the taps on the host
+// only -- pb_fista_solve_pp_d never falls through to four waves, PB_FLAG_PP_SPLIT names them); another window than F64_WIND
+// has no register form.  The stop_mode is the caller's to validate: pb_fista_which_kernel_d / _pp_d pass an unknown one
+// through and are answered as for a call without a rule.
+const ExactEntry* pick_f64_default(int N, int K, int stop_mode, int wind, bool four_waves, int* form = nullptr) {
+  if (stop_mode == PB_STOP_WINDOW && wind != F64_WIND) return nullptr;
+  for (int f : {F64_ONE_WAVE, F64_FOUR_WAVES}) {
+    const ExactEntry* e = (f == F64_ONE_WAVE || four_waves) ? pick_f64(f, N, K, PB_STOP_NONE, wind) : nullptr;
+    if (e) {
+      if (form) *form = f;
+      return e;
+    }
+  }
+  return nullptr;
 }
 
 template <int S, int KT>

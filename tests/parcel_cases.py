@@ -120,8 +120,8 @@ def input_conditions(case):
 
 
 # ---- the grouped normal equations: host rules restated, parcel layouts -----------------------------------------------
-NE_UNITS, NE_MIN_ROWS = 1024, 16                     # NE_GROUPED_UNITS, NE_GROUPED_MIN_ROWS (csrc/capi.hip:1663)
-NE_LDS_DOUBLES_MAX = 20000                           # LDS_DOUBLES_MAX (csrc/capi.hip:52)
+NE_UNITS, NE_MIN_ROWS = 1024, 16                     # NE_GROUPED_UNITS, NE_GROUPED_MIN_ROWS (csrc/capi.hip)
+NE_LDS_DOUBLES_MAX = 20000                           # LDS_DOUBLES_MAX (csrc/capi.hip)
 
 
 def ne_len(K):
@@ -130,19 +130,19 @@ def ne_len(K):
 
 
 def ne_rows_per_unit(V):
-    """ne_grouped_rows, csrc/capi.hip:1682-1685: about 1 024 workgroups, 16 rows at least each."""
+    """ne_grouped_rows of csrc/capi.hip: about 1 024 workgroups, 16 rows at least each."""
     return max(NE_MIN_ROWS, -(-V // NE_UNITS))
 
 
 def ne_work_len(V, G, K):
-    """ne_grouped_work, csrc/capi.hip:1688-1694 (doubles), with grouped_max_units of csrc/plan.h:339."""
+    """ne_grouped_work of csrc/capi.hip (doubles), with grouped_max_units of csrc/plan.h:339."""
     max_units = V // ne_rows_per_unit(V) + G
     return (G + 2 + 3 * max_units + 1) // 2 + max_units * ne_len(K)
 
 
 def reduce_e_log2(max_units, G, ne):
-    """csrc/capi.hip:1845-1846: entries per workgroup of the second stage from the largest parcel's units, raised until
-    the grid stays within 2^16 workgroups."""
+    """e_log2 in pb_hrf_normal_eq_w_grouped, csrc/capi.hip: entries per workgroup of the second stage from the largest
+    parcel's units, raised until the grid stays within 2^16 workgroups."""
     e = 8 if max_units <= 4 else (6 if max_units <= 16 else (4 if max_units <= 64 else (2 if max_units <= 256 else 0)))
     while e < 8 and G * ((ne + (1 << e) - 1) >> e) > 65536:
         e += 1
@@ -164,7 +164,7 @@ def ne_sum_lds_doubles(N, K):
 
 
 def ne_kernel(N, K):
-    """Which of the three kernels pb_hrf_normal_eq_w_grouped launches (csrc/capi.hip:1810, :1828-1836, ne_wave_form :297-302)."""
+    """Which of the three kernels pb_hrf_normal_eq_w_grouped launches (its `wave_form` and the launch below it in csrc/capi.hip; ne_wave_form)."""
     if K <= 32 and ne_wave_lds_doubles(N, K) <= NE_LDS_DOUBLES_MAX:
         return "register" if K * K <= 64 * 12 and N <= 64 * 5 else "wave"
     return "sum"

@@ -54,7 +54,7 @@ def pick_cheapest(tab, N, K, lane):
 
 def pick(table, N, K):
     """The entry of `table` that carries (N, K), or None.  The four-wave float64 table serves only what the one-wave
-    table does not (pick_exact_split)."""
+    table does not (the scan ranges of kF64 in csrc/dispatch.h)."""
     if N < 1 or K < 1:
         return None
     if table == "exact_split" and pick_cheapest(entries("exact"), N, K, per_lane("exact")):
