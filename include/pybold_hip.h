@@ -784,7 +784,8 @@ int pb_inf_norm(const double* x_dev, int64_t ldx, double* out_dev, int64_t ldo, 
  *                    per_voxel = 1: out_dev [V][len], one set per voxel; work_dev unused.
  * pb_theta_fit       argmin over theta in [lo, hi] of the quadratic form for M sets
  *                    (ne_dev [M][ldne]) with h(theta) the un-normalised two-gamma SPM HRF
- *                    at the K sample times t_dev (parameters as pb_spm_hrf): section search
+ *                    at the K sample times t_dev (parameters as pb_spm_hrf; 1 <= K <= 127, the
+ *                    first scan in four groups of 16 candidates above 111 taps): section search
  *                    -- one scan of 64 candidates over [lo, hi], then, per further level
  *                    of n_refine, two scans of 16 candidates around the best one (bracket
  *                    / 56 per level) -- closed by a parabola vertex (n_refine = 3: about

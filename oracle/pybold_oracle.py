@@ -387,13 +387,16 @@ def spm_hrf(delta, t_r=1.0, dur=60.0, normalized_hrf=True, dt=0.001,
         raise ValueError("delta should belong in [{0}, {1}], got {2}".format(
             MIN_DELTA, MAX_DELTA, delta))
     t = np.linspace(0, dur, int(float(dur) / dt)) - float(onset) / dt
+    dec = int(t_r / dt)
+    if not normalized_hrf:
+        # nothing below looks across samples: evaluate the kept ones only (the same values, bit for bit)
+        t, dec = t[::dec], 1
     ts = delta * t
     peak = gamma.pdf(ts, p_delay / p_disp, loc=dt / p_disp)
     under = gamma.pdf(ts, undershoot / u_disp, loc=dt / u_disp)
     hrf = peak - p_u_ratio * under
     if normalized_hrf:
         hrf = hrf / np.max(hrf + 1.0e-30)
-    dec = int(t_r / dt)
     return hrf[::dec], t[::dec]
 
 
@@ -668,28 +671,37 @@ def gen_regular_bloc_bold(dur=10, tr=1.0, dur_bloc=30.0, hrf=None, snr=1.0, nois
     return clean + noise, clean, ai_s, i_s, noise
 
 
-def theta_fit_normal_eq(G, b, yy, t_r, hrf_dur, bounds, n_refine=3, n_grid=64):
+def theta_fit_normal_eq(G, b, yy, t_r, hrf_dur, bounds, n_refine=3, n_grid=64, schedule="uniform", dt=0.001,
+                        p_delay=6, undershoot=16.0, p_disp=1.0, u_disp=1.0, p_u_ratio=0.167):
     """The device theta-step restated on the CPU: minimise the quadratic form
     ``0.5 yy - h^T b + 0.5 h^T G h`` (= :func:`shared_hrf_cost` written with the normal
-    equations of :func:`hrf_normal_eq`) over ``bounds`` by section search -- ``n_grid``
-    equispaced candidates, bracket = the two cells around the best one -- closed by the
-    vertex of the parabola through the best candidate and its neighbours.
-    Returns ``(theta, F(theta), h(theta))``."""
+    equations of :func:`hrf_normal_eq`) over ``bounds`` by section search -- equispaced
+    candidates, bracket = the two cells around the best one (the first minimum wins a tie) --
+    closed by the vertex of the parabola through the best candidate and its neighbours.
+    ``schedule="uniform"``: ``n_refine`` scans of ``n_grid`` candidates.  ``schedule="kernel"``:
+    the scans of ``theta_fit_kernel`` (csrc/blind.h) -- one of 64 candidates, then
+    ``2 (n_refine - 1)`` of 16 -- with the parabola on the last scan only.  The model keywords
+    are those of :func:`spm_hrf`.  Returns ``(theta, F(theta), h(theta))``."""
+    if schedule not in ("uniform", "kernel"):
+        raise ValueError("schedule must be 'uniform' or 'kernel', got %r" % (schedule,))
+    model = dict(dt=dt, p_delay=p_delay, undershoot=undershoot, p_disp=p_disp, u_disp=u_disp, p_u_ratio=p_u_ratio)
+
     def price(th):
-        h = spm_hrf(th, t_r, hrf_dur, False)[0]
+        h = spm_hrf(th, t_r, hrf_dur, False, **model)[0]
         return 0.5 * yy - h.dot(b) + 0.5 * h.dot(G.dot(h))
+    grids = [n_grid] * n_refine if schedule == "uniform" else [64] + [16] * (2 * (n_refine - 1))
     a, c = bounds
     best = a
-    for r in range(n_refine):
-        grid = a + (c - a) * (np.arange(n_grid) / float(n_grid - 1))
+    for r, ng in enumerate(grids):
+        grid = a + (c - a) * (np.arange(ng) / float(ng - 1))
         f = np.array([price(t) for t in grid])
         m = int(np.argmin(f))
-        il, ir = max(m - 1, 0), min(m + 1, n_grid - 1)
+        il, ir = max(m - 1, 0), min(m + 1, ng - 1)
         best = grid[m]
-        if r == n_refine - 1 and 0 < m < n_grid - 1:
+        if r == len(grids) - 1 and 0 < m < ng - 1:
             den = f[il] - 2.0 * f[m] + f[ir]
             if den > 0.0:
                 tv = grid[m] + 0.5 * (grid[m] - grid[il]) * (f[il] - f[ir]) / den
                 best = min(max(tv, grid[il]), grid[ir])
         a, c = grid[il], grid[ir]
-    return best, price(best), spm_hrf(best, t_r, hrf_dur, False)[0]
+    return best, price(best), spm_hrf(best, t_r, hrf_dur, False, **model)[0]

@@ -703,7 +703,13 @@ __device__ __forceinline__ double spm_hrf_value(const HrfModel& hm, double x) {
 // candidate and its neighbours.  Every wave reduces the same 64 values in the same order, so
 // the four agree on the bracket without exchanging it.
 // LDS: set [ne], h [K][64] (lane-major columns, conflict-free), part [4][64].
+// K > 111: 64 columns of taps no longer fit beside the set, and the first scan prices its 64 candidates in four
+// groups of 16 with the deal of the refinement scans -- h [K][16], part [16], f [64] -- K <= 127 in 18 546 doubles.
 // theta[s], cost[s] = F(theta*), taps[s][K] = h(theta*).
+constexpr int THETA_LDS_DOUBLES_MAX = 20000;   // 160 KB per workgroup (LDS_DOUBLES_MAX of capi.hip)
+__host__ __device__ inline bool theta_fit_wide(int K) { return ne_len(K) + 1 + 64 * K + 256 <= THETA_LDS_DOUBLES_MAX; }
+__host__ __device__ inline int theta_fit_lds_doubles(int K) { return ne_len(K) + 1 + (theta_fit_wide(K) ? 64 : 16) * K + 256; }
+
 __global__ __launch_bounds__(256) void theta_fit_kernel(const double* ne_sets, int64_t ldne, int M,
                                                         int K, const double* t, HrfModel hm,
                                                         double lo, double hi, int n_refine,
@@ -717,8 +723,9 @@ __global__ __launch_bounds__(256) void theta_fit_kernel(const double* ne_sets, i
   const int ne = ne_len(K);
   double* G = reinterpret_cast<double*>(smem);
   double* b = G + K * K;
+  const bool wide = theta_fit_wide(K);
   double* hl = G + ne + lane;                 // h[k] of candidate `lane` at hl[k * 64]
-  double* part = G + ne + 64 * K;             // [4][64]
+  double* part = G + ne + (wide ? 64 : 16) * K;   // [4][64]
   const double* src = ne_sets + (int64_t)s * ldne;
   for (int e = threadIdx.x; e < ne; e += 256) G[e] = src[e];
   __syncthreads();
@@ -742,7 +749,45 @@ __global__ __launch_bounds__(256) void theta_fit_kernel(const double* ne_sets, i
   };
 
   double a = lo, c = hi, best_t = lo;
-  {
+  if (!wide) {
+    // first scan, K > 111: the same 64 candidates, 16 at a time (thread = candidate x one of 16 shares, as below)
+    const int cand = threadIdx.x >> 4, sh = threadIdx.x & 15;
+    double* h16 = G + ne;                        // [K][16]
+    double* f64 = part + 16;                     // [64]
+    for (int g = 0; g < 4; ++g) {
+      const double th = a + (c - a) * ((double)(g * 16 + cand) / 63.0);
+      for (int k = sh; k < K; k += 16) h16[k * 16 + cand] = spm_hrf_value(hm, th * t[k]);
+      __syncthreads();
+      double v = 0.0;
+      for (int m = sh; m < K; m += 16) {
+        double row = 0.0;
+        for (int mp = 0; mp < K; ++mp) row = fma(G[m * K + mp], h16[mp * 16 + cand], row);
+        v = fma(h16[m * 16 + cand], 0.5 * row - b[m], v);
+      }
+#pragma unroll
+      for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+      if (sh == 0) f64[g * 16 + cand] = 0.5 * yy + v;
+      __syncthreads();                           // (h16 is rewritten by the next group)
+    }
+    int im = 0;
+    double fm = f64[0];
+    for (int q = 1; q < 64; ++q) {               // first minimum wins
+      const double fq = f64[q];
+      if (fq < fm) { fm = fq; im = q; }
+    }
+    const int il = im > 0 ? im - 1 : 0, ir = im < 63 ? im + 1 : 63;
+    const double tl = a + (c - a) * ((double)il / 63.0), tm = a + (c - a) * ((double)im / 63.0);
+    const double tr = a + (c - a) * ((double)ir / 63.0);
+    const double fl = f64[il], fr = f64[ir];
+    __syncthreads();                             // f64 read by all before part is rewritten
+    best_t = tm;
+    if (n_refine == 1 && im > 0 && im < 63) {
+      const double den = fl - 2.0 * fm + fr;
+      if (den > 0.0) best_t = fmin(fmax(tm + 0.5 * (tm - tl) * (fl - fr) / den, tl), tr);
+    }
+    a = tl;
+    c = tr;
+  } else {
     // first scan: 64 candidates over the whole interval (lane = candidate)
     const double th = a + (c - a) * ((double)lane / 63.0);
     const double f = price(th);

@@ -1312,6 +1312,13 @@ int pb_hrf_normal_eq_d(const double* z_dev, int64_t ldz, const double* y_dev, in
                                 out_dev, stream, "pb_hrf_normal_eq_d");
 }
 
+// (more than 64 KB of dynamic LDS -- K >= 63 -- has to be asked for, per kernel and device, as in launch_mfma4)
+static void theta_fit_lds(int64_t nd) {
+  if (nd * (int64_t)sizeof(double) > 65536)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pb::theta_fit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(nd * sizeof(double)));
+}
+
 int pb_theta_fit(const double* ne_dev, int64_t ldne, int M, int K, const double* t_dev,
                  double a_peak, double loc_peak, double a_under, double loc_under, double ratio,
                  double lo, double hi, int n_refine, double* theta_dev, double* cost_dev,
@@ -1319,12 +1326,13 @@ int pb_theta_fit(const double* ne_dev, int64_t ldne, int M, int K, const double*
   if (M < 0 || K < 1 || K > 127 || n_refine < 1 || !(a_peak > 0.0) || !(a_under > 0.0) ||
       !(lo <= hi) || (M > 1 && ldne < pb::ne_len(K)) || (taps_dev && M > 1 && ldt < K))
     return fail(PB_ERR_INVALID, "pb_theta_fit: bad argument");
-  const int64_t nd = (int64_t)pb::ne_len(K) + 64 * (int64_t)K + 256;
+  const int64_t nd = pb::theta_fit_lds_doubles(K);      // (K > 111: the first scan in groups of 16 candidates)
   if (nd > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "pb_theta_fit: K=%d exceeds LDS", K);
   if (M == 0) return PB_OK;
   if (!ne_dev || !t_dev || !theta_dev || !cost_dev)
     return fail(PB_ERR_INVALID, "pb_theta_fit: NULL pointer");
   const pb::HrfModel hm = hrf_model(a_peak, loc_peak, a_under, loc_under, ratio);
+  theta_fit_lds(nd);
   hipLaunchKernelGGL(pb::theta_fit_kernel, dim3(M), dim3(256), (size_t)nd * sizeof(double),
                      (hipStream_t)stream, ne_dev, ldne, M, K, t_dev, hm, lo, hi, n_refine, theta_dev,
                      cost_dev, taps_dev, ldt, 0, (double*)nullptr, 0.0, (double*)nullptr);
@@ -1338,11 +1346,12 @@ int pb_theta_fit_step(const double* msg_dev, int K, const double* t_dev, double 
                       void* stream) {
   if (K < 1 || K > 127 || N < K || n_refine < 1 || !(a_peak > 0.0) || !(a_under > 0.0) || !(lo <= hi))
     return fail(PB_ERR_INVALID, "pb_theta_fit_step: bad argument");
-  const int64_t nd = (int64_t)pb::ne_len(K) + 1 + 64 * (int64_t)K + 256;
+  const int64_t nd = pb::theta_fit_lds_doubles(K);      // (K > 111: the first scan in groups of 16 candidates)
   if (nd > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "pb_theta_fit_step: K=%d exceeds LDS", K);
   if (!msg_dev || !t_dev || !theta_dev || !cost_dev || !taps_dev || !step_dev || !jcost_dev)
     return fail(PB_ERR_INVALID, "pb_theta_fit_step: NULL pointer");
   const pb::HrfModel hm = hrf_model(a_peak, loc_peak, a_under, loc_under, ratio);
+  theta_fit_lds(nd);
   hipLaunchKernelGGL(pb::theta_fit_kernel, dim3(1), dim3(256), (size_t)nd * sizeof(double),
                      (hipStream_t)stream, msg_dev, (int64_t)pb::ne_len(K) + 1, 1, K, t_dev, hm, lo, hi,
                      n_refine, theta_dev, cost_dev, taps_dev, (int64_t)K, N, step_dev, lbda, jcost_dev);

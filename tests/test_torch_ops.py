@@ -43,6 +43,14 @@ def test_torch_ops_equal_the_ctypes_path(golden):
     th2, f2, tp2 = ops.theta_fit(ne.reshape(1, -1), solver._sample_times_on(ne.device, t_r, dur), 6.0, 0.001, 16.0, 0.001,
                                  0.167, 0.6, 1.9, 3)
     assert torch.equal(th, th2) and torch.equal(f, f2) and torch.equal(tp, tp2)
+    tp_default = tp
+    # a model without integer powers (both densities on the exp/log path): the same shapes and locations, the same bits
+    nonint = dict(p_delay=5.5, p_disp=1.0, undershoot=14.5, u_disp=1.0, p_u_ratio=0.25)
+    th, f, tp = solver.theta_fit(ne, t_r, dur, (0.6, 1.9), **nonint)
+    th2, f2, tp2 = ops.theta_fit(ne.reshape(1, -1), solver._sample_times_on(ne.device, t_r, dur), 5.5 / 1.0, 0.001 / 1.0,
+                                 14.5 / 1.0, 0.001 / 1.0, 0.25, 0.6, 1.9, 3)
+    assert torch.equal(th, th2) and torch.equal(f, f2) and torch.equal(tp, tp2)
+    assert not torch.equal(tp, tp_default) and bool(torch.isfinite(tp).all())
     # errors surface as RuntimeError with the library's message
     with pytest.raises(RuntimeError, match="pb_fista_solve"):
         torch_ops.fista_solve(Y[:4], hrf, 1.0, -1.0, 5)
