@@ -85,6 +85,9 @@ extern "C" {
  * tiles (fista_mfma_kernel, 12 matrix instructions per block and pass) instead of the 2:4-sparse joined tile
  * (fista_mfma_sparse_kernel, 6).  For A/B runs and as a fallback. */
 enum { PB_FLAG_MFMA_DENSE_TILES = 4194304 };
+/* And bit 23, an enumerator as well: pb_fista_solve_grouped only: series of 311 .. 1 280 scans with up to 48 taps may run on the
+ * split matrix-pipe forms, one unit of 16 rows per workgroup (OPT-IN; see pb_fista_solve_grouped and pb_fista_grouped_route). */
+enum { PB_FLAG_GROUPED_SPLIT = 8388608 };
 #define PB_FLAG_ONE_LAUNCH 32u    /* never split a plain solve into a full-rounds launch and a
                                      remainder launch (see pb_fista_solve) */
 
@@ -188,6 +191,7 @@ int pb_fista_plan_ex(int N, int K, int P, int stop_mode, int wind, unsigned flag
  *   129 .. 310   <= 33     (b)                  (b) certificate          (b) in full           fista_mfma_kernel, one wave per 16 problems
  *   129 .. 310   34 .. 48  (b)                  (b) from 225 scans on    (b) from 225 scans on ... with three near tiles (stop rules: split form)
  *   129 .. 310   <= 33     (b) one HRF per parcel, rows contiguous by parcel (pb_fista_solve_grouped, plain only):   the same kernels, a wave's 16 problems of one parcel; other shapes: (a), per problem
+ *   311 .. 1280  <= 48     (b) one HRF per parcel, OPT-IN with PB_FLAG_GROUPED_SPLIT (pb_fista_solve_grouped, plain only):           fista_mfma2_kernel (up to 640 scans) / fista_mfma4_kernel, a workgroup's 16 problems of one parcel; without the flag: (a), per problem
  *   311 .. 640   <= 33     (b)                  (b) certificate          (b) in full           fista_mfma2_kernel, two waves per 16 problems
  *   311 .. 640   34 .. 48  (b)                  (b) certificate          (b) in full           ... with three near tiles
  *   641 .. 1280  <= 33     (b)                  (b) certificate          (b) in full           fista_mfma4_kernel, four waves per 16 problems
@@ -859,6 +863,26 @@ int pb_theta_fit_step(const double* msg_dev, int K, const double* t_dev,
  *                     number of rows, PB_ERR_INVALID for a shape it does not serve;
  *                     PB_FLAG_NO_RHO_GUARD, _CERT_NO_RESOLVE, _COLD_START, _ONE_LAUNCH as for
  *                     pb_fista_solve_pp (the grouped matrix-pipe solve is one launch as it is).
+ *                     OPT-IN, with PB_FLAG_GROUPED_SPLIT only: series of 311 .. 1 280 scans with up to 48 taps
+ *                     (n_done_dev given) may run on the split matrix-pipe forms of the shared-HRF z-step --
+ *                     fista_mfma2_kernel up to 640 scans, fista_mfma4_kernel beyond; GROUPED instantiations,
+ *                     three near tiles from 34 taps on --, one unit of 16 rows of the same table per WORKGROUP.
+ *                     Whole passes (wave slots / 4 units on two waves, / 8 on four: 512 / 256 on 256 compute
+ *                     units) run there, a remainder above 5/16 (two waves) or 10/16 (four) of a pass too, a
+ *                     smaller one on the vector forms behind the passes; two-wave calls of fewer than
+ *                     5 120 slot rows (16 x units; 2 048 for 34+ taps) stay on the vector route.  These are
+ *                     the thresholds of the shared-HRF route, applied to 16 x units; they were measured for
+ *                     that route.  PB_FLAG_FORCE_MFMA with the flag: every unit in one launch, PB_ERR_INVALID
+ *                     outside 311 .. 1 280 scans / 48 taps (129 .. 310 scans decide as without the flag).
+ *                     Without the flag nothing changes: such shapes run on the vector route, and forcing the
+ *                     matrix pipe there is an error.
+ * pb_fista_grouped_route   host-only, launches nothing: the decision pb_fista_solve_grouped takes for these offsets,
+ *                     (N, K) and flags, n_done_dev given.  Returns the main launch in the numbering of
+ *                     pb_fista_which_kernel -- 4 one wave per unit, 5 two waves, 6 four waves, 0 every row on the
+ *                     vector route, -1 the call would fail (the flags force a form the shape lacks; bad offsets or
+ *                     sizes; P = 0) --, *main_units = the units of the table in that launch, *row_cut = the
+ *                     first row behind them (P: none; those rows run on the vector forms).  Code 0 or -1: both 0.
+ *                     Either pointer may be NULL.
  * pb_fista_grouped_plan    host-only: the unit table of a grouped solve for offsets in host memory --
  *                     table_out [3 * units] = (first row, rows <= per, parcel) per unit, first_out [G + 1]
  *                     = first unit of every parcel (either may be NULL); per = 16 is the wave table.
@@ -874,6 +898,7 @@ int pb_theta_fit_step(const double* msg_dev, int K, const double* t_dev,
 int64_t pb_fista_grouped_work_len(int P, int G, int K);
 int pb_fista_grouped_waves(const int32_t* offsets_host, int G, int P);
 int pb_fista_grouped_plan(const int32_t* offsets_host, int G, int P, int per, int32_t* table_out, int32_t* first_out);
+int pb_fista_grouped_route(const int32_t* offsets_host, int G, int P, int N, int K, unsigned flags, int* main_units, int* row_cut);
 int pb_fista_solve_grouped(const float* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int P, int N,
                            const double* taps_dev, int64_t ldt, int K, const double* step_dev, int G,
                            const int32_t* offsets_host, const int32_t* offsets_dev, double lbda,

@@ -34,6 +34,7 @@ PB_FLAG_NO_ILL_GUARD = 524288
 PB_FLAG_PP_SPLIT = 1048576           # pb_fista_solve_pp_d only: the four-wave per-problem-tap form or an error
 PB_FLAG_MFMA_DENSE_TILES = 4194304   # one-wave matrix-pipe form: the dense near tiles instead of the 2:4-sparse joined tile
 PB_FLAG_LONG_HRF = 2097152     # pb_fista_solve_d / pb_fista_solve_pp_d: the 48-tap one-wave register form (opt-in), or an error
+PB_FLAG_GROUPED_SPLIT = 8388608      # pb_fista_solve_grouped only: 311 .. 1 280 scans, up to 48 taps on the split matrix-pipe forms (opt-in)
 PB_PATH_DENSE_RATIO = 0.19         # include/pybold_hip.h (series of up to 310 scans; 0.22 beyond)
 PB_STOP_NONE = 0
 PB_STOP_LOOPS = 1
@@ -211,6 +212,7 @@ SIGNATURES = {
     "pb_fista_grouped_work_len": (_c_i64, [_c_int, _c_int, _c_int]),
     "pb_fista_grouped_waves": (_c_int, [_ptr, _c_int, _c_int]),
     "pb_fista_grouped_plan": (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr, _ptr]),
+    "pb_fista_grouped_route": (_c_int, [_ptr, _c_int, _c_int, _c_int, _c_int, ctypes.c_uint, _ptr, _ptr]),   # offsets_host, G, P, N, K, flags, main_units, row_cut
     "pb_fista_solve_grouped": (_c_int, [
         _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int,     # y, ldy, w, ldw, P, N
         _ptr, _c_i64, _c_int, _ptr, _c_int,             # taps_dev, ldt, K, step_dev, G

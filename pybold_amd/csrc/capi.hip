@@ -27,6 +27,7 @@
 #include "grouped.h"
 #include "fista_mfma2.h"
 #include "fista_mfma4.h"
+#include "fista_mfma_split_grouped.h"
 #include "path.h"
 #include "dispatch.h"
 
@@ -1426,11 +1427,6 @@ int pb_fista_solve_pp(const float* y_dev, int64_t ldy, double* w_dev, int64_t ld
 // ---- one HRF per parcel (rows contiguous by parcel; plan.h: the unit table, grouped.h: its device side) ----
 }  // extern "C"
 namespace {
-// Below this many rows a grouped call stays on the per-problem vector route: a matrix-pipe pass costs the same whatever
-// it carries (one wave per SIMD: 1.74 ms per 500 iterations at 300 scans), one problem per wave finishes up to 2 048 rows
-// in 0.37 ms, and the per-problem route runs at 0.45 .. 0.6e9 row-iterations/s beyond: the pass wins from
-// ~4 000 rows on.  (From those figures; not measured for grouped calls.)
-constexpr int GROUPED_MFMA_MIN_P = 4096;
 constexpr int NE_GROUPED_UNITS = 1024, NE_GROUPED_MIN_ROWS = 16;     // normal equations: ~1 024 workgroups, 16 rows at least each
 
 struct GroupedWork { int64_t taps, steps, first, table, total; };    // offsets in int32 words (the float64 parts first)
@@ -1477,6 +1473,15 @@ int pb_fista_grouped_waves(const int32_t* offsets_host, int G, int P) {
   return pb_fista_grouped_plan(offsets_host, G, P, pb::GROUPED_WAVE_ROWS, nullptr, nullptr);
 }
 
+int pb_fista_grouped_route(const int32_t* offsets_host, int G, int P, int N, int K, unsigned flags, int* main_units, int* row_cut) {
+  GroupedRoute r{-1, 0, 0, nullptr};
+  if (P > 0 && P <= (1 << 25) && N >= 1 && K >= 1 && G >= 0 && pb::grouped_offsets_ok(offsets_host, G, P))
+    r = route_grouped(offsets_host, G, P, N, K, flags, true);
+  if (main_units) *main_units = r.main_units;
+  if (row_cut) *row_cut = r.row_cut;
+  return r.code;
+}
+
 int pb_fista_solve_grouped(const float* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int P, int N,
                            const double* taps_dev, int64_t ldt, int K, const double* step_dev, int G,
                            const int32_t* offsets_host, const int32_t* offsets_dev, double lbda,
@@ -1495,11 +1500,16 @@ int pb_fista_solve_grouped(const float* y_dev, int64_t ldy, double* w_dev, int64
   if (work_len < wl.total || (reinterpret_cast<uintptr_t>(work_dev) & 7) != 0)
     return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: work buffer must hold %lld int32 words (pb_fista_grouped_work_len), 8-byte aligned",
                 (long long)wl.total);
-  const grouped_launch_fn mf = (n_done_dev && !(flags & FLAGS_VECTOR_ONLY)) ? pick_mfma_grouped(N, K) : nullptr;
-  const bool forced = (flags & PB_FLAG_FORCE_MFMA) != 0;
-  if (forced && !mf)
+  // the decision (dispatch.h: route_grouped -- what pb_fista_grouped_route reports)
+  const GroupedRoute gr = route_grouped(offsets_host, G, P, N, K, flags, n_done_dev != nullptr);
+  if (gr.code < 0) {
+    if ((flags & PB_FLAG_GROUPED_SPLIT) && N > MFMA1_NMAX)
+      return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: no matrix-pipe form for N=%d K=%d (with PB_FLAG_GROUPED_SPLIT: 311 .. 1 280 scans, K <= %d, n_done_dev given)",
+                  N, K, GROUPED_SPLIT_KMAX);
     return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: no matrix-pipe form for N=%d K=%d (129 .. 310 scans, K <= 33, n_done_dev given)", N, K);
-  const bool use_mfma = mf && (forced || P >= GROUPED_MFMA_MIN_P);
+  }
+  const grouped_launch_fn mf = gr.fn;
+  const bool use_mfma = gr.code > 0;
   const bool resolve = !(flags & PB_FLAG_CERT_NO_RESOLVE);
   const hipStream_t user = (hipStream_t)stream;
   int32_t* first = work_dev + wl.first;
@@ -1509,37 +1519,23 @@ int pb_fista_solve_grouped(const float* y_dev, int64_t ldy, double* w_dev, int64
   double* step_rows = reinterpret_cast<double*>(work_dev + wl.steps);
   const int units = pb::grouped_table(offsets_host, G, P, pb::GROUPED_WAVE_ROWS, nullptr, nullptr);     // (P > 0: at least one)
   launch_grouped_table(offsets_dev, G, P, pb::GROUPED_WAVE_ROWS, (int)pb::grouped_max_units(P, G, pb::GROUPED_WAVE_ROWS), first, table, user);
-  // Whole rounds of waves (one per SIMD) go to the matrix pipe; a last partial round costs a whole pass there whatever it
-  // carries, so up to GROUPED_MFMA_MIN_P rows of it go to the vector forms instead, behind the rounds (the split of
-  // plan_pieces_mfma; not under PB_FLAG_ONE_LAUNCH / _FORCE_MFMA).  `row_cut`: the first row of the first wave left out.
-  int main_units = units, row_cut = P;
-  if (use_mfma && !forced && !(flags & PB_FLAG_ONE_LAUNCH)) {
-    const int round = (int)wave_slots() / 2;
-    const int whole = units / round * round;
-    if (whole > 0 && whole < units) {
-      int u = 0, cut = P;
-      for (int g = 0; g < G; ++g) {
-        const int n = (offsets_host[g + 1] - offsets_host[g] + pb::GROUPED_WAVE_ROWS - 1) / pb::GROUPED_WAVE_ROWS;
-        if (u + n > whole) { cut = offsets_host[g] + (whole - u) * pb::GROUPED_WAVE_ROWS; break; }
-        u += n;
-      }
-      if (P - cut <= GROUPED_MFMA_MIN_P) { main_units = whole; row_cut = cut; }
-    }
-  }
+  // `main_units` units of the table run on the matrix pipe (whole rounds or passes and, where it pays, the rest), the rows
+  // from `row_cut` on -- the first row of the first unit left out -- on the vector forms behind them
+  const int main_units = use_mfma ? gr.main_units : units, row_cut = use_mfma ? gr.row_cut : P;
   if (!use_mfma || resolve || row_cut < P)
     hipLaunchKernelGGL(pb::grouped_expand_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, user, table, n_units_dev, taps_dev,
                        ldt, K, step_dev, taps_rows, step_rows);
   int rc = check_launch("pb_fista_solve_grouped: unit table");
   if (rc != PB_OK) return rc;
-  const unsigned vector_flags = flags & ~(PB_FLAG_FORCE_MFMA | PB_FLAG_NO_MFMA);
+  const unsigned vector_flags = flags & ~(PB_FLAG_FORCE_MFMA | PB_FLAG_NO_MFMA | PB_FLAG_GROUPED_SPLIT);
   if (!use_mfma)
     return pb_fista_solve_pp(y_dev, ldy, w_dev, ldw, P, N, taps_rows, K, K, step_rows, lbda, lbda_dev, betas_dev, n_iter, PB_STOP_NONE,
                              0.0, n_done_dev, vector_flags, stream);
   pb::FistaArgs a = fista_args(P, N, K, n_iter, 1, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, PB_STOP_NONE, 0.0, n_done_dev, flags);
   a.y = y_dev; a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = 0;
-  a.perm = table; a.n_dense = n_units_dev; a.grid_slots = main_units;     // (whole rounds: a multiple of the four waves of a workgroup)
+  a.perm = table; a.n_dense = n_units_dev; a.grid_slots = main_units;     // (one wave per unit: whole rounds are a multiple of the four waves of a workgroup; the split forms: one workgroup per unit)
   if (mf(a, K, user) != 0) return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: the matrix-pipe kernel rejected its launch");
-  rc = check_launch("fista_mfma_kernel(grouped)");
+  rc = check_launch(gr.code == 4 ? "fista_mfma_kernel(grouped)" : gr.code == 5 ? "fista_mfma2_kernel(grouped)" : "fista_mfma4_kernel(grouped)");
   if (rc != PB_OK) return rc;
   // the per-problem vector forms, every row with its parcel's taps: the rows behind the whole rounds, then what the
   // guards handed back (n_done = -1)

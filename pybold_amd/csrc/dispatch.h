@@ -79,6 +79,14 @@ PB_MFMA2(6, 7) PB_MFMA2(7, 7) PB_MFMA2(7, 8) PB_MFMA2(8, 8) PB_MFMA2(8, 9) PB_MF
 #define PB_MFMA4(A) extern template int launch_mfma4<A>(const FistaArgs&, const double*, int, bool, hipStream_t);
 PB_MFMA4(6) PB_MFMA4(7) PB_MFMA4(8) PB_MFMA4(9) PB_MFMA4(10)
 #undef PB_MFMA4
+// (fista_mfma_split_grouped.h: the two split kernels with one HRF per parcel, pb_fista_solve_grouped with PB_FLAG_GROUPED_SPLIT)
+#define PB_MFMA2(A, B) extern template int launch_mfma2_grouped<A, B>(const FistaArgs&, int, hipStream_t);
+PB_MFMA2(5, 5) PB_MFMA2(5, 6) PB_MFMA2(6, 6) PB_MFMA2(6, 7) PB_MFMA2(7, 7) PB_MFMA2(7, 8) PB_MFMA2(8, 8) PB_MFMA2(8, 9) PB_MFMA2(9, 9)
+PB_MFMA2(9, 10) PB_MFMA2(10, 10)
+#undef PB_MFMA2
+#define PB_MFMA4(A) extern template int launch_mfma4_grouped<A>(const FistaArgs&, int, hipStream_t);
+PB_MFMA4(6) PB_MFMA4(7) PB_MFMA4(8) PB_MFMA4(9) PB_MFMA4(10)
+#undef PB_MFMA4
 }
 namespace {
 // the matrix-pipe form with one series split over the two waves of a workgroup (fista_mfma2.h): nb = ceil(N / 32)
@@ -467,6 +475,97 @@ constexpr unsigned FLAGS_NO_SPLIT_PAIR = PB_FLAG_FORCE_GENERIC | PB_FLAG_NO_PAIR
 constexpr unsigned FLAGS_NO_PARTITION = PB_FLAG_FORCE_GENERIC | PB_FLAG_FORCE_PAIR | PB_FLAG_FORCE_WIDE | PB_FLAG_NO_PAIR |
                                         PB_FLAG_DIRECT_FIR | PB_FLAG_NO_MFMA | PB_FLAG_ONE_LAUNCH | PB_FLAG_FORCE_MFMA2 |
                                         PB_FLAG_CERT_NO_RESOLVE | PB_FLAG_NO_PARTITION;
+
+// ---- the route of pb_fista_solve_grouped (one HRF per parcel): the entry point runs it, pb_fista_grouped_route reports it ------
+// Below this many rows a grouped call of 129 .. 310 scans stays on the per-problem vector route: a matrix-pipe pass costs the
+// same whatever it carries (one wave per SIMD: 1.74 ms per 500 iterations at 300 scans), one problem per wave finishes up to
+// 2 048 rows in 0.37 ms, and the per-problem route runs at 0.45 .. 0.6e9 row-iterations/s beyond: the pass wins
+// from ~4 000 rows on.  (From those figures; not measured for grouped calls.)
+constexpr int GROUPED_MFMA_MIN_P = 4096;
+// the split forms of the grouped z-step (PB_FLAG_GROUPED_SPLIT): 311 .. 640 scans on two waves per unit, 641 .. 1 280 on four;
+// up to 48 taps, where the table of the one-problem-per-wave form ends -- the rows behind the passes and the re-solve of
+// handed-back rows need a vector form with per-row taps
+constexpr int GROUPED_SPLIT_KMAX = 48;
+grouped_launch_fn pick_mfma2_grouped(int N, int K) {
+  static const grouped_launch_fn tab[] = {
+      &pb::launch_mfma2_grouped<5, 5>, &pb::launch_mfma2_grouped<5, 6>, &pb::launch_mfma2_grouped<6, 6>, &pb::launch_mfma2_grouped<6, 7>,
+      &pb::launch_mfma2_grouped<7, 7>, &pb::launch_mfma2_grouped<7, 8>, &pb::launch_mfma2_grouped<8, 8>, &pb::launch_mfma2_grouped<8, 9>,
+      &pb::launch_mfma2_grouped<9, 9>, &pb::launch_mfma2_grouped<9, 10>, &pb::launch_mfma2_grouped<10, 10>};
+  if (N <= MFMA1_NMAX || N > 640 || K < 1 || K > GROUPED_SPLIT_KMAX || !pick_wide(N, K)) return nullptr;
+  return tab[(N + 31) / 32 - 10];
+}
+grouped_launch_fn pick_mfma4_grouped(int N, int K) {
+  static const grouped_launch_fn tab[] = {&pb::launch_mfma4_grouped<6>, &pb::launch_mfma4_grouped<7>, &pb::launch_mfma4_grouped<8>,
+                                          &pb::launch_mfma4_grouped<9>, &pb::launch_mfma4_grouped<10>};
+  if (N <= 640 || N > 1280 || K < 1 || K > GROUPED_SPLIT_KMAX || !pick_wide(N, K)) return nullptr;
+  return tab[(N + 127) / 128 - 6];
+}
+
+// `code`: the main launch in the numbering of pb_fista_which_kernel -- 4 one wave per unit of 16 rows, 5 two waves, 6 four
+// waves, 0 every row on the per-problem vector route, -1 the flags force a form the shape lacks; `main_units`: the units of
+// the table in that launch (from the first on); `row_cut`: the first row behind them (P: none) -- those rows run on the
+// vector forms.  code 0: main_units = 0, row_cut = 0.
+struct GroupedRoute {
+  int code, main_units, row_cut;
+  grouped_launch_fn fn;
+};
+// first row of unit `whole` of the table (units of GROUPED_WAVE_ROWS rows that never cross a parcel)
+int grouped_row_of_unit(const int32_t* offsets_host, int G, int P, int whole) {
+  int u = 0;
+  for (int g = 0; g < G; ++g) {
+    const int n = (offsets_host[g + 1] - offsets_host[g] + pb::GROUPED_WAVE_ROWS - 1) / pb::GROUPED_WAVE_ROWS;
+    if (u + n > whole) return offsets_host[g] + (whole - u) * pb::GROUPED_WAVE_ROWS;
+    u += n;
+  }
+  return P;
+}
+// (offsets checked by the caller, P > 0; `n_done`: n_done_dev given -- the matrix-pipe forms hand rows back through it)
+GroupedRoute route_grouped(const int32_t* offsets_host, int G, int P, int N, int K, unsigned fl, bool n_done) {
+  GroupedRoute r{0, 0, 0, nullptr};
+  const bool forced = (fl & PB_FLAG_FORCE_MFMA) != 0, one_launch = forced || (fl & PB_FLAG_ONE_LAUNCH) != 0;
+  const bool pipe = n_done && !(fl & FLAGS_VECTOR_ONLY);
+  const bool split = (fl & PB_FLAG_GROUPED_SPLIT) != 0 && N > MFMA1_NMAX;      // (up to 310 scans the flag changes nothing)
+  const bool four = N > 640;
+  r.fn = !pipe ? nullptr : !split ? pick_mfma_grouped(N, K) : four ? pick_mfma4_grouped(N, K) : pick_mfma2_grouped(N, K);
+  if (!r.fn) {
+    r.code = forced ? -1 : 0;
+    return r;
+  }
+  const int units = pb::grouped_table(offsets_host, G, P, pb::GROUPED_WAVE_ROWS, nullptr, nullptr);
+  int main_units = units;
+  if (!split) {
+    // Whole rounds of waves (one per SIMD) go to the matrix pipe; a last partial round costs a whole pass there whatever it
+    // carries, so up to GROUPED_MFMA_MIN_P rows of it go to the vector forms instead, behind the rounds (the split of
+    // plan_pieces_mfma; not under PB_FLAG_ONE_LAUNCH / _FORCE_MFMA)
+    if (!forced && P < GROUPED_MFMA_MIN_P) main_units = 0;
+    else if (!one_launch) {
+      const int round = (int)wave_slots() / 2;
+      const int whole = units / round * round;
+      if (whole > 0 && whole < units && P - grouped_row_of_unit(offsets_host, G, P, whole) <= GROUPED_MFMA_MIN_P) main_units = whole;
+    }
+  } else if (!forced) {
+    // The thresholds of the shared-HRF route (route_pp: mfma2_long_min_p, mfma2_long_base, mfma4_base) applied to 16 x units,
+    // because a unit costs a workgroup whatever it carries: whole passes on the matrix pipe, a remainder above 5/16 (two waves)
+    // or 10/16 (four waves) of a pass too, a smaller one behind the passes on the vector forms.  MEASURED FOR THE SHARED-HRF
+    // FORMS, not for grouped calls (profiles/r4_split_form_passes.txt, r5_long_series_*.txt; profiles/parcels_split.txt says
+    // what is known about grouped ones).  A two-wave call that meets the minimum but fills no whole pass is one partial pass:
+    // there the minimum decides, not the remainder rule (34+ taps, 2 048 .. 2 560 rows).
+    const int slot_rows = 16 * units;
+    if (!four && slot_rows < mfma2_long_min_p(K)) main_units = 0;
+    else {
+      const int base = (four ? mfma4_base(slot_rows, one_launch) : mfma2_long_base(slot_rows, one_launch)) / 16;
+      main_units = (!four && base == 0) ? units : base;
+    }
+  }
+  if (main_units == 0) {
+    r.fn = nullptr;
+    return r;
+  }
+  r.code = !split ? 4 : four ? 6 : 5;
+  r.main_units = main_units;
+  r.row_cut = main_units == units ? P : grouped_row_of_unit(offsets_host, G, P, main_units);
+  return r;
+}
 
 // The window rule at the reference's wind = 6 as a per-iteration no-fire certificate (fista_pair_ffa.h, the matrix-pipe
 // forms), then an exact re-solve of the problems it could not clear (n_done = -1).  Worth it when the rule is not expected

@@ -43,8 +43,14 @@ constexpr size_t mfma2_lds_bytes(int nbm) {
 // LOOPS: the _loops_deconv stop rule in full, as on the one-wave form (fista_mfma.h): each wave adds up its half of the two
 //   norms next to the update, the halves meet in LDS at the barrier that ends the iteration; plain variant only.
 // NT: near tiles -- 2 (K <= 33), or 3 (K <= 65: the tiles reach TWO blocks across the cut).
-template <int NBA, int NBB, bool TAPS_DEV, int ROLE, bool WITH_J = false, bool CERT = false, bool LOOPS = false, int NT = 2>
+// GROUPED (pb_fista_solve_grouped with PB_FLAG_GROUPED_SPLIT; with TAPS_DEV, plain variant): one HRF and one step per parcel
+//   as on the one-wave form (fista_mfma.h), the unit being the WORKGROUP: workgroup u takes its first row, its number of rows
+//   and its parcel from entry u of the unit table (a.perm, *a.n_dense entries) -- both waves read the same entry --, slots
+//   beyond its rows are dead (they read the unit's first row and store nothing), workgroups beyond the table leave.  The
+//   prologue only: everything that crosses the cut through LDS is per problem (slot v) already.
+template <int NBA, int NBB, bool TAPS_DEV, int ROLE, bool WITH_J = false, bool CERT = false, bool LOOPS = false, int NT = 2, bool GROUPED = false>
 __device__ __forceinline__ void mfma2_role(const FistaArgs& a, const MfmaTaps& tp, char* smem) {
+  static_assert(!GROUPED || (TAPS_DEV && !WITH_J && !CERT && !LOOPS), "parcels ride the plain variant with taps in device memory");
   static_assert(!CERT || (WITH_J && !TAPS_DEV), "the certificate runs in the rotated (cost trace) loop");
   static_assert(!LOOPS || (!WITH_J && !TAPS_DEV && !CERT), "the _loops_deconv rule rides the plain variant");
   static_assert(NBB >= NBA && NBB <= NBA + 1 && NBA >= 2 && NBB <= 10, "right half = the larger one; two blocks at least per wave");
@@ -57,9 +63,12 @@ __device__ __forceinline__ void mfma2_role(const FistaArgs& a, const MfmaTaps& t
   const int lane = threadIdx.x & 63;
   const int v = lane & 15, g = lane >> 4;
   int s0, s1;                                      // this launch's slots of its list (fista_fast.h: launch_slots)
-  launch_slots(a, s0, s1);
+  if constexpr (!GROUPED) launch_slots(a, s0, s1);
   bool live;
-  const int p = slot_to_problem(a, (int)blockIdx.x * 16 + v + s0, s1, live);
+  int parcel = 0;                                  // GROUPED: this workgroup's parcel (the same in every lane: scalar loads)
+  int pg = 0;
+  if constexpr (GROUPED) pg = grouped_problem(a, (int)blockIdx.x, v, live, parcel);
+  const int p = GROUPED ? pg : slot_to_problem(a, (int)blockIdx.x * 16 + v + s0, s1, live);
   const int tb = 8 * g;
 
   // ---- LDS: residual fragments of both waves, the exchange areas, the taps --------------------------------
@@ -92,11 +101,13 @@ __device__ __forceinline__ void mfma2_role(const FistaArgs& a, const MfmaTaps& t
   double step = a.step, g_scale = tp.g_scale;
   float y_scale = tp.y_scale;
   if constexpr (TAPS_DEV) {
+    const double* taps_w = a.taps_pp;                // this workgroup's HRF
+    if constexpr (GROUPED) taps_w += (int64_t)parcel * a.ldt;
     double run = 0.0, run2 = 0.0;
-    for (int k = 0; k <= lane && k < a.K; ++k) run += (double)(float)a.taps_pp[k];
+    for (int k = 0; k <= lane && k < a.K; ++k) run += (double)(float)taps_w[k];
     float cm = fabsf((float)run);
     if constexpr (NT == 3) {                       // lags 64 .. 95, every lane for lag 64 + (lane & 31): the store below stays unmasked
-      for (int k = 0; k <= 64 + (lane & 31) && k < a.K; ++k) run2 += (double)(float)a.taps_pp[k];
+      for (int k = 0; k <= 64 + (lane & 31) && k < a.K; ++k) run2 += (double)(float)taps_w[k];
       cm = fmaxf(cm, fabsf((float)run2));
     }
 #pragma unroll
@@ -108,7 +119,7 @@ __device__ __forceinline__ void mfma2_role(const FistaArgs& a, const MfmaTaps& t
     if constexpr (NT == 3) lc[64 + (lane & 31)] = (float)ldexp(run2, sa);
     g_scale = ldexp(1.0, -2 * sa);
     y_scale = ldexpf(1.0f, sa);
-    step = a.step_vec[0];
+    step = a.step_vec[GROUPED ? parcel : 0];
   } else {
     lc[lane] = tp.c[lane];
     // (every lane, the upper half twice: a `lane < 32` mask is one more exec-masked region for the compiler to park registers in)
@@ -551,14 +562,18 @@ __device__ __forceinline__ void mfma2_role(const FistaArgs& a, const MfmaTaps& t
 }
 
 // one workgroup = two waves = 16 problems; the wave index picks the half (a scalar branch: each wave runs one role)
-template <int NBA, int NBB, bool TAPS_DEV = false, bool WITH_J = false, bool CERT = false, bool LOOPS = false, int NT = 2>
+template <int NBA, int NBB, bool TAPS_DEV = false, bool WITH_J = false, bool CERT = false, bool LOOPS = false, int NT = 2, bool GROUPED = false>
 __global__ __launch_bounds__(128) void fista_mfma2_kernel(FistaArgs a, MfmaTaps tp) {
   extern __shared__ __attribute__((aligned(16))) char mf2_smem[];
+  if constexpr (!GROUPED) {
   if (a.range) {                                   // a candidate launch of a device-side plan: workgroups beyond its slots leave
     if ((int)blockIdx.x * 16 + a.range[0] >= a.range[1]) return;      // (both waves: before any barrier)
   }
-  if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) mfma2_role<NBA, NBB, TAPS_DEV, 0, WITH_J, CERT, LOOPS, NT>(a, tp, mf2_smem);
-  else mfma2_role<NBA, NBB, TAPS_DEV, 1, WITH_J, CERT, LOOPS, NT>(a, tp, mf2_smem);
+  } else {
+    if ((int)blockIdx.x >= *a.n_dense) return;     // beyond the unit table (blockIdx.x and the load are scalar: both waves, before any barrier)
+  }
+  if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) mfma2_role<NBA, NBB, TAPS_DEV, 0, WITH_J, CERT, LOOPS, NT, GROUPED>(a, tp, mf2_smem);
+  else mfma2_role<NBA, NBB, TAPS_DEV, 1, WITH_J, CERT, LOOPS, NT, GROUPED>(a, tp, mf2_smem);
 }
 
 // Plain solves, with or without the cost trace, the window rule (wind = 6) as a no-fire certificate, the _loops_deconv

@@ -34,8 +34,11 @@ constexpr size_t mfma4_lds_bytes(int A) {
 // One wave's share, KW = wave index.  HAS_L / HAS_R: there is a wave to the left / right; LASTW: the wave holding the end
 // of the series (any of its blocks may be padding).  (Four bodies per kernel: with the index at run time the two middle
 // waves could share one, at the price of a dozen address registers -- and of scratch, at ten blocks per wave.)
-template <int NBW, int KW, bool TAPS_DEV, bool WITH_J = false, bool CERT = false, bool LOOPS = false, int NT = 2>
+// GROUPED: one HRF and one step per parcel, the workgroup's 16 problems from entry blockIdx.x of the unit table -- fista_mfma2.h's
+// GROUPED, restated; all four waves read the same entry.
+template <int NBW, int KW, bool TAPS_DEV, bool WITH_J = false, bool CERT = false, bool LOOPS = false, int NT = 2, bool GROUPED = false>
 __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& tp, char* smem) {
+  static_assert(!GROUPED || (TAPS_DEV && !WITH_J && !CERT && !LOOPS), "parcels ride the plain variant with taps in device memory");
   constexpr int k = KW;
   constexpr bool HAS_L = KW > 0, HAS_R = KW < MFMA4_WAVES - 1, LASTW = KW == MFMA4_WAVES - 1;
   static_assert(!CERT || (WITH_J && !TAPS_DEV), "the certificate runs in the rotated (cost trace) loop");
@@ -51,9 +54,12 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
   const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   const int v = lane & 15, g = lane >> 4;
   int s0, s1;                                      // this launch's slots of its list (fista_fast.h: launch_slots)
-  launch_slots(a, s0, s1);
+  if constexpr (!GROUPED) launch_slots(a, s0, s1);
   bool live;
-  const int p = slot_to_problem(a, (int)blockIdx.x * 16 + v + s0, s1, live);
+  int parcel = 0;                                  // GROUPED: this workgroup's parcel (the same in every lane: scalar loads)
+  int pg = 0;
+  if constexpr (GROUPED) pg = grouped_problem(a, (int)blockIdx.x, v, live, parcel);
+  const int p = GROUPED ? pg : slot_to_problem(a, (int)blockIdx.x * 16 + v + s0, s1, live);
   const int tb = 8 * g;
   const int nrem = a.N - 32 * qoff - tb;           // sample j of block q of this lane exists iff 32 q + j < nrem
 
@@ -83,11 +89,13 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
   double step = a.step, g_scale = tp.g_scale;
   float y_scale = tp.y_scale;
   if constexpr (TAPS_DEV) {
+    const double* taps_w = a.taps_pp;                // this workgroup's HRF
+    if constexpr (GROUPED) taps_w += (int64_t)parcel * a.ldt;
     double run = 0.0, run2 = 0.0;
-    for (int kk = 0; kk <= lane && kk < a.K; ++kk) run += (double)(float)a.taps_pp[kk];
+    for (int kk = 0; kk <= lane && kk < a.K; ++kk) run += (double)(float)taps_w[kk];
     float cm = fabsf((float)run);
     if constexpr (NT == 3) {                       // lags 64 .. 95, every lane for lag 64 + (lane & 31): the store below stays unmasked
-      for (int kk = 0; kk <= 64 + (lane & 31) && kk < a.K; ++kk) run2 += (double)(float)a.taps_pp[kk];
+      for (int kk = 0; kk <= 64 + (lane & 31) && kk < a.K; ++kk) run2 += (double)(float)taps_w[kk];
       cm = fmaxf(cm, fabsf((float)run2));
     }
 #pragma unroll
@@ -99,7 +107,7 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
     if constexpr (NT == 3) lc[64 + (lane & 31)] = (float)ldexp(run2, sa);
     g_scale = ldexp(1.0, -2 * sa);
     y_scale = ldexpf(1.0f, sa);
-    step = a.step_vec[0];
+    step = a.step_vec[GROUPED ? parcel : 0];
   } else {
     lc[lane] = tp.c[lane];
     // (every lane, the upper half twice: a `lane < 32` mask is one more exec-masked region for the compiler to park registers in)
@@ -580,17 +588,21 @@ __device__ __forceinline__ void mfma4_role(const FistaArgs& a, const MfmaTaps& t
 }
 
 // one workgroup = four waves = 16 problems; the wave index picks the share (scalar branches: each wave runs one role)
-template <int A, bool TAPS_DEV = false, bool WITH_J = false, bool CERT = false, bool LOOPS = false, int NT = 2>
+template <int A, bool TAPS_DEV = false, bool WITH_J = false, bool CERT = false, bool LOOPS = false, int NT = 2, bool GROUPED = false>
 __global__ __launch_bounds__(256) void fista_mfma4_kernel(FistaArgs a, MfmaTaps tp) {
   extern __shared__ __attribute__((aligned(16))) char mf4_smem[];
+  if constexpr (!GROUPED) {
   if (a.range) {                                   // a candidate launch of a device-side plan: workgroups beyond its slots leave
     if ((int)blockIdx.x * 16 + a.range[0] >= a.range[1]) return;      // (all waves: before any barrier)
   }
+  } else {
+    if ((int)blockIdx.x >= *a.n_dense) return;     // beyond the unit table (blockIdx.x and the load are scalar: all waves, before any barrier)
+  }
   const int k = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (k == 0) mfma4_role<A, 0, TAPS_DEV, WITH_J, CERT, LOOPS, NT>(a, tp, mf4_smem);
-  else if (k == 1) mfma4_role<A, 1, TAPS_DEV, WITH_J, CERT, LOOPS, NT>(a, tp, mf4_smem);
-  else if (k == 2) mfma4_role<A, 2, TAPS_DEV, WITH_J, CERT, LOOPS, NT>(a, tp, mf4_smem);
-  else mfma4_role<A, 3, TAPS_DEV, WITH_J, CERT, LOOPS, NT>(a, tp, mf4_smem);
+  if (k == 0) mfma4_role<A, 0, TAPS_DEV, WITH_J, CERT, LOOPS, NT, GROUPED>(a, tp, mf4_smem);
+  else if (k == 1) mfma4_role<A, 1, TAPS_DEV, WITH_J, CERT, LOOPS, NT, GROUPED>(a, tp, mf4_smem);
+  else if (k == 2) mfma4_role<A, 2, TAPS_DEV, WITH_J, CERT, LOOPS, NT, GROUPED>(a, tp, mf4_smem);
+  else mfma4_role<A, 3, TAPS_DEV, WITH_J, CERT, LOOPS, NT, GROUPED>(a, tp, mf4_smem);
 }
 
 // Plain solves, with or without the cost trace, the window rule (wind = 6) as a no-fire certificate, the _loops_deconv rule

@@ -9,11 +9,19 @@ parcel's taps (``pb_fista_solve_grouped``), the normal equations summed per parc
 (``pb_hrf_normal_eq_w_grouped``), the 1-D searches (``pb_theta_fit``, one workgroup per parcel) and the step constants
 (``pb_gram_frobenius``).  Single GPU; float32 ``Y``; no early stopping.
 """
+import os
+
 import numpy as np
 import torch
 
 from . import _lib, solver
 from .hrf_model import MAX_DELTA, MIN_DELTA
+
+# Series of 311 .. 1 280 scans (up to 48 taps) on the split matrix-pipe forms of the grouped z-step is OPT-IN
+# (PB_FLAG_GROUPED_SPLIT): the environment variable PYBOLD_AMD_PARCELS_SPLIT ("1" is on; the convention of
+# PYBOLD_AMD_PP_SPLIT, bold_signal.py) ORs the flag into every z-step of bd_parcels.  Read when a loop starts.
+def parcels_split_opt_in():
+    return os.environ.get("PYBOLD_AMD_PARCELS_SPLIT", "0") == "1"
 
 
 def sort_by_label(labels):
@@ -31,6 +39,8 @@ def _parcel_loop(Y, po, t_r, lbda, theta, hrf_dur, bounds, nb_iter, nb_inner, fo
     V, n = Y.shape
     dev = Y.device
     base = force if isinstance(force, int) else solver._FORCE[force]
+    if parcels_split_opt_in():
+        base |= _lib.PB_FLAG_GROUPED_SPLIT
     taps = solver.spm_hrf_batch(theta, t_r, hrf_dur)                    # (G, K)
     K = taps.shape[1]
     ne_len = K * K + K + 1
@@ -70,7 +80,11 @@ def bd_parcels(Y, labels, t_r, lbda=1.0, theta_0=None, hrf_dur=20.0, bounds=None
     ``(G, K)`` with one HRF per parcel, and ``d`` with ``'labels'`` (the G distinct labels: row ``g`` of ``H``, column
     ``g`` of ``'theta'`` and ``'J'`` belong to ``d['labels'][g]``), ``'sizes'`` (voxels per parcel), ``'theta'``
     ``(nb_iter + 1, G)`` and ``'J'`` ``(nb_iter + 2, G)``, the cost of every parcel normalised by its own ``||y||^2``.
-    ``force`` is handed to the z-steps (``"mfma"``, ``"valu"``: tests and measurements).  Rows are sorted by label
+    ``force`` is handed to the z-steps (``"mfma"``, ``"valu"``: tests and measurements; ``"gsplit"``, ``"gsplit_mfma"``:
+    the opt-in below).  Up to 310 scans with up to 33 taps the z-steps run on the matrix pipe; 311 .. 1 280 scans with up to
+    48 taps do so only by opt-in -- ``force="gsplit"`` or ``PYBOLD_AMD_PARCELS_SPLIT=1`` in the environment, which adds
+    ``PB_FLAG_GROUPED_SPLIT`` to whatever ``force`` says (:func:`pybold_amd.solver.fista_solve_grouped`) -- and on the
+    per-problem vector forms otherwise.  Rows are sorted by label
     once; with ``verbose=0`` nothing returns to the host before the loop ends."""
     if not torch.is_tensor(Y):
         Y = torch.from_numpy(np.ascontiguousarray(np.asarray(Y), dtype=np.float32)).to(solver.device())

@@ -55,7 +55,12 @@ _FORCE = {None: 0, "generic": PB_FLAG_FORCE_GENERIC, "fast": PB_FLAG_FORCE_FAST,
           "noresolve": _lib.PB_FLAG_CERT_NO_RESOLVE,          # ... through the default dispatch
           "mfmaonly": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | _lib.PB_FLAG_CERT_NO_RESOLVE,
           "mfmacert": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | PB_FLAG_FORCE_CERT,
-          "mfmacertonly": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | PB_FLAG_FORCE_CERT | _lib.PB_FLAG_CERT_NO_RESOLVE}
+          "mfmacertonly": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | PB_FLAG_FORCE_CERT | _lib.PB_FLAG_CERT_NO_RESOLVE,
+          # fista_solve_grouped only (opt-in): 311 .. 1 280 scans on the split matrix-pipe forms -- "gsplit": library dispatch;
+          # "gsplit_mfma": every unit on them, one launch; "gsplit_mfmaonly": ... and no re-solve of what the guards hand back
+          "gsplit": _lib.PB_FLAG_GROUPED_SPLIT,
+          "gsplit_mfma": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | _lib.PB_FLAG_GROUPED_SPLIT,
+          "gsplit_mfmaonly": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | _lib.PB_FLAG_GROUPED_SPLIT | _lib.PB_FLAG_CERT_NO_RESOLVE}
 
 
 _warned = set()
@@ -1321,13 +1326,33 @@ def grouped_wave_table(offsets, per=16):
     return table, first
 
 
+def grouped_route(offsets, n_scans, n_taps, force=None):
+    """What :func:`fista_solve_grouped` decides for these parcels (``offsets``: ``G + 1`` integers or a
+    :class:`ParcelOffsets`), series length, HRF length and ``force`` (a name or raw ``PB_FLAG_*`` bits), from the host side
+    of the library (``pb_fista_grouped_route``; no launch): ``(code, main_units, row_cut)`` -- ``code`` in the numbering of
+    :func:`which_kernel`'s library call: 4 the one-wave matrix-pipe form, 5 two waves per unit of 16 rows, 6 four waves,
+    0 every row on the per-problem vector route, -1 the call would raise; ``main_units`` units of the table run in that
+    launch, the rows from ``row_cut`` on (the number of rows: none) on the vector forms behind it."""
+    import ctypes
+    host = offsets.host if isinstance(offsets, ParcelOffsets) else np.ascontiguousarray(np.asarray(offsets).ravel(), dtype=np.int32)
+    mu, rc = ctypes.c_int(0), ctypes.c_int(0)
+    code = _lib.load().pb_fista_grouped_route(host.ctypes.data, int(host.size - 1), int(host[-1]) if host.size else 0, int(n_scans),
+                                              int(n_taps), force if isinstance(force, int) else _FORCE[force], ctypes.byref(mu),
+                                              ctypes.byref(rc))
+    return int(code), mu.value, rc.value
+
+
 def fista_solve_grouped(Y, taps, steps, offsets, lbda, n_iter, W0=None, force=None, inplace=False, work=None):
     """:func:`fista_solve_pp` with one HRF and one step per PARCEL: the rows of ``Y`` (float32 CUDA ``(V, N)``) are
     contiguous by parcel, ``offsets`` (``G + 1`` integers or a :class:`ParcelOffsets`) their ranges, ``taps`` float64
     CUDA ``(G, K)``, ``steps`` float64 CUDA ``(G,)``.  129 .. 310 scans with up to 33 taps run on the matrix pipe, a
     wave's 16 problems all of one parcel (calls of 4 096 rows or more; ``force="mfma"`` / ``"mfmaonly"``: whatever the
     number of rows, an error for other shapes), everything else -- and ``force="valu"`` -- on the per-problem vector
-    forms with each row's parcel's taps.  ``force`` may also be raw ``PB_FLAG_*`` bits.  No stop rule.  ``work``: an int32 CUDA buffer of
+    forms with each row's parcel's taps.  Opt-in, ``force="gsplit"`` (``PB_FLAG_GROUPED_SPLIT``): 311 .. 1 280 scans with
+    up to 48 taps run on the split matrix-pipe forms too -- two waves per unit of 16 rows up to 640 scans, four beyond; whole
+    passes and large remainders there, the rest behind them on the vector forms (:func:`grouped_route` tells) --,
+    ``"gsplit_mfma"`` / ``"gsplit_mfmaonly"``: every unit there, whatever the number of rows.  Without the opt-in those
+    lengths run on the vector route.  ``force`` may also be raw ``PB_FLAG_*`` bits.  No stop rule.  ``work``: an int32 CUDA buffer of
     ``pb_fista_grouped_work_len(V, G, K)`` words to reuse.  Returns ``(W, n_done)``."""
     lib = _lib.load()
     Y = _rows(Y, torch.float32, "Y")
