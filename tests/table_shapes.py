@@ -19,9 +19,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pybold_amd", "csrc")
 
-# table -> (file, macro, scans per unit of S)
+# table -> (file, macro, scans per unit of S); the two 48-tap tables are read by tests/search_cases.py
 TABLES = {"fast": ("fast_table.inc", "PB_FAST", 16), "wide": ("wide_table.inc", "PB_WIDE", 64),
-          "exact": ("exact_table.inc", "PB_EXACT", 64), "exact_split": ("exact_split_table.inc", "PB_EXACT_SPLIT", 256)}
+          "exact": ("exact_table.inc", "PB_EXACT", 64), "exact_split": ("exact_split_table.inc", "PB_EXACT_SPLIT", 256),
+          "exact_long": ("exact_long_table.inc", "PB_EXACT_LONG", 64),
+          "exact_split_long": ("exact_split_long_table.inc", "PB_EXACT_SPLIT_LONG", 256)}
 N_GRID, K_GRID = 2500, 50          # the brute-force grid: 1 <= N <= N_GRID, 1 <= K <= K_GRID
 WINDS = (4, 6, 8)                  # window lengths the register-resident forms carry
 TOLS = (0.1, 0.02, 0.005)          # the tolerances of test_window_rule_other_window_lengths
