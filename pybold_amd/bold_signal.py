@@ -29,6 +29,7 @@ Beyond the reference's surface: ``deconv_auto`` is that ``lbda=None`` call with 
 whole search resident on the device (``engine``), see there.
 There is no CPU fallback: without the HIP library or a GPU these raise.
 """
+import collections
 import os
 
 import numpy as np
@@ -156,23 +157,93 @@ LONG_HRF = os.environ.get("PYBOLD_AMD_LONG_HRF", "0") == "1"
 SPLIT_LONG_HRF = os.environ.get("PYBOLD_AMD_SPLIT_LONG_HRF", "0") == "1"
 
 
+# The three switches above: (the module attribute, read at call time; the form of `solver.F64_FORMS` it turns on, whose `force`
+# name and solve query are used; the fewest taps at which it names the form -- up to 32 the default register forms carry the call).
+_SWITCHES = (("PER_VOXEL_SPLIT", "four_waves", 1), ("LONG_HRF", "long", 33), ("SPLIT_LONG_HRF", "four_waves_long", 33))
+
+
+def _switch_force(switches, n, n_taps, stop, wind):
+    for switch, key, min_taps in switches:
+        form = solver.F64_FORMS[key]
+        if globals()[switch] and n_taps >= min_taps and getattr(solver, form.public.solve_query)(n, n_taps, stop, wind):
+            return form.force
+    return None
+
+
 def _long_hrf_force(n, n_taps, stop, wind):
     """``force`` of a float64 solve: ``"long_hrf"`` when ``LONG_HRF`` is on, the HRF has more than 32 taps (up to 32 the
     default register form carries the call) and the shape is carried; ``"split_long_hrf"`` likewise under
     ``SPLIT_LONG_HRF`` (the two carry disjoint series lengths)."""
-    if LONG_HRF and n_taps > 32 and solver.long_hrf_supported(n, n_taps, stop, wind):
-        return "long_hrf"
-    if SPLIT_LONG_HRF and n_taps > 32 and solver.split_long_hrf_supported(n, n_taps, stop, wind):
-        return "split_long_hrf"
-    return None
+    return _switch_force(_SWITCHES[1:], n, n_taps, stop, wind)
 
 
 def _pv_force(n, n_taps, stop, wind):
     """``force`` of a per-voxel-HRF solve: ``"split"`` when ``PER_VOXEL_SPLIT`` is on and the shape is carried,
     ``"long_hrf"`` / ``"split_long_hrf"`` likewise under ``LONG_HRF`` / ``SPLIT_LONG_HRF``."""
-    if PER_VOXEL_SPLIT and solver.pp_split_supported(n, n_taps, stop, wind):
-        return "split"
-    return _long_hrf_force(n, n_taps, stop, wind)
+    return _switch_force(_SWITCHES, n, n_taps, stop, wind)
+
+
+# The engines of the `lbda=None` search that are resident on the device, one row each: the form of `solver.F64_FORMS` whose
+# search it runs; the HRFs it takes ("1d": one for all voxels, "pv": one per voxel, "any"); the fewest taps at which it is the
+# engine to run; `fallback`: the engine asked next when it does not carry a call -- under `AUTO_LBDA` always ("device_split"
+# also means everything "device" does), in `deconv_auto` only with `named_fallback`, where every other engine asked for by name
+# refuses; then what `deconv_auto(engine=...)` answers after "deconv_auto(engine='...'): " to the wrong kind of HRF and to a
+# shape beyond its limits.
+_Engine = collections.namedtuple("_Engine", "name form hrf min_taps fallback named_fallback wrong_hrf limit")
+_THIS_CALL = "; this call has %d scans, %d taps, wind = %d"
+_SPLIT_LIMIT = ("the four-wave device-resident lambda search carries series of 641..1280 scans, HRFs of up to 32 taps and "
+                "wind = 6" + _THIS_CALL)
+_ENGINES = collections.OrderedDict((e.name, e) for e in (
+    _Engine("device", "one_wave", "any", 1, None, False, None,
+            "the device-resident lambda search carries series of up to 640 scans, HRFs of up to 32 taps and wind = 6" + _THIS_CALL),
+    _Engine("device_split", "four_waves", "1d", 1, "device", False,
+            "the four-wave device-resident lambda search takes one HRF for all voxels; with one HRF per voxel (hrf of shape "
+            "{hrf}) the device-resident search carries series of up to 640 scans (engine='device'), longer ones run the host "
+            "loop (engine='host') or, opt-in, the four-wave search with per-voxel HRFs (engine='device_split_pp')", _SPLIT_LIMIT),
+    _Engine("device_split_pp", "four_waves", "pv", 1, "device_split", False,
+            "the four-wave device-resident lambda search with one HRF per voxel takes hrf of shape (V, K); a 1-D hrf runs on "
+            "engine='device_split'", _SPLIT_LIMIT),
+    _Engine("device_long_hrf", "long", "any", 33, "device", False, None,
+            "the device-resident lambda search for long HRFs carries HRFs of 33..48 taps, series of up to 640 scans and "
+            "wind = 6 (up to 32 taps: engine='device')" + _THIS_CALL),
+    # (asked for by name it still runs what "device_split" does: the existing four-wave search, faster up to 32 taps)
+    _Engine("device_split_long_hrf", "four_waves_long", "any", 33, "device_split", True, None,
+            "the four-wave device-resident lambda search for long HRFs carries HRFs of 33..48 taps (1-D, or one per voxel), "
+            "series of 641..1280 scans and wind = 6 (up to 32 taps with one HRF for all voxels it runs engine='device_split'; "
+            "one HRF per voxel of up to 32 taps: engine='device_split_pp'; up to 640 scans: engine='device_long_hrf')"
+            + _THIS_CALL)))
+
+
+def _engine_that_carries(asked, n, n_taps, wind, per_voxel, by_name):
+    """The engine of ``_ENGINES`` that runs a call asking for ``asked`` -- itself, or down its fallbacks the first whose
+    HRF kind, tap floor and form's search (``solver.auto_lbda*_supported``) fit -- or None.  ``by_name``: as
+    ``deconv_auto(engine=asked)`` falls back; else as ``AUTO_LBDA = asked`` does."""
+    row = _ENGINES.get(asked)
+    while row is not None:
+        carried = getattr(solver, solver.F64_FORMS[row.form].public.search_query)
+        if row.hrf in ("any", "pv" if per_voxel else "1d") and n_taps >= row.min_taps and carried(n, n_taps, wind):
+            return row.name
+        row = _ENGINES.get(row.fallback) if (row.named_fallback or not by_name) else None
+    return None
+
+
+def _resolve_engine(engine, n, n_taps, wind, per_voxel, hrf_shape):
+    """What ``deconv_auto(engine=engine)`` runs: "host", or the device engine that carries the call; the ``ValueError`` of an
+    engine asked for by name that does not; for "auto" the host loop with one warning."""
+    if engine == "host":
+        return engine
+    row = _ENGINES["device" if engine == "auto" else engine]
+    if row.hrf not in ("any", "pv" if per_voxel else "1d"):
+        raise ValueError("deconv_auto(engine=%r): " % (engine,) + row.wrong_hrf.format(hrf=hrf_shape))
+    runs = _engine_that_carries(row.name, n, n_taps, wind, per_voxel, by_name=True)
+    if runs is None:
+        limit = row.limit % (n, n_taps, wind)
+        if engine != "auto":
+            raise ValueError("deconv_auto(engine=%r): " % (engine,) + limit)
+        solver.warn_once(("auto-lambda-host", n, n_taps, wind), "deconv_auto: " + limit + ": running the host loop.",
+                         stacklevel=4)                # (the caller of deconv_auto, as from there)
+        runs = "host"
+    return runs
 
 
 def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
@@ -193,19 +264,9 @@ def deconv(y, t_r, hrf, lbda=None, early_stopping=True, tol=1.0e-6,  # noqa
     """
     per_voxel = _per_voxel_hrf(y, hrf, "deconv")
     if lbda is None:
-        if (AUTO_LBDA in ("device", "device_split", "device_split_pp", "device_long_hrf", "device_split_long_hrf")
-                and _n_dim(y) == 2):
+        if AUTO_LBDA in _ENGINES and _n_dim(y) == 2:   # (1-D calls, and what no engine of AUTO_LBDA's carries: the host loop)
             n_taps = int(_shape_of(hrf)[-1]) if per_voxel else np.size(hrf)
-            split = (AUTO_LBDA in ("device_split", "device_split_pp", "device_split_long_hrf")
-                     and solver.auto_lbda_split_supported(_n_scans(y), n_taps, wind))
-            engine = ("device" if solver.auto_lbda_supported(_n_scans(y), n_taps, wind)
-                      else "device_long_hrf" if (AUTO_LBDA == "device_long_hrf" and n_taps > 32
-                                                 and solver.auto_lbda_long_supported(_n_scans(y), n_taps, wind))
-                      else "device_split_long_hrf" if (AUTO_LBDA == "device_split_long_hrf" and n_taps > 32
-                                                       and solver.auto_lbda_split_long_supported(_n_scans(y), n_taps, wind))
-                      else "device_split" if split and not per_voxel
-                      else "device_split_pp" if split and per_voxel and AUTO_LBDA == "device_split_pp"
-                      else None)
+            engine = _engine_that_carries(AUTO_LBDA, _n_scans(y), n_taps, wind, per_voxel, by_name=False)
             if engine:
                 return deconv_auto(y, t_r, hrf, early_stopping=early_stopping, tol=tol, wind=wind, nb_iter=nb_iter,
                                    nb_sub_iter=nb_sub_iter, engine=engine, verbose=verbose)[:6]
@@ -312,54 +373,12 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     same input (lists for a 1-D ``y``; ``(n_outer, V)`` arrays padded with NaN for a batch, trimmed to the longest
     row's outer iterations; CUDA in -> ``x, z, diff_z`` CUDA); ``info`` holds ``alpha``, ``lbda`` (final, per
     voxel), ``n_outer``, ``n_inner`` (outer / summed inner iterations per voxel), ``sigma`` and ``engine``."""
-    if engine not in ("auto", "device", "host", "device_split", "device_split_pp", "device_long_hrf", "device_split_long_hrf"):
+    if engine not in ("auto", "host") + tuple(_ENGINES):
         raise ValueError("deconv_auto: engine must be 'auto', 'device', 'host', 'device_split', 'device_split_pp', "
                          "'device_split_long_hrf' or 'device_long_hrf', got %r" % (engine,))
     per_voxel = _per_voxel_hrf(y, hrf, "deconv_auto")
     n, n_taps = _n_scans(y), (int(_shape_of(hrf)[-1]) if per_voxel else int(np.size(hrf)))
-    if engine == "device_split":
-        if per_voxel:
-            raise ValueError("deconv_auto(engine='device_split'): the four-wave device-resident lambda search takes one HRF "
-                             "for all voxels; with one HRF per voxel (hrf of shape %s) the device-resident search carries "
-                             "series of up to 640 scans (engine='device'), longer ones run the host loop (engine='host') "
-                             "or, opt-in, the four-wave search with per-voxel HRFs (engine='device_split_pp')"
-                             % (_shape_of(hrf),))
-        if not solver.auto_lbda_split_supported(n, n_taps, wind):
-            raise ValueError("deconv_auto(engine='device_split'): the four-wave device-resident lambda search carries series of "
-                             "641..1280 scans, HRFs of up to 32 taps and wind = 6; this call has %d scans, %d taps, wind = %d"
-                             % (n, n_taps, wind))
-    elif engine == "device_split_pp":
-        if not per_voxel:
-            raise ValueError("deconv_auto(engine='device_split_pp'): the four-wave device-resident lambda search with one HRF "
-                             "per voxel takes hrf of shape (V, K); a 1-D hrf runs on engine='device_split'")
-        if not solver.auto_lbda_split_supported(n, n_taps, wind):
-            raise ValueError("deconv_auto(engine='device_split_pp'): the four-wave device-resident lambda search carries "
-                             "series of 641..1280 scans, HRFs of up to 32 taps and wind = 6; this call has %d scans, %d taps, "
-                             "wind = %d" % (n, n_taps, wind))
-    elif engine == "device_long_hrf":
-        if not (33 <= n_taps <= 48 and solver.auto_lbda_long_supported(n, n_taps, wind)):
-            raise ValueError("deconv_auto(engine='device_long_hrf'): the device-resident lambda search for long HRFs carries "
-                             "HRFs of 33..48 taps, series of up to 640 scans and wind = 6 (up to 32 taps: engine='device'); "
-                             "this call has %d scans, %d taps, wind = %d" % (n, n_taps, wind))
-    elif engine == "device_split_long_hrf":
-        if n_taps <= 32 and not per_voxel and solver.auto_lbda_split_supported(n, n_taps, wind):
-            engine = "device_split"                 # (what "device_split" does: the existing four-wave search, faster up to 32 taps)
-        elif not (33 <= n_taps <= 48 and solver.auto_lbda_split_long_supported(n, n_taps, wind)):
-            raise ValueError("deconv_auto(engine='device_split_long_hrf'): the four-wave device-resident lambda search for long "
-                             "HRFs carries HRFs of 33..48 taps (1-D, or one per voxel), series of 641..1280 scans and wind = 6 "
-                             "(up to 32 taps with one HRF for all voxels it runs engine='device_split'; one HRF per voxel of up "
-                             "to 32 taps: engine='device_split_pp'; up to 640 scans: engine='device_long_hrf'); this call has "
-                             "%d scans, %d taps, wind = %d" % (n, n_taps, wind))
-    elif engine != "host":
-        if solver.auto_lbda_supported(n, n_taps, wind):
-            engine = "device"
-        else:
-            limit = ("the device-resident lambda search carries series of up to 640 scans, HRFs of up to 32 taps and "
-                     "wind = 6; this call has %d scans, %d taps, wind = %d" % (n, n_taps, wind))
-            if engine == "device":
-                raise ValueError("deconv_auto(engine='device'): " + limit)
-            solver.warn_once(("auto-lambda-host", n, n_taps, wind), "deconv_auto: " + limit + ": running the host loop.")
-            engine = "host"
+    engine = _resolve_engine(engine, n, n_taps, wind, per_voxel, _shape_of(hrf))
     on_device = torch.is_tensor(y) and y.is_cuda
     if sigma is None:
         if on_device and 5 <= n <= solver.MAD_DAUB_NMAX and y.dtype in (torch.float32, torch.float64):
@@ -373,12 +392,11 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
         info["engine"] = "host"
         return out + (info,)
 
+    names = solver.F64_FORMS[_ENGINES[engine].form].public      # (looked up on `solver` at call time)
     if per_voxel:
         Y, T, one_d = _pv_to_device(y, hrf)
         V = Y.shape[0]
-        solve = {"device_split_pp": solver.auto_lbda_solve_split_pp,
-                 "device_long_hrf": solver.auto_lbda_solve_long_pp,
-                 "device_split_long_hrf": solver.auto_lbda_solve_split_long_pp}.get(engine, solver.auto_lbda_solve_pp)
+        solve = getattr(solver, names.search_pp)
         W, res = solve(Y, T, _pv_steps(T, n), sigma, early_stopping=early_stopping, tol=tol, wind=wind,
                        nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
         X, Z = solver.fista_outputs_pp(W, T)
@@ -394,9 +412,7 @@ def deconv_auto(y, t_r, hrf, sigma=None, early_stopping=True, tol=1.0e-6, wind=6
     hrf = np.asarray(hrf, dtype=np.float64)
     H = ConvAndLinear(DiscretInteg(), hrf, dim_in=n, dim_out=n)
     step = 1.0 / (0.9 * spectral_radius_est(H, (n,)))
-    solve = {"device_split": solver.auto_lbda_solve_split,
-             "device_long_hrf": solver.auto_lbda_solve_long,
-             "device_split_long_hrf": solver.auto_lbda_solve_split_long}.get(engine, solver.auto_lbda_solve)
+    solve = getattr(solver, names.search)
     W, res = solve(Y, hrf, step, sigma, early_stopping=early_stopping, tol=tol, wind=wind,
                    nb_iter=int(nb_iter), nb_sub_iter=int(nb_sub_iter), outer_chunk=int(outer_chunk or 0))
     X, Z = solver.fista_outputs(W, hrf)

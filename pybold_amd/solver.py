@@ -5,6 +5,8 @@ device memory and streams only); the arithmetic happens in the hand-written
 HIP kernels of ``libpybold_hip.so``.  Rows are problems ("voxels"), the last
 dimension is time.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -62,17 +64,71 @@ _FORCE = {None: 0, "generic": PB_FLAG_FORCE_GENERIC, "fast": PB_FLAG_FORCE_FAST,
           "gsplit_mfma": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | _lib.PB_FLAG_GROUPED_SPLIT,
           "gsplit_mfmaonly": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | _lib.PB_FLAG_GROUPED_SPLIT | _lib.PB_FLAG_CERT_NO_RESOLVE}
 
+# The float64 register family, one row per form: what Python has to know of `kF64[]` (csrc/dispatch.h).  No limit
+# of a form stands here -- the `*_supported` queries ask the library.  `force`: the name that asks a float64 solve for the form;
+# `solve` / `solve_pp`: the C entry point and flag bits that name selects with the taps on the host / with one HRF per problem
+# (None: no such solve); `solve_query`, `search_query`: its `pb_*_supported` queries; `search`, `search_pp`: its lambda-search
+# entry points; `op`: its `torch.ops.pybold_hip` search operator; `public`: the names of this module bound to it (below, beside
+# `_auto_lbda_solve`) -- the search, the search with one HRF per problem, the solve query, the search query.
+_F64Names = collections.namedtuple("_F64Names", "search search_pp solve_query search_query")
+_F64Form = collections.namedtuple("_F64Form", "key force solve solve_pp solve_query search_query search search_pp op public")
+F64_FORMS = collections.OrderedDict((f.key, f) for f in (
+    _F64Form("one_wave", "fast",
+             ("pb_fista_solve_d", PB_FLAG_FORCE_FAST), ("pb_fista_solve_pp_d", PB_FLAG_FORCE_FAST),
+             None, "pb_auto_lbda_supported", "pb_auto_lbda_d", "pb_auto_lbda_pp_d", "auto_lbda_solve",
+             _F64Names("auto_lbda_solve", "auto_lbda_solve_pp", None, "auto_lbda_supported")),
+    _F64Form("four_waves", "split",
+             None, ("pb_fista_solve_pp_d", _lib.PB_FLAG_PP_SPLIT),
+             "pb_fista_pp_split_supported", "pb_auto_lbda_split_supported", "pb_auto_lbda_split_d", "pb_auto_lbda_split_pp_d",
+             "auto_lbda_solve_split",
+             _F64Names("auto_lbda_solve_split", "auto_lbda_solve_split_pp", "pp_split_supported", "auto_lbda_split_supported")),
+    _F64Form("long", "long_hrf",
+             ("pb_fista_solve_d", _lib.PB_FLAG_LONG_HRF), ("pb_fista_solve_pp_d", _lib.PB_FLAG_LONG_HRF),
+             "pb_fista_long_hrf_supported", "pb_auto_lbda_long_supported", "pb_auto_lbda_long_d", "pb_auto_lbda_long_pp_d",
+             "auto_lbda_solve_long",
+             _F64Names("auto_lbda_solve_long", "auto_lbda_solve_long_pp", "long_hrf_supported", "auto_lbda_long_supported")),
+    # (the four-wave form for long HRFs has solve entry points of its own, with the same parameter lists, in the place of a flag)
+    _F64Form("four_waves_long", "split_long_hrf",
+             ("pb_fista_solve_split_long_d", 0), ("pb_fista_solve_split_long_pp_d", 0),
+             "pb_fista_split_long_hrf_supported", "pb_auto_lbda_split_long_supported", "pb_auto_lbda_split_long_d",
+             "pb_auto_lbda_split_long_pp_d", "auto_lbda_solve_split_long",
+             _F64Names("auto_lbda_solve_split_long", "auto_lbda_solve_split_long_pp", "split_long_hrf_supported",
+                       "auto_lbda_split_long_supported"))))
+_F64_BY_FORCE = dict((f.force, f) for f in F64_FORMS.values())
+_F64_SPLIT_PP_ONLY = "force='split' names the four-wave form with one HRF per problem: fista_solve_pp_d only"
+_F64_FORCE_NAMES = {          # what a float64 solve answers to any other `force`: taps on the host / one HRF per problem
+    False: "float64 y: force must be None, 'fast' (register-resident float64 "
+           "kernel, one problem per wave), 'generic' (LDS kernel), 'long_hrf' (the register form "
+           "for HRFs of up to 48 taps, up to 640 scans) or 'split_long_hrf' (the same over four waves, "
+           "641..1280 scans)",
+    True: "float64 y: force must be None, 'fast' (register-resident float64 kernel, one problem per "
+          "wave), 'split' (the same over four waves, 641..1280 scans), 'generic' (LDS kernel), "
+          "'long_hrf' (one problem per wave, HRFs of up to 48 taps) or 'split_long_hrf' (four waves, "
+          "641..1280 scans, HRFs of up to 48 taps)"}
+
+
+def _f64_solve_route(force, pp):
+    """``(C entry point, flag bits)`` of a float64 solve asked for by ``force`` -- :func:`fista_solve_pp_d` (``pp``) or
+    :func:`fista_solve` on a float64 ``Y``; ``ValueError`` for a name that is no float64 form's."""
+    if force in (None, "generic"):                      # the library's dispatch / its LDS kernel: no form of the table
+        return "pb_fista_solve_pp_d" if pp else "pb_fista_solve_d", _FORCE[force]
+    form = _F64_BY_FORCE.get(force)
+    route = form and (form.solve_pp if pp else form.solve)
+    if route:
+        return route
+    raise ValueError(_F64_SPLIT_PP_ONLY if force == "split" else _F64_FORCE_NAMES[pp])
+
 
 _warned = set()
 
 
-def warn_once(key, message):
+def warn_once(key, message, stacklevel=3):
     """One ``RuntimeWarning`` per process and ``key``: the silent performance cliffs of the
     dispatch (LDS kernel, all-float64 kernel) are made loud here, not in a header."""
     if key not in _warned:
         _warned.add(key)
         import warnings
-        warnings.warn(message, RuntimeWarning, stacklevel=3)
+        warnings.warn(message, RuntimeWarning, stacklevel=stacklevel)
 
 
 def _warn_if_slow_kernel(lib, N, K, P, want_J, stop, wind, flags):
@@ -197,6 +253,30 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
+def _warm_start(W0, shape, dev, inplace=False):
+    """``(W, cold flag)``: the iterate a solve works in.  Without ``W0`` the kernels start from 0 themselves (no memset, no
+    read: ``PB_FLAG_COLD_START``); else a copy of ``W0`` -- with ``inplace``, ``W0`` itself where its rows need no copy."""
+    if W0 is None:
+        return torch.empty(shape, dtype=torch.float64, device=dev), PB_FLAG_COLD_START
+    W = _rows(W0, torch.float64, "W0")
+    if not inplace or W.data_ptr() != W0.data_ptr():
+        W = W.clone()
+    if W.shape != shape:
+        raise ValueError("W0 must be %s, got %s" % (shape, tuple(W.shape)))
+    return W, 0
+
+
+def _lbda_arg(lbda, dev, n=None):
+    """``(lbda_scalar, lbda_dev)``: a scalar as a number, anything else as a float64 vector on ``dev`` (of ``n`` entries,
+    where the caller says how many)."""
+    if np.ndim(lbda) == 0 and not torch.is_tensor(lbda):
+        return float(lbda), None
+    lbda_dev = torch.as_tensor(lbda, dtype=torch.float64).to(dev).contiguous().ravel()
+    if n is not None and lbda_dev.numel() != n:
+        raise ValueError("per-problem lbda must have %d entries" % n)
+    return 0.0, lbda_dev
+
+
 def has_fast_path(n_scans, n_taps):
     return bool(_lib.load().pb_fista_has_fast_path(int(n_scans), int(n_taps)))
 
@@ -278,7 +358,7 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
     Returns ``(W float64 (P, N), J float32 (P, n_iter) or None, n_done int32 (P,))``.
     """
     if force == "split":
-        raise ValueError("force='split' names the four-wave form with one HRF per problem: fista_solve_pp_d only")
+        raise ValueError(_F64_SPLIT_PP_ONLY)
     lib = _lib.load()
     f64 = torch.is_tensor(Y) and Y.dtype == torch.float64
     if force == "long_hrf" and not f64:
@@ -292,26 +372,12 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
     P = V * int(y_rep)
     taps = _as_taps(hrf)
     taps_dev = torch.from_numpy(taps).to(dev)
-    cold = 0
-    if W0 is None:                     # the kernels start from 0 themselves: no memset, no read
-        W = torch.empty((P, N), dtype=torch.float64, device=dev)
-        cold = PB_FLAG_COLD_START
-    else:
-        W = _rows(W0, torch.float64, "W0").clone()
-        if W.shape != (P, N):
-            raise ValueError("W0 must be %s, got %s" % ((P, N), tuple(W.shape)))
-    lbda_dev = None
-    lbda_scalar = 0.0
+    W, cold = _warm_start(W0, (P, N), dev)
     if not f64 and not (torch.is_tensor(lbda) and lbda.is_cuda) and (np.asarray(lbda) < 0).any():
         # pybold/bold_signal.py:66 with a negative threshold GROWS every entry (its lambda search gets there,
         # :141-145); only the float64 kernels restate that expression, the float32-FIR kernels clamp
         raise ValueError("negative lbda: only the float64 path (float64 Y) reproduces the reference's prox for it")
-    if np.ndim(lbda) == 0 and not torch.is_tensor(lbda):
-        lbda_scalar = float(lbda)
-    else:
-        lbda_dev = torch.as_tensor(lbda, dtype=torch.float64).to(dev).contiguous().ravel()
-        if lbda_dev.numel() != P:
-            raise ValueError("per-problem lbda must have %d entries" % P)
+    lbda_scalar, lbda_dev = _lbda_arg(lbda, dev, P)
     betas = _betas_on(dev, n_iter)
     J = torch.empty((P, max(n_iter, 1)), dtype=torch.float64 if f64 else torch.float32,
                     device=dev) if want_J else None
@@ -319,14 +385,7 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop=None,
         J.fill_(float("nan"))
     n_done = torch.empty((P,), dtype=torch.int32, device=dev)
     if f64:
-        if force not in (None, "generic", "fast", "long_hrf", "split_long_hrf"):
-            raise ValueError("float64 y: force must be None, 'fast' (register-resident float64 "
-                             "kernel, one problem per wave), 'generic' (LDS kernel), 'long_hrf' (the register form "
-                             "for HRFs of up to 48 taps, up to 640 scans) or 'split_long_hrf' (the same over four waves, "
-                             "641..1280 scans)")
-        flags = _lib.PB_FLAG_LONG_HRF if force == "long_hrf" else _FORCE.get(force, 0)
-        # (the four-wave form for long HRFs has an entry point of its own, with this parameter list, in the place of a flag)
-        entry = "pb_fista_solve_split_long_d" if force == "split_long_hrf" else "pb_fista_solve_d"
+        entry, flags = _f64_solve_route(force, pp=False)
         with torch.cuda.device(dev):
             rc = getattr(lib, entry)(
                 Y.data_ptr(), _ld(Y), int(y_rep), W.data_ptr(), _ld(W), P, N,
@@ -377,14 +436,10 @@ def fista_solve_backtrack(Y, hrf, lbda, step0, n_iter, eta=0.5, max_halvings_per
         W = torch.empty((P, N), dtype=torch.float64, device=dev)
         cold = PB_FLAG_COLD_START
     else:
-        W = _rows(W0, torch.float64, "W0").clone()
-    lbda_dev, lbda_scalar = None, 0.0
-    if np.ndim(lbda) == 0 and not torch.is_tensor(lbda):
-        lbda_scalar = float(lbda)
-    else:
-        lbda_dev = torch.as_tensor(lbda, dtype=torch.float64).to(dev).contiguous().ravel()
+        W = _rows(W0, torch.float64, "W0").clone()        # (no shape check here: _warm_start would add one)
+    lbda_scalar, lbda_dev = _lbda_arg(lbda, dev)
     betas = _betas_on(dev, n_iter)
-    step = torch.empty((P,), dtype=torch.float64, device=dev)
+    step =torch.empty((P,), dtype=torch.float64, device=dev)
     halv = torch.empty((P,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         rc = lib.pb_fista_solve_backtrack_d(
@@ -419,12 +474,7 @@ class FistaPlan:
             raise ValueError("W must be (%d, %d) with unit stride along time" % (self.P, self.N))
         self.W = _rows(W, torch.float64, "W")
         self.n_done = torch.empty((self.P,), dtype=torch.int32, device=self.dev)
-        self.lbda_dev = None
-        self.lbda = 0.0
-        if np.ndim(lbda) == 0 and not torch.is_tensor(lbda):
-            self.lbda = float(lbda)
-        else:
-            self.lbda_dev = torch.as_tensor(lbda, dtype=torch.float64).to(self.dev).contiguous().ravel()
+        self.lbda, self.lbda_dev = _lbda_arg(lbda, self.dev)
         self.step = float(step)
         self.n_iter = int(n_iter)
         self.betas = _betas_on(self.dev, self.n_iter)
@@ -768,21 +818,8 @@ def fista_solve_pp(Y, taps, steps, lbda, n_iter, W0=None, stop=None, tol=0.0, fo
     steps = steps.to(device=dev, dtype=torch.float64).contiguous().ravel()
     if steps.numel() != (1 if shared else V):
         raise ValueError("steps must have one entry per voxel (one in all for a shared HRF)")
-    cold = 0
-    if W0 is None:
-        W = torch.empty((V, N), dtype=torch.float64, device=dev)
-        cold = PB_FLAG_COLD_START
-    else:
-        W = _rows(W0, torch.float64, "W0")
-        if not inplace or W.data_ptr() != W0.data_ptr():
-            W = W.clone()
-        if W.shape != (V, N):
-            raise ValueError("W0 must be %s, got %s" % ((V, N), tuple(W.shape)))
-    lbda_dev, lbda_scalar = None, 0.0
-    if np.ndim(lbda) == 0 and not torch.is_tensor(lbda):
-        lbda_scalar = float(lbda)
-    else:
-        lbda_dev = torch.as_tensor(lbda, dtype=torch.float64).to(dev).contiguous().ravel()
+    W, cold = _warm_start(W0, (V, N), dev, inplace)
+    lbda_scalar, lbda_dev = _lbda_arg(lbda, dev)
     betas = _betas_on(dev, n_iter)
     n_done = torch.empty((V,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -823,28 +860,9 @@ def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=N
     steps = torch.as_tensor(steps, dtype=torch.float64).to(dev).contiguous().ravel()
     if steps.numel() != V:
         raise ValueError("steps must have one entry per voxel (%d)" % V)
-    if force not in (None, "generic", "fast", "split", "long_hrf", "split_long_hrf"):
-        raise ValueError("float64 y: force must be None, 'fast' (register-resident float64 kernel, one problem per "
-                         "wave), 'split' (the same over four waves, 641..1280 scans), 'generic' (LDS kernel), "
-                         "'long_hrf' (one problem per wave, HRFs of up to 48 taps) or 'split_long_hrf' (four waves, "
-                         "641..1280 scans, HRFs of up to 48 taps)")
-    flags = {"split": _lib.PB_FLAG_PP_SPLIT, "long_hrf": _lib.PB_FLAG_LONG_HRF}.get(force, _FORCE.get(force, 0))
-    entry = "pb_fista_solve_split_long_pp_d" if force == "split_long_hrf" else "pb_fista_solve_pp_d"
-    cold = 0
-    if W0 is None:
-        W = torch.empty((V, N), dtype=torch.float64, device=dev)
-        cold = PB_FLAG_COLD_START
-    else:
-        W = _rows(W0, torch.float64, "W0").clone()
-        if W.shape != (V, N):
-            raise ValueError("W0 must be %s, got %s" % ((V, N), tuple(W.shape)))
-    lbda_dev, lbda_scalar = None, 0.0
-    if np.ndim(lbda) == 0 and not torch.is_tensor(lbda):
-        lbda_scalar = float(lbda)
-    else:
-        lbda_dev = torch.as_tensor(lbda, dtype=torch.float64).to(dev).contiguous().ravel()
-        if lbda_dev.numel() != V:
-            raise ValueError("per-problem lbda must have %d entries" % V)
+    entry, flags = _f64_solve_route(force, pp=True)
+    W, cold = _warm_start(W0, (V, N), dev)
+    lbda_scalar, lbda_dev = _lbda_arg(lbda, dev, V)
     betas = _betas_on(dev, n_iter)
     J = torch.full((V, max(n_iter, 1)), float("nan"), dtype=torch.float64, device=dev) if want_J else None
     n_done = torch.empty((V,), dtype=torch.int32, device=dev)
@@ -856,24 +874,6 @@ def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=N
             _STOP[stop], float(tol), int(wind), n_done.data_ptr(), flags | cold, _stream_ptr(dev))
     _lib.check(rc, entry)
     return W, J, n_done
-
-
-def pp_split_supported(n_scans, n_taps, stop=None, wind=6):
-    """Whether :func:`fista_solve_pp_d` with ``force="split"`` carries this shape (``pb_fista_pp_split_supported``:
-    ``641 <= N <= 1280``, ``K <= 32``, the window rule at ``wind == 6``)."""
-    return bool(_lib.load().pb_fista_pp_split_supported(int(n_scans), int(n_taps), _STOP[stop], int(wind)))
-
-
-def long_hrf_supported(n_scans, n_taps, stop=None, wind=6):
-    """Whether :func:`fista_solve` (float64 ``Y``) and :func:`fista_solve_pp_d` with ``force="long_hrf"`` carry this
-    shape (``pb_fista_long_hrf_supported``: ``N <= 640``, ``K <= 48``, the window rule at ``wind == 6``)."""
-    return bool(_lib.load().pb_fista_long_hrf_supported(int(n_scans), int(n_taps), _STOP[stop], int(wind)))
-
-
-def split_long_hrf_supported(n_scans, n_taps, stop=None, wind=6):
-    """Whether :func:`fista_solve` (float64 ``Y``) and :func:`fista_solve_pp_d` with ``force="split_long_hrf"`` carry this
-    shape (``pb_fista_split_long_hrf_supported``: ``641 <= N <= 1280``, ``K <= 48``, the window rule at ``wind == 6``)."""
-    return bool(_lib.load().pb_fista_split_long_hrf_supported(int(n_scans), int(n_taps), _STOP[stop], int(wind)))
 
 
 def fista_stats_pp(W, Y, taps):
@@ -991,127 +991,23 @@ def mad_daub_noise_est(Y, c=0.6744):
     return out
 
 
-def auto_lbda_supported(n_scans, n_taps, wind=6):
-    """Whether :func:`auto_lbda_solve` carries this shape (``N <= 640``, ``K <= 32``, ``wind == 6``)."""
-    return bool(_lib.load().pb_auto_lbda_supported(int(n_scans), int(n_taps), int(wind)))
-
-
-def auto_lbda_split_supported(n_scans, n_taps, wind=6):
-    """Whether :func:`auto_lbda_solve_split` carries this shape (``641 <= N <= 1280``, ``K <= 32``, ``wind == 6``)."""
-    return bool(_lib.load().pb_auto_lbda_split_supported(int(n_scans), int(n_taps), int(wind)))
-
-
-def auto_lbda_long_supported(n_scans, n_taps, wind=6):
-    """Whether :func:`auto_lbda_solve_long` and :func:`auto_lbda_solve_long_pp` carry this shape (``N <= 640``,
-    ``K <= 48``, ``wind == 6``)."""
-    return bool(_lib.load().pb_auto_lbda_long_supported(int(n_scans), int(n_taps), int(wind)))
-
-
-def auto_lbda_split_long_supported(n_scans, n_taps, wind=6):
-    """Whether :func:`auto_lbda_solve_split_long` and :func:`auto_lbda_solve_split_long_pp` carry this shape
-    (``641 <= N <= 1280``, ``K <= 48``, ``wind == 6``)."""
-    return bool(_lib.load().pb_auto_lbda_split_long_supported(int(n_scans), int(n_taps), int(wind)))
-
-
-def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                    outer_chunk=0, W0=None, want_trace=True):
-    """The noise-driven lambda search of ``deconv(lbda=None)`` (pybold/bold_signal.py:99-214) for every row of ``Y``
-    as one device-resident solve (``pb_auto_lbda_d``: one voxel per wave, no host round trip, no synchronisation).
-
-    Y      float64 CUDA ``(V, N)``, ``N <= 640``;  hrf  1-D array of ``K <= 32`` taps (host);  step  ``1 / L``
-    sigma  float64 ``(V,)`` noise levels (CUDA tensor, array or scalar)
-    W0     optional float64 CUDA ``(V, N)`` warm start (not modified)
-    outer_chunk  outer iterations per launch (0: the library's choice); changes no bit of the result
-    Returns ``(W, info)``: the final iterate and a dict of CUDA tensors ``alpha``, ``lbda`` (float64 ``(V,)``),
-    ``n_outer`` (int32), ``n_inner`` (int64, inner iterations summed) and, with ``want_trace``, ``R``, ``G``, ``J``
-    (float64 ``(V, nb_iter)``, NaN from a voxel's ``n_outer`` on)."""
-    return _auto_lbda_solve("pb_auto_lbda_d", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
-                            outer_chunk, W0, want_trace)
-
-
-def auto_lbda_solve_split(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                          outer_chunk=0, W0=None, want_trace=True):
-    """:func:`auto_lbda_solve` for series of ``641 <= N <= 1280`` scans (``pb_auto_lbda_split_d``: one voxel per
-    workgroup of four waves): the same arguments, the same return value."""
-    return _auto_lbda_solve("pb_auto_lbda_split_d", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
-                            outer_chunk, W0, want_trace)
-
-
-def auto_lbda_solve_long(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                         outer_chunk=0, W0=None, want_trace=True):
-    """:func:`auto_lbda_solve` for HRFs of up to 48 taps (``pb_auto_lbda_long_d``: one voxel per wave, the taps in one
-    VGPR pair; :func:`auto_lbda_long_supported`): the same arguments, the same return value; with ``K <= 32`` the same
-    bits.  Opt-in: :func:`auto_lbda_solve` keeps its limit of 32 taps."""
-    return _auto_lbda_solve("pb_auto_lbda_long_d", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
-                            outer_chunk, W0, want_trace)
-
-
-def auto_lbda_solve_split_long(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                               outer_chunk=0, W0=None, want_trace=True):
-    """:func:`auto_lbda_solve_split` for HRFs of up to 48 taps (``pb_auto_lbda_split_long_d``: one voxel per workgroup of
-    four waves, the taps in one VGPR pair of every wave; :func:`auto_lbda_split_long_supported`): the same arguments, the
-    same return value; with ``K <= 32`` the same bits.  Opt-in: :func:`auto_lbda_solve_split` keeps its limit of 32 taps."""
-    return _auto_lbda_solve("pb_auto_lbda_split_long_d", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
-                            outer_chunk, W0, want_trace)
-
-
-def auto_lbda_solve_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                       outer_chunk=0, W0=None, want_trace=True, _entry="pb_auto_lbda_pp_d"):
-    """:func:`auto_lbda_solve` with one HRF and one step per voxel (``pb_auto_lbda_pp_d``): ``taps`` float64 CUDA
-    ``(V, K)``, ``steps`` float64 ``(V,)``; the same limits (:func:`auto_lbda_supported`), the same return value."""
-    Y = _rows(Y, torch.float64, "Y")
-    taps = _rows(taps, torch.float64, "taps")
-    if taps.shape[0] != Y.shape[0]:
-        raise ValueError("taps must have one row per voxel: %s against %s" % (tuple(taps.shape), tuple(Y.shape)))
-    steps = torch.as_tensor(steps, dtype=torch.float64).to(Y.device).contiguous().ravel()
-    if steps.numel() != Y.shape[0]:
-        raise ValueError("steps must have one entry per voxel (%d)" % Y.shape[0])
-    return _auto_lbda_solve(_entry, Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
-                            outer_chunk, W0, want_trace)
-
-
-def auto_lbda_solve_split_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                             outer_chunk=0, W0=None, want_trace=True):
-    """:func:`auto_lbda_solve_pp` for series of ``641 <= N <= 1280`` scans (``pb_auto_lbda_split_pp_d``: one voxel per
-    workgroup of four waves; :func:`auto_lbda_split_supported` answers for its shapes): the same arguments, the same
-    return value.  Opt-in: :func:`auto_lbda_solve_pp` keeps its limit of 640 scans."""
-    return auto_lbda_solve_pp(Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0,
-                              want_trace, _entry="pb_auto_lbda_split_pp_d")
-
-
-def auto_lbda_solve_long_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                            outer_chunk=0, W0=None, want_trace=True):
-    """:func:`auto_lbda_solve_pp` for HRFs of up to 48 taps (``pb_auto_lbda_long_pp_d``;
-    :func:`auto_lbda_long_supported` answers for its shapes): the same arguments, the same return value.  Opt-in:
-    :func:`auto_lbda_solve_pp` keeps its limit of 32 taps."""
-    return auto_lbda_solve_pp(Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0,
-                              want_trace, _entry="pb_auto_lbda_long_pp_d")
-
-
-def auto_lbda_solve_split_long_pp(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000,
-                                  nb_sub_iter=1000, outer_chunk=0, W0=None, want_trace=True):
-    """:func:`auto_lbda_solve_split_pp` for HRFs of up to 48 taps (``pb_auto_lbda_split_long_pp_d``;
-    :func:`auto_lbda_split_long_supported` answers for its shapes): the same arguments, the same return value.  Opt-in:
-    :func:`auto_lbda_solve_split_pp` keeps its limit of 32 taps."""
-    return auto_lbda_solve_pp(Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0,
-                              want_trace, _entry="pb_auto_lbda_split_long_pp_d")
-
-
-def _auto_lbda_solve(entry, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0, want_trace):
+def _auto_lbda_solve(entry, pp, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0, want_trace):
+    """The one body of the eight searches: ``entry`` of a row of ``F64_FORMS``; ``pp``: ``hrf`` is CUDA ``(V, K)``, ``step`` ``(V,)``."""
+    if pp:
+        Y = _rows(Y, torch.float64, "Y")
+        hrf = _rows(hrf, torch.float64, "taps")
+        if hrf.shape[0] != Y.shape[0]:
+            raise ValueError("taps must have one row per voxel: %s against %s" % (tuple(hrf.shape), tuple(Y.shape)))
+        step = torch.as_tensor(step, dtype=torch.float64).to(Y.device).contiguous().ravel()
+        if step.numel() != Y.shape[0]:
+            raise ValueError("steps must have one entry per voxel (%d)" % Y.shape[0])
     lib = _lib.load()
     Y = _rows(Y, torch.float64, "Y")
     dev = Y.device
     V, N = Y.shape
-    pp = entry in ("pb_auto_lbda_pp_d", "pb_auto_lbda_split_pp_d", "pb_auto_lbda_long_pp_d",
-                   "pb_auto_lbda_split_long_pp_d")     # hrf: CUDA (V, K), step: CUDA (V,)
     taps = None if pp else _as_taps(hrf)
     nb_iter, nb_sub_iter = int(nb_iter), int(nb_sub_iter)
-    if W0 is None:
-        W = torch.empty((V, N), dtype=torch.float64, device=dev)
-    else:
-        W = _rows(W0, torch.float64, "W0").clone()
-        if W.shape != (V, N):
-            raise ValueError("W0 must be %s, got %s" % ((V, N), tuple(W.shape)))
+    W, _ = _warm_start(W0, (V, N), dev)               # (a cold start is an argument of the searches, not a flag)
     if torch.is_tensor(sigma):
         sig = sigma.to(device=dev, dtype=torch.float64).reshape(-1)
     else:
@@ -1142,6 +1038,101 @@ def _auto_lbda_solve(entry, Y, hrf, step, sigma, early_stopping, tol, wind, nb_i
     _lib.check(rc, entry)
     return W, {"alpha": alpha, "lbda": lbda, "n_outer": n_outer, "n_inner": n_inner,
                "R": trace[0], "G": trace[1], "J": trace[2]}
+
+
+def _bind_search(entry, pp):
+    if pp:
+        def search(Y, taps, steps, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                   outer_chunk=0, W0=None, want_trace=True):
+            return _auto_lbda_solve(entry, True, Y, taps, steps, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+                                    outer_chunk, W0, want_trace)
+    else:
+        def search(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+                   outer_chunk=0, W0=None, want_trace=True):
+            return _auto_lbda_solve(entry, False, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+                                    outer_chunk, W0, want_trace)
+    return search
+
+
+def _bind_query(query, with_stop):
+    if with_stop:                                       # a solve's query: the stop rule decides too
+        def supported(n_scans, n_taps, stop=None, wind=6):
+            return bool(getattr(_lib.load(), query)(int(n_scans), int(n_taps), _STOP[stop], int(wind)))
+    else:
+        def supported(n_scans, n_taps, wind=6):
+            return bool(getattr(_lib.load(), query)(int(n_scans), int(n_taps), int(wind)))
+    return supported
+
+
+# What each public name of the family says of itself; the functions are bound below, one per name of a row's `public`.
+_F64_DOCS = {
+    "auto_lbda_solve":
+    """The noise-driven lambda search of ``deconv(lbda=None)`` (pybold/bold_signal.py:99-214) for every row of ``Y``
+    as one device-resident solve (``pb_auto_lbda_d``: one voxel per wave, no host round trip, no synchronisation).
+
+    Y      float64 CUDA ``(V, N)``, ``N <= 640``;  hrf  1-D array of ``K <= 32`` taps (host);  step  ``1 / L``
+    sigma  float64 ``(V,)`` noise levels (CUDA tensor, array or scalar)
+    W0     optional float64 CUDA ``(V, N)`` warm start (not modified)
+    outer_chunk  outer iterations per launch (0: the library's choice); changes no bit of the result
+    Returns ``(W, info)``: the final iterate and a dict of CUDA tensors ``alpha``, ``lbda`` (float64 ``(V,)``),
+    ``n_outer`` (int32), ``n_inner`` (int64, inner iterations summed) and, with ``want_trace``, ``R``, ``G``, ``J``
+    (float64 ``(V, nb_iter)``, NaN from a voxel's ``n_outer`` on).""",
+    "auto_lbda_solve_split":
+    """:func:`auto_lbda_solve` for series of ``641 <= N <= 1280`` scans (``pb_auto_lbda_split_d``: one voxel per
+    workgroup of four waves): the same arguments, the same return value.""",
+    "auto_lbda_solve_long":
+    """:func:`auto_lbda_solve` for HRFs of up to 48 taps (``pb_auto_lbda_long_d``: one voxel per wave, the taps in one
+    VGPR pair; :func:`auto_lbda_long_supported`): the same arguments, the same return value; with ``K <= 32`` the same
+    bits.  Opt-in: :func:`auto_lbda_solve` keeps its limit of 32 taps.""",
+    "auto_lbda_solve_split_long":
+    """:func:`auto_lbda_solve_split` for HRFs of up to 48 taps (``pb_auto_lbda_split_long_d``: one voxel per workgroup of
+    four waves, the taps in one VGPR pair of every wave; :func:`auto_lbda_split_long_supported`): the same arguments, the
+    same return value; with ``K <= 32`` the same bits.  Opt-in: :func:`auto_lbda_solve_split` keeps its limit of 32 taps.""",
+    "auto_lbda_solve_pp":
+    """:func:`auto_lbda_solve` with one HRF and one step per voxel (``pb_auto_lbda_pp_d``): ``taps`` float64 CUDA
+    ``(V, K)``, ``steps`` float64 ``(V,)``; the same limits (:func:`auto_lbda_supported`), the same return value.""",
+    "auto_lbda_solve_split_pp":
+    """:func:`auto_lbda_solve_pp` for series of ``641 <= N <= 1280`` scans (``pb_auto_lbda_split_pp_d``: one voxel per
+    workgroup of four waves; :func:`auto_lbda_split_supported` answers for its shapes): the same arguments, the same
+    return value.  Opt-in: :func:`auto_lbda_solve_pp` keeps its limit of 640 scans.""",
+    "auto_lbda_solve_long_pp":
+    """:func:`auto_lbda_solve_pp` for HRFs of up to 48 taps (``pb_auto_lbda_long_pp_d``;
+    :func:`auto_lbda_long_supported` answers for its shapes): the same arguments, the same return value.  Opt-in:
+    :func:`auto_lbda_solve_pp` keeps its limit of 32 taps.""",
+    "auto_lbda_solve_split_long_pp":
+    """:func:`auto_lbda_solve_split_pp` for HRFs of up to 48 taps (``pb_auto_lbda_split_long_pp_d``;
+    :func:`auto_lbda_split_long_supported` answers for its shapes): the same arguments, the same return value.  Opt-in:
+    :func:`auto_lbda_solve_split_pp` keeps its limit of 32 taps.""",
+    "pp_split_supported":
+    """Whether :func:`fista_solve_pp_d` with ``force="split"`` carries this shape (``pb_fista_pp_split_supported``:
+    ``641 <= N <= 1280``, ``K <= 32``, the window rule at ``wind == 6``).""",
+    "long_hrf_supported":
+    """Whether :func:`fista_solve` (float64 ``Y``) and :func:`fista_solve_pp_d` with ``force="long_hrf"`` carry this
+    shape (``pb_fista_long_hrf_supported``: ``N <= 640``, ``K <= 48``, the window rule at ``wind == 6``).""",
+    "split_long_hrf_supported":
+    """Whether :func:`fista_solve` (float64 ``Y``) and :func:`fista_solve_pp_d` with ``force="split_long_hrf"`` carry this
+    shape (``pb_fista_split_long_hrf_supported``: ``641 <= N <= 1280``, ``K <= 48``, the window rule at ``wind == 6``).""",
+    "auto_lbda_supported":
+    """Whether :func:`auto_lbda_solve` and :func:`auto_lbda_solve_pp` carry this shape (``pb_auto_lbda_supported``:
+    ``N <= 640``, ``K <= 32``, ``wind == 6``).""",
+    "auto_lbda_split_supported":
+    """Whether :func:`auto_lbda_solve_split` and :func:`auto_lbda_solve_split_pp` carry this shape
+    (``pb_auto_lbda_split_supported``: ``641 <= N <= 1280``, ``K <= 32``, ``wind == 6``).""",
+    "auto_lbda_long_supported":
+    """Whether :func:`auto_lbda_solve_long` and :func:`auto_lbda_solve_long_pp` carry this shape
+    (``pb_auto_lbda_long_supported``: ``N <= 640``, ``K <= 48``, ``wind == 6``).""",
+    "auto_lbda_split_long_supported":
+    """Whether :func:`auto_lbda_solve_split_long` and :func:`auto_lbda_solve_split_long_pp` carry this shape
+    (``pb_auto_lbda_split_long_supported``: ``641 <= N <= 1280``, ``K <= 48``, ``wind == 6``)."""}
+
+for _form in F64_FORMS.values():
+    for _name, _fn in zip(_form.public, (_bind_search(_form.search, False), _bind_search(_form.search_pp, True),
+                                         _form.solve_query and _bind_query(_form.solve_query, True),
+                                         _bind_query(_form.search_query, False))):
+        if _name:
+            _fn.__name__ = _fn.__qualname__ = _name
+            _fn.__doc__ = _F64_DOCS[_name]
+            globals()[_name] = _fn
 
 
 def inf_norm_rows(X):
@@ -1366,21 +1357,8 @@ def fista_solve_grouped(Y, taps, steps, offsets, lbda, n_iter, W0=None, force=No
     steps = steps.to(device=dev, dtype=torch.float64).contiguous().ravel()
     if steps.numel() != G:
         raise ValueError("steps must have one entry per parcel")
-    cold = 0
-    if W0 is None:
-        W = torch.empty((V, N), dtype=torch.float64, device=dev)
-        cold = PB_FLAG_COLD_START
-    else:
-        W = _rows(W0, torch.float64, "W0")
-        if not inplace or W.data_ptr() != W0.data_ptr():
-            W = W.clone()
-        if W.shape != (V, N):
-            raise ValueError("W0 must be %s, got %s" % ((V, N), tuple(W.shape)))
-    lbda_dev, lbda_scalar = None, 0.0
-    if np.ndim(lbda) == 0 and not torch.is_tensor(lbda):
-        lbda_scalar = float(lbda)
-    else:
-        lbda_dev = torch.as_tensor(lbda, dtype=torch.float64).to(dev).contiguous().ravel()
+    W, cold = _warm_start(W0, (V, N), dev, inplace)
+    lbda_scalar, lbda_dev = _lbda_arg(lbda, dev)
     betas = _betas_on(dev, n_iter)
     n_done = torch.empty((V,), dtype=torch.int32, device=dev)
     need = int(lib.pb_fista_grouped_work_len(V, G, K))

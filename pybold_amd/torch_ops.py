@@ -8,6 +8,8 @@ import os
 
 import torch
 
+from . import solver
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 OPS_PATH = os.path.join(_HERE, "libpybold_torch_ops.so")
 _loaded = False
@@ -28,7 +30,6 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop_mode=0, 
     """The same contract as :func:`pybold_amd.solver.fista_solve` through ``torch.ops.pybold_hip.fista_solve``
     (scalar ``lbda``); returns ``(W, J or None, n_done)``."""
     import numpy as np
-    from . import solver
     ops = load()
     dev = Y.device
     taps = torch.from_numpy(np.ascontiguousarray(np.asarray(hrf, dtype=np.float64).ravel()))
@@ -47,40 +48,8 @@ def fista_solve(Y, hrf, lbda, step, n_iter, W0=None, want_J=False, stop_mode=0, 
     return W, J, n_done
 
 
-def auto_lbda_solve(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                    outer_chunk=0, W0=None, want_trace=True):
-    """The same contract as :func:`pybold_amd.solver.auto_lbda_solve` through ``torch.ops.pybold_hip.auto_lbda_solve``."""
-    return _auto_lbda_solve("auto_lbda_solve", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
-                            outer_chunk, W0, want_trace)
-
-
-def auto_lbda_solve_split(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                          outer_chunk=0, W0=None, want_trace=True):
-    """The same contract as :func:`pybold_amd.solver.auto_lbda_solve_split` through
-    ``torch.ops.pybold_hip.auto_lbda_solve_split``."""
-    return _auto_lbda_solve("auto_lbda_solve_split", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
-                            outer_chunk, W0, want_trace)
-
-
-def auto_lbda_solve_long(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                         outer_chunk=0, W0=None, want_trace=True):
-    """The same contract as :func:`pybold_amd.solver.auto_lbda_solve_long` through
-    ``torch.ops.pybold_hip.auto_lbda_solve_long``."""
-    return _auto_lbda_solve("auto_lbda_solve_long", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
-                            outer_chunk, W0, want_trace)
-
-
-def auto_lbda_solve_split_long(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
-                               outer_chunk=0, W0=None, want_trace=True):
-    """The same contract as :func:`pybold_amd.solver.auto_lbda_solve_split_long` through
-    ``torch.ops.pybold_hip.auto_lbda_solve_split_long``."""
-    return _auto_lbda_solve("auto_lbda_solve_split_long", Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter,
-                            nb_sub_iter, outer_chunk, W0, want_trace)
-
-
 def _auto_lbda_solve(op, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter, outer_chunk, W0, want_trace):
     import numpy as np
-    from . import solver
     ops = load()
     dev = Y.device
     taps = torch.from_numpy(np.ascontiguousarray(np.asarray(hrf, dtype=np.float64).ravel()))
@@ -92,6 +61,20 @@ def _auto_lbda_solve(op, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter
         torch.as_tensor(sigma, dtype=torch.float64).to(dev).contiguous().ravel(), bool(early_stopping), float(tol),
         int(wind), int(nb_iter), int(nb_sub_iter), int(outer_chunk), R, G, J)
     return W, {"alpha": alpha, "lbda": lbda, "n_outer": n_outer, "n_inner": n_inner, "R": R, "G": G, "J": J}
+
+
+def _bind_search(op, like):
+    def search(Y, hrf, step, sigma, early_stopping=True, tol=1.0e-6, wind=6, nb_iter=1000, nb_sub_iter=1000,
+               outer_chunk=0, W0=None, want_trace=True):
+        return _auto_lbda_solve(op, Y, hrf, step, sigma, early_stopping, tol, wind, nb_iter, nb_sub_iter,
+                                outer_chunk, W0, want_trace)
+    search.__name__ = search.__qualname__ = op
+    search.__doc__ = "The same contract as :func:`pybold_amd.solver.%s` through ``torch.ops.pybold_hip.%s``." % (like, op)
+    return search
+
+
+for _form in solver.F64_FORMS.values():                # auto_lbda_solve, _split, _long, _split_long: one per form's operator
+    globals()[_form.op] = _bind_search(_form.op, _form.public.search)
 
 
 def mad_daub_noise_est(Y, c=0.6744):
