@@ -238,7 +238,9 @@ __device__ __forceinline__ void normal_eq_sum_body(const double* z, int64_t ldz,
       __syncthreads();
       double woff = 0.0;
       for (int i = 0; i < wid; ++i) woff += red8[i];
-      double run = woff + incl - local;
+      double excl = __shfl_up(incl, 1, 64);        // (the chunks before this one: earlier elements only, as block_cumsum)
+      if (lane == 0) excl = 0.0;
+      double run = woff + excl;
       for (int i = lo; i < hi2; ++i) {
         run += lz[ne_sk(i)];
         lz[ne_sk(i)] = run;
@@ -483,7 +485,9 @@ __device__ __forceinline__ void normal_eq_wave_body(const double* z, int64_t ldz
 #pragma unroll
       for (int g4 = 0; g4 < GEN_WAVES; ++g4) {
         const int lo = (g4 * 64 + lane) * chunk, hi2 = min(lo + chunk, N);
-        double run = woff + incl[g4] - local[g4];
+        double excl = __shfl_up(incl[g4], 1, 64);  // (the chunks before this one: earlier elements only, as block_cumsum)
+        if (lane == 0) excl = 0.0;
+        double run = woff + excl;
         if (inreg) {
 #pragma unroll
           for (int c = 0; c < CH; ++c) {

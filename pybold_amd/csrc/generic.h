@@ -54,7 +54,12 @@ __device__ __forceinline__ void block_cumsum(const double* src, double* dst, int
   __syncthreads();
   double woff = 0.0;
   for (int i = 0; i < wid; ++i) woff += red[i];
-  double run = woff + incl - local;
+  // the total of the chunks before this one, from the neighbour's inclusive total: a sum of EARLIER elements only.
+  // (woff + incl - local rounds at the size of the thread's own chunk, which a prefix that ends before it does not
+  // warrant: a small running sum in front of a large element lost its low bits)
+  double excl = __shfl_up(incl, 1, 64);
+  if (lane == 0) excl = 0.0;
+  double run = woff + excl;
   __syncthreads();
   // dst may alias src: a thread reads an element of its own chunk right before
   // it overwrites it and never touches another thread's chunk

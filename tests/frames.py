@@ -336,3 +336,112 @@ def hrf_normal_eq_w(w, y, K, work, out):
         rc = lib.pb_hrf_normal_eq_w(w.ptr, w.ld, y.ptr, y.ld, w.rows, w.cols, int(K), work.ptr, work.n, out.ptr,
                                     solver._stream_ptr(dev))
     _lib.check(rc, "pb_hrf_normal_eq_w")
+
+
+# ---- the row-in-LDS helpers (tests/test_gpu_helper_kernels.py) -----------------------------------------------------------
+def _taps_dev(taps, dev):
+    """Taps as a packed device vector; None (the two scans take none) passes as a null pointer."""
+    if taps is None:
+        return None, 0, 0
+    t = _taps(taps, dev)[1]
+    return t, t.data_ptr(), t.numel()
+
+
+def _op(name, x, out, n_in, n_out, taps):
+    """pb_conv / pb_corr / pb_op_forward / pb_op_adjoint: x and out are Frame2D float64 of the same number of rows."""
+    lib, _lib, solver = _env()
+    dev = x.buf.device
+    keep, ptr, K = _taps_dev(taps, dev)
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(x.ptr, x.ld, out.ptr, out.ld, x.rows, int(n_in), int(n_out), ptr, K, solver._stream_ptr(dev))
+    _lib.check(rc, name)
+
+
+def _integ(name, x, out):
+    lib, _lib, solver = _env()
+    dev = x.buf.device
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(x.ptr, x.ld, out.ptr, out.ld, x.rows, x.cols, solver._stream_ptr(dev))
+    _lib.check(rc, name)
+
+
+def integ_op(x, out):
+    _integ("pb_integ_op", x, out)
+
+
+def integ_adj(x, out):
+    _integ("pb_integ_adj", x, out)
+
+
+def conv(x, out, hrf):
+    """x: n_in columns, out: n_out columns."""
+    _op("pb_conv", x, out, x.cols, out.cols, hrf)
+
+
+def corr(r, out, hrf):
+    """r: n_out columns (the range of the Toeplitz matrix), out: n_in columns."""
+    _op("pb_corr", r, out, out.cols, r.cols, hrf)
+
+
+def op_forward(x, out, hrf):
+    _op("pb_op_forward", x, out, x.cols, out.cols, hrf)
+
+
+def op_adjoint(r, out, hrf):
+    _op("pb_op_adjoint", r, out, out.cols, r.cols, hrf)
+
+
+def _hrf_cost(base, z, y, taps, K, n_hrf, cost):
+    lib, _lib, solver = _env()
+    dev = z.buf.device
+    name = base + ("_d" if y.dtype == torch.float64 else "")
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(z.ptr, z.ld, y.ptr, y.ld, z.rows, z.cols, taps.ptr, int(K), int(n_hrf), cost.ptr,
+                                solver._stream_ptr(dev))
+    _lib.check(rc, name)
+
+
+def hrf_cost(z, y, taps, K, n_hrf, cost):
+    """pb_hrf_cost (float32 y) or pb_hrf_cost_d: taps a Frame1D of n_hrf * K packed taps, cost a Frame1D of n_hrf * V."""
+    _hrf_cost("pb_hrf_cost", z, y, taps, K, n_hrf, cost)
+
+
+def hrf_cost_pv(z, y, taps, K, n_hrf, cost):
+    """pb_hrf_cost_pv (float32 y) or pb_hrf_cost_pv_d: taps a Frame1D of n_hrf * V * K packed taps."""
+    _hrf_cost("pb_hrf_cost_pv", z, y, taps, K, n_hrf, cost)
+
+
+def gram_frobenius(taps, K, N, out):
+    """taps: Frame2D [P][ldt] float64, out: Frame1D of P."""
+    lib, _lib, solver = _env()
+    dev = taps.buf.device
+    with torch.cuda.device(dev):
+        rc = lib.pb_gram_frobenius(taps.ptr, taps.ld, taps.rows, int(K), int(N), out.ptr, solver._stream_ptr(dev))
+    _lib.check(rc, "pb_gram_frobenius")
+
+
+def spectral_radius(x0, taps, nb_iter, tol, out):
+    """x0, taps: Frame1D float64; out: Frame1D of 2 (norm, steps)."""
+    lib, _lib, solver = _env()
+    dev = x0.buf.device
+    with torch.cuda.device(dev):
+        rc = lib.pb_spectral_radius(x0.ptr, x0.n, taps.ptr, taps.n, int(nb_iter), float(tol), out.ptr, solver._stream_ptr(dev))
+    _lib.check(rc, "pb_spectral_radius")
+
+
+def spectral_radius_pp(x0, taps, K, nb_iter, tol, out):
+    """x0: Frame2D [V][ldx], taps: Frame2D [V][ldt], out: Frame1D of 2 V."""
+    lib, _lib, solver = _env()
+    dev = x0.buf.device
+    with torch.cuda.device(dev):
+        rc = lib.pb_spectral_radius_pp(x0.ptr, x0.ld, x0.rows, x0.cols, taps.ptr, taps.ld, int(K), int(nb_iter), float(tol),
+                                       out.ptr, solver._stream_ptr(dev))
+    _lib.check(rc, "pb_spectral_radius_pp")
+
+
+def inf_norm(x, out):
+    lib, _lib, solver = _env()
+    dev = x.buf.device
+    with torch.cuda.device(dev):
+        rc = lib.pb_inf_norm(x.ptr, x.ld, out.ptr, out.ld, x.rows, x.cols, solver._stream_ptr(dev))
+    _lib.check(rc, "pb_inf_norm")
