@@ -88,6 +88,15 @@ enum { PB_FLAG_MFMA_DENSE_TILES = 4194304 };
 /* And bit 23, an enumerator as well: pb_fista_solve_grouped only: series of 311 .. 1 280 scans with up to 48 taps may run on the
  * split matrix-pipe forms, one unit of 16 rows per workgroup (OPT-IN; see pb_fista_solve_grouped and pb_fista_grouped_route). */
 enum { PB_FLAG_GROUPED_SPLIT = 8388608 };
+/* Bits 24 and 25, enumerators too.  A partitioned call (pb_fista_solve with 4 096 problems or more, pb_fista_solve_ex with a
+ * workspace) of 129 .. 320 scans and up to 33 taps, plain solve, one-wave matrix-pipe main form, runs the dense rows that the
+ * whole rounds leave on fista_mfma_row_kernel (one series per wave on the matrix pipe, csrc/fista_mfma_row.h) instead of
+ * fista_fast_kernel (one per wave on the vector pipe).  PB_FLAG_VECTOR_LEFTOVERS turns that off: the vector kernel takes the
+ * whole range as before.  For A/B runs and as a fallback.
+ * PB_FLAG_FORCE_MFMA_ROW: pb_fista_solve / _ex run EVERY row on fista_mfma_row_kernel alone, in place, no partition and no
+ * re-solve: rows its guards hand back keep n_done = -1 and their w untouched.  PB_ERR_INVALID outside 129 .. 320 scans,
+ * 1 .. 33 taps, plain solve without cost trace, n_done_dev given.  For tests and measurements. */
+enum { PB_FLAG_VECTOR_LEFTOVERS = 16777216, PB_FLAG_FORCE_MFMA_ROW = 33554432 };
 #define PB_FLAG_ONE_LAUNCH 32u    /* never split a plain solve into a full-rounds launch and a
                                      remainder launch (see pb_fista_solve) */
 
@@ -190,6 +199,8 @@ int pb_fista_plan_ex(int N, int K, int P, int stop_mode, int wind, unsigned flag
  *   <= 128       <= 32     (a)                  (a) certificate          (a)                   two problems per row / single row
  *   129 .. 310   <= 33     (b)                  (b) certificate          (b) in full           fista_mfma_kernel, one wave per 16 problems
  *   129 .. 310   34 .. 48  (b)                  (b) from 225 scans on    (b) from 225 scans on ... with three near tiles (stop rules: split form)
+ *   129 .. 310   <= 33     (b) plain only, taps from the host: the dense rows that the whole rounds of a partitioned call leave (config 3: 1 696 of 100 000):   fista_mfma_row_kernel, ONE series per wave
+ *                          (behind the one-problem-per-wave launches of the plan; PB_FLAG_VECTOR_LEFTOVERS: those rows on (a), one problem per wave, as before; the plan queries do not report it)
  *   129 .. 310   <= 33     (b) one HRF per parcel, rows contiguous by parcel (pb_fista_solve_grouped, plain only):   the same kernels, a wave's 16 problems of one parcel; other shapes: (a), per problem
  *   311 .. 1280  <= 48     (b) one HRF per parcel, OPT-IN with PB_FLAG_GROUPED_SPLIT (pb_fista_solve_grouped, plain only):           fista_mfma2_kernel (up to 640 scans) / fista_mfma4_kernel, a workgroup's 16 problems of one parcel; without the flag: (a), per problem
  *   311 .. 640   <= 33     (b)                  (b) certificate          (b) in full           fista_mfma2_kernel, two waves per 16 problems

@@ -35,6 +35,8 @@ PB_FLAG_PP_SPLIT = 1048576           # pb_fista_solve_pp_d only: the four-wave p
 PB_FLAG_MFMA_DENSE_TILES = 4194304   # one-wave matrix-pipe form: the dense near tiles instead of the 2:4-sparse joined tile
 PB_FLAG_LONG_HRF = 2097152     # pb_fista_solve_d / pb_fista_solve_pp_d: the 48-tap one-wave register form (opt-in), or an error
 PB_FLAG_GROUPED_SPLIT = 8388608      # pb_fista_solve_grouped only: 311 .. 1 280 scans, up to 48 taps on the split matrix-pipe forms (opt-in)
+PB_FLAG_VECTOR_LEFTOVERS = 16777216  # partitioned calls: the dense rows whole rounds leave stay on the vector kernel (A/B, fallback)
+PB_FLAG_FORCE_MFMA_ROW = 33554432    # every row on fista_mfma_row_kernel alone, no re-solve (tests, measurements)
 PB_PATH_DENSE_RATIO = 0.19         # include/pybold_hip.h (series of up to 310 scans; 0.22 beyond)
 PB_STOP_NONE = 0
 PB_STOP_LOOPS = 1

@@ -23,6 +23,7 @@
 #include "blind.h"
 #include "fista_mfma.h"
 #include "fista_mfma_sparse.h"
+#include "fista_mfma_row.h"
 #include "fista_mfma_grouped.h"
 #include "grouped.h"
 #include "fista_mfma2.h"
@@ -131,12 +132,15 @@ bool stream_is_capturing(hipStream_t st) {
 // ---- workspace of a partitioned solve (int32 units) -----------------------------------------------------------
 //   [0, P) the lists   [P] length of the front list   [P+1, P+1+nblk) block counts   ranges of the three lists'
 //   candidate launches   lambda_max of every series (float64, when the caller has none)
-struct WorkLayout { int64_t ranges, lmax, total; };
+//   ... then, for each of the three one-problem-per-wave candidates, three words s0 <= mid <= s1: its range cut at the end of
+//   the dense class (path.h: path_scan_kernel) -- [s0, mid) for fista_mfma_row_kernel, [mid, s1) for the vector kernel
+struct WorkLayout { int64_t ranges, split, lmax, total; };
 WorkLayout work_layout(int P, int V) {
   const int64_t nblk = ((int64_t)P + pb::PATH_PER_BLOCK - 1) / pb::PATH_PER_BLOCK;
   WorkLayout w;
   w.ranges = ((int64_t)P + 2 + 2 * nblk + 8 + 1) & ~(int64_t)1;   // (list, n_front, front / ill counts per block, n_ill: path.h)
-  w.lmax = w.ranges + 3 * 2 * pb::CAND_COUNT + 4;           // (3 x candidate ranges + the ill range; even: 8-byte aligned when the buffer is)
+  w.split = w.ranges + 3 * 2 * pb::CAND_COUNT + 4;          // (3 x candidate ranges + the ill range)
+  w.lmax = w.split + 3 * pb::WIDE_CANDS + 3;                // (even: 8-byte aligned when the buffer is)
   w.total = w.lmax + 2 * (int64_t)V + 8;
   return w;
 }
@@ -513,7 +517,7 @@ int cand_bound(const Route& r, int c, int P) {
 // a whole list: its candidates in their static order, the side-stream ones forked after the whole rounds
 template <class LF>
 int solve_list(const Route& r, const pb::FistaArgs& a, const LF& lf, hipStream_t user, Side& side, const int32_t* work_dev,
-               const int32_t* ranges, int list, bool exact_rule) {
+               const int32_t* ranges, int list, bool exact_rule, const int32_t* split = nullptr, const double* taps_host = nullptr) {
   pb::FistaArgs b = a;
   b.perm = work_dev;
   b.n_dense = work_dev + a.P;
@@ -529,7 +533,19 @@ int solve_list(const Route& r, const pb::FistaArgs& a, const LF& lf, hipStream_t
     if (c >= pb::CAND_FIRST_AFTER_FORK && side.ss) rc = side.fork(user, lf.name);
     if (rc != PB_OK) break;
     b.range = ranges + 2 * c;
-    rc = launch(lf, form, b, (pb::cand_side(c) && side.ss) ? side.ss->stream : user, exact_rule);
+    const hipStream_t st = (pb::cand_side(c) && side.ss) ? side.ss->stream : user;
+    if (split && form == FORM_WIDE) {
+      // the dense rows of this range, [s0, mid), one series per wave on the matrix pipe (fista_mfma_row.h); the vector
+      // kernel right behind it, launched as ever, with what is left of the range
+      const int32_t* cut = split + 3 * pb::wide_cand_index(c);
+      b.range = cut;
+      rc = pb::launch_mfma_row(b, taps_host, a.K, false, st) != 0
+               ? fail(PB_ERR_INVALID, "%s: fista_mfma_row_kernel rejected its launch", lf.name)
+               : check_launch("fista_mfma_row_kernel");
+      if (rc != PB_OK) break;                      // (the join below still runs)
+      b.range = cut + 1;
+    }
+    rc = launch(lf, form, b, st, exact_rule);
   }
   const int rj = side.join(user, lf.name);
   return rj != PB_OK ? rj : rc;
@@ -554,10 +570,10 @@ void launch_lmax_pass(const pb::FistaArgs& a, int V_series, const double* taps_h
 
 // count, scan (which also plans the lists: plan_kernel's work on thread 0) and scatter of one class predicate
 int launch_partition(const pb::ClassPred& cp, int P, int32_t* work_dev, const pb::PlanSpec& front, const pb::PlanSpec& back,
-                     int32_t* rg_front, int32_t* rg_back, int32_t* rg_ill, const char* what, hipStream_t st) {
+                     int32_t* rg_front, int32_t* rg_back, int32_t* rg_ill, const char* what, hipStream_t st, int32_t* rg_split = nullptr) {
   const int nblk = (P + pb::PATH_PER_BLOCK - 1) / pb::PATH_PER_BLOCK;
   hipLaunchKernelGGL(pb::path_count_kernel, dim3(nblk), dim3(pb::PATH_THREADS), 0, st, cp, P, work_dev);
-  hipLaunchKernelGGL(pb::path_scan_kernel, dim3(1), dim3(pb::PATH_THREADS), 0, st, P, nblk, work_dev, front, back, rg_front, rg_back, rg_ill);
+  hipLaunchKernelGGL(pb::path_scan_kernel, dim3(1), dim3(pb::PATH_THREADS), 0, st, P, nblk, work_dev, front, back, rg_front, rg_back, rg_ill, rg_split);
   hipLaunchKernelGGL(pb::path_scatter_kernel, dim3(nblk), dim3(pb::PATH_THREADS), 0, st, cp, P, work_dev);
   return check_launch(what);
 }
@@ -599,14 +615,23 @@ int run_partition(const Route& r, const pb::FistaArgs& a, const LF& lf, hipStrea
                        : N > 640 ? PB_PATH_DENSE_RATIO_LONGER : (N > MFMA1_NMAX ? PB_PATH_DENSE_RATIO_LONG : PB_PATH_DENSE_RATIO);
   pb::PlanSpec front = sp.dense;
   front.merged = 1;
+  // What the whole rounds leave of the dense class runs one series per wave on the matrix pipe instead of the vector pipe
+  // (fista_mfma_row.h) where that kernel has the shape: a plain solve of 129 .. 320 scans with up to 33 taps from the host,
+  // the one-wave matrix-pipe form as the call's main form.  The plan is not touched: each one-problem-per-wave candidate's
+  // range is cut at the end of the dense class, on the device, into spare words of the workspace.
+  const bool row_leftovers = r.path == PATH_PART_SHORT && r.mfma && !(flags & PB_FLAG_VECTOR_LEFTOVERS) && taps_host &&
+                             N >= pb::ROW_NMIN && N <= pb::ROW_NMAX && K <= pb::ROW_KMAX && a.stop_mode == PB_STOP_NONE && !a.J &&
+                             !a.taps_pp && a.n_done;
+  int32_t* rg_split = row_leftovers ? work_dev + wl.split : nullptr;
   int rc = launch_partition(pb::ClassPred{a.lbda_vec, a.lbda, lmax, a.y_rep, ratio, nullptr}, P, work_dev, front, sp.sparse, rg_dense,
-                            rg_sparse, rg_ill, "partition", user);
+                            rg_sparse, rg_ill, "partition", user, rg_split);
   if (rc != PB_OK) return rc;
   Side side;
   if (!one_stream) side.take();
   // ONE list for the call: positions [0, P) of the list array (dense problems first), one plan (plan.h: plan_partitioned)
   const bool only_dense = (flags & PB_FLAG_ONLY_DENSE) != 0, only_sparse = (flags & PB_FLAG_ONLY_SPARSE) != 0;   // (measurement aids)
-  rc = solve_list(r, a, lf, user, side, work_dev, rg_dense, only_dense ? 1 : (only_sparse ? 2 : 0), false);
+  rc = solve_list(r, a, lf, user, side, work_dev, rg_dense, only_dense ? 1 : (only_sparse ? 2 : 0), false,
+                  (only_dense || only_sparse) ? nullptr : rg_split, taps_host);
   if (rc != PB_OK || only_dense || only_sparse) return rc;
   if (ill_exact || ill_generic) {                // (its workgroups stride over the list, which is empty for ordinary data)
     pb::FistaArgs b = a;
@@ -751,6 +776,14 @@ static int solve_impl(const float* y_dev, int64_t ldy, int y_rep, double* w_dev,
     if (v >= 8 && v <= 15) a.ybits = v;
   }
 #endif
+  if (flags & PB_FLAG_FORCE_MFMA_ROW) {           // every row on fista_mfma_row_kernel alone, in place (tests, measurements)
+    if (N < pb::ROW_NMIN || N > pb::ROW_NMAX || K > pb::ROW_KMAX || J_dev || stop_mode != PB_STOP_NONE || !n_done_dev)
+      return fail(PB_ERR_INVALID, "pb_fista_solve: PB_FLAG_FORCE_MFMA_ROW serves plain solves of %d .. %d scans with up to %d taps, "
+                  "no cost trace, n_done_dev given (N=%d K=%d stop=%d)", pb::ROW_NMIN, pb::ROW_NMAX, pb::ROW_KMAX, N, K, stop_mode);
+    if (pb::launch_mfma_row(a, taps_host, K, false, (hipStream_t)stream) != 0)
+      return fail(PB_ERR_INVALID, "pb_fista_solve: fista_mfma_row_kernel rejected its launch");
+    return check_launch("fista_mfma_row_kernel");
+  }
   const int V_series = (P + y_rep - 1) / y_rep;
   // (PB_FLAG_FORCE_MFMA without the caller's lambda_max: "everything on the matrix pipe", unpartitioned)
   const bool workspace = work_dev && work_len >= work_layout(P, V_series).total && !((flags & PB_FLAG_FORCE_MFMA) && !lmax_dev);

@@ -97,7 +97,8 @@ __device__ __forceinline__ void plan_call(const PlanSpec& front, const PlanSpec&
 
 // ... and, once the total is known, the launch plans of the two lists (thread 0: plan.h's planners on the list lengths)
 __global__ __launch_bounds__(PATH_THREADS) void path_scan_kernel(int P, int nblk, int32_t* work, PlanSpec front, PlanSpec back,
-                                                                  int32_t* ranges_front, int32_t* ranges_back, int32_t* range_ill) {
+                                                                  int32_t* ranges_front, int32_t* ranges_back, int32_t* range_ill,
+                                                                  int32_t* ranges_split = nullptr) {
   __shared__ int buf[PATH_THREADS];
   __shared__ int carry;
   int total[2] = {0, 0};
@@ -133,6 +134,17 @@ __global__ __launch_bounds__(PATH_THREADS) void path_scan_kernel(int P, int nblk
     else {
       if (ranges_front) plan_list(front, n_front, ranges_front);
       if (ranges_back) plan_list(back, P_eff - n_front, ranges_back);
+    }
+    // every one-problem-per-wave candidate's range [s0, s1) cut at the end of the dense class (positions below n_front of
+    // the list array): s0 <= mid <= s1 in three words, [s0, mid) for fista_mfma_row_kernel, [mid, s1) for the vector kernel
+    if (ranges_split && ranges_front) {
+      for (int k = 0; k < WIDE_CANDS; ++k) {
+        const int s0 = ranges_front[2 * wide_cand(k)], s1 = ranges_front[2 * wide_cand(k) + 1];
+        const int mid = n_front < s0 ? s0 : (n_front > s1 ? s1 : n_front);
+        ranges_split[3 * k] = s0;
+        ranges_split[3 * k + 1] = mid;
+        ranges_split[3 * k + 2] = s1;
+      }
     }
   }
 }

@@ -269,6 +269,10 @@ PB_HD int cand_form(int c) {
          : (c == CAND_FAST0 || c == CAND_FAST1 || c == CAND_SIDE_FAST) ? FORM_FAST1 : FORM_WIDE;
 }
 PB_HD bool cand_side(int c) { return c >= CAND_FIRST_SIDE; }
+// the one-problem-per-wave candidates, numbered (capi.hip keeps three words per such candidate: its range cut in two)
+constexpr int WIDE_CANDS = 3;
+PB_HD int wide_cand(int k) { return k == 0 ? CAND_WIDE : (k == 1 ? CAND_SIDE_WIDE0 : CAND_SIDE_WIDE1); }
+PB_HD int wide_cand_index(int c) { return c == CAND_WIDE ? 0 : (c == CAND_SIDE_WIDE0 ? 1 : 2); }
 
 // the most slots candidate c can be given in a plan of at most n_max problems: what the host sizes its grid for
 // (tests/test_host_logic.py checks every plan against these bounds)

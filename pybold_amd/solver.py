@@ -62,7 +62,11 @@ _FORCE = {None: 0, "generic": PB_FLAG_FORCE_GENERIC, "fast": PB_FLAG_FORCE_FAST,
           # "gsplit_mfma": every unit on them, one launch; "gsplit_mfmaonly": ... and no re-solve of what the guards hand back
           "gsplit": _lib.PB_FLAG_GROUPED_SPLIT,
           "gsplit_mfma": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | _lib.PB_FLAG_GROUPED_SPLIT,
-          "gsplit_mfmaonly": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | _lib.PB_FLAG_GROUPED_SPLIT | _lib.PB_FLAG_CERT_NO_RESOLVE}
+          "gsplit_mfmaonly": PB_FLAG_ONE_LAUNCH | _lib.PB_FLAG_FORCE_MFMA | _lib.PB_FLAG_GROUPED_SPLIT | _lib.PB_FLAG_CERT_NO_RESOLVE,
+          # "mfma_row": every row on the one-series-per-wave matrix-pipe kernel alone (129 .. 320 scans, up to 33 taps, plain
+          # solves; rows its guards hand back keep n_done = -1, no re-solve); "vector_leftovers": library dispatch without that
+          # kernel -- what whole rounds leave of the dense class stays on the vector kernel (A/B runs, fallback)
+          "mfma_row": _lib.PB_FLAG_FORCE_MFMA_ROW, "vector_leftovers": _lib.PB_FLAG_VECTOR_LEFTOVERS}
 
 # The float64 register family, one row per form: what Python has to know of `kF64[]` (csrc/dispatch.h).  No limit
 # of a form stands here -- the `*_supported` queries ask the library.  `force`: the name that asks a float64 solve for the form;
