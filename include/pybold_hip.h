@@ -920,6 +920,59 @@ int pb_hrf_normal_eq_w_grouped(const double* w_dev, int64_t ldw, const float* y_
                                int N, int K, int G, const int32_t* offsets_host, const int32_t* offsets_dev,
                                double* work_dev, int64_t work_len, double* out_dev, int64_t ldo, void* stream);
 
+/*
+ * The conditioning guard of the solves whose HRF lives in DEVICE memory (opt-in: the plain entry points above enqueue
+ * what they always did).  A series that the operator H = K_h . cumsum barely sees -- alternating signs, period-2..6
+ * carriers, high-pass noise, an ordinary signal under such a carrier -- loses digits in every arithmetic narrower than
+ * float64 (up to 4e-4 on the matrix pipe, 5e-3 on the float32 vector forms).  The guard classes every row on the
+ * coherence gamma_2 = lambda_max / (||y||_2 sum|c| / sqrt(N)), c = cumsum(h), h the row's own HRF, into three classes:
+ *   mark 2   gamma_2 < 1e-2: solved on a float64 kernel with per-problem taps (register-resident where the shape has
+ *            an entry -- up to 1 280 scans and 48 taps --, else the any-size LDS kernel);
+ *   mark 1   gamma_2 < 7e-2 / 3e-2 / 2e-2 (up to 310 scans or 34+ taps / up to 640 scans / beyond): kept off the matrix
+ *            pipe -- solved on the float32 vector form of the route's own re-solves.  Only where the call's route puts
+ *            rows on a matrix-pipe form; elsewhere such rows run on the vector forms as it is;
+ *   mark 0   everything else (an all-zero series too): the plain call's answer, bit for bit.
+ * These are the bounds of the partitioned pb_fista_solve_ex route, compared in the same form.
+ *
+ * pb_conditioning_marks    marks_dev[p] (int32) = the class of row p of y_dev for the HRF taps_dev + r(p) * ldt:
+ *                     r(p) = p (one HRF per row), ldt = 0 (one for all rows), or, with offsets_dev (int32 [G + 1],
+ *                     device memory, as for pb_fista_solve_grouped), the parcel of p.  Up to 64 taps and 1 344 scans.
+ *                     One wave per row, float32; launches one kernel on `stream`.
+ * pb_fista_guard_supported  host-only: the float64 kernel a guarded call of this shape and stop rule (PB_STOP_NONE /
+ *                     _LOOPS) re-solves mark-2 rows on -- 1 one wave per row (up to 640 scans, 32 taps), 2 four waves
+ *                     (641 .. 1 280 scans), 3 / 4 the same for 33 .. 48 taps, 5 the LDS kernel -- or 0: no guard (more
+ *                     than 64 taps or 1 344 scans, nothing fits); a guarded call then still succeeds, with no row marked.
+ * pb_fista_guard_work_len   int32 words of the guard's work buffer for P rows of N scans (smaller with
+ *                     PB_FLAG_COLD_START in flags: no warm start is saved).  Layout: csrc/guard.h; after a call
+ *                     work[1] = rows solved in float64, work[3] = rows re-solved on the vector form.
+ * pb_fista_solve_pp_guarded   the arguments of pb_fista_solve_pp plus the guard's work buffer (8-byte aligned);
+ *                     n_done_dev is required.  On the caller's stream, without host synchronisation (a call can be
+ *                     captured into a graph): the marks pass, the two lists, the warm start of the listed rows saved;
+ *                     the main solve exactly as pb_fista_solve_pp enqueues it, over all rows; the saved rows put
+ *                     back; the two lists solved again in place.  n_done of a re-solved row is what its kernel reports.
+ * pb_fista_solve_grouped_guarded   the same around pb_fista_solve_grouped: its arguments (work_dev / work_len its own
+ *                     work buffer), then the guard's buffer.  The re-solves read the per-row taps and steps of the
+ *                     grouped work buffer.
+ */
+int pb_conditioning_marks(const float* y_dev, int64_t ldy, int P, int N, const double* taps_dev, int64_t ldt, int K,
+                          const int32_t* offsets_dev, int G, int32_t* marks_dev, void* stream);
+int pb_fista_guard_supported(int N, int K, int stop_mode);
+/* host-only: 1 when the route of pb_fista_solve_pp for this call (shared: ldt = 0; n_done_dev given) puts rows on a
+ * matrix-pipe form -- the calls whose guarded form builds the mark-1 list --, else 0 */
+int pb_fista_pp_has_matrix_pipe(int N, int K, int P, int shared, int stop_mode, unsigned flags);
+int64_t pb_fista_guard_work_len(int P, int N, unsigned flags);
+int pb_fista_solve_pp_guarded(const float* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int P, int N,
+                              const double* taps_dev, int64_t ldt, int K, const double* step_dev,
+                              double lbda, const double* lbda_dev, const double* betas_dev, int n_iter,
+                              int stop_mode, double tol, int32_t* n_done_dev, int32_t* work_dev, int64_t work_len,
+                              unsigned flags, void* stream);
+int pb_fista_solve_grouped_guarded(const float* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int P, int N,
+                                   const double* taps_dev, int64_t ldt, int K, const double* step_dev, int G,
+                                   const int32_t* offsets_host, const int32_t* offsets_dev, double lbda,
+                                   const double* lbda_dev, const double* betas_dev, int n_iter, int32_t* n_done_dev,
+                                   int32_t* work_dev, int64_t work_len, int32_t* guard_work_dev, int64_t guard_work_len,
+                                   unsigned flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,24 @@ SIGNATURES = {
     "pb_hrf_normal_eq_w_grouped_work_len": (_c_i64, [_c_int, _c_int, _c_int]),
     "pb_hrf_normal_eq_w_grouped": (_c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr,
                                             _ptr, _c_i64, _ptr, _c_i64, _ptr]),
+    # opt-in: the conditioning guard of the solves whose HRF lives in device memory (csrc/guard.h)
+    "pb_conditioning_marks": (_c_int, [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_i64, _c_int,     # y, ldy, P, N, taps_dev, ldt, K
+                                       _ptr, _c_int, _ptr, _ptr]),                             # offsets_dev, G, marks_dev, stream
+    "pb_fista_guard_supported": (_c_int, [_c_int, _c_int, _c_int]),
+    "pb_fista_pp_has_matrix_pipe": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_uint]),
+    "pb_fista_guard_work_len": (_c_i64, [_c_int, _c_int, ctypes.c_uint]),
+    "pb_fista_solve_pp_guarded": (_c_int, [
+        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int,     # y, ldy, w, ldw, P, N
+        _ptr, _c_i64, _c_int, _ptr,                     # taps_dev, ldt, K, step_dev
+        _c_dbl, _ptr, _ptr, _c_int,                     # lbda, lbda_dev, betas_dev, n_iter
+        _c_int, _c_dbl, _ptr, _ptr, _c_i64,             # stop_mode, tol, n_done, work_dev, work_len
+        ctypes.c_uint, _ptr]),                          # flags, stream
+    "pb_fista_solve_grouped_guarded": (_c_int, [
+        _ptr, _c_i64, _ptr, _c_i64, _c_int, _c_int,     # y, ldy, w, ldw, P, N
+        _ptr, _c_i64, _c_int, _ptr, _c_int,             # taps_dev, ldt, K, step_dev, G
+        _ptr, _ptr, _c_dbl, _ptr, _ptr, _c_int,         # offsets_host, offsets_dev, lbda, lbda_dev, betas_dev, n_iter
+        _ptr, _ptr, _c_i64, _ptr, _c_i64,               # n_done, work_dev, work_len, guard_work_dev, guard_work_len
+        ctypes.c_uint, _ptr]),                          # flags, stream
 }
 
 _lib = None

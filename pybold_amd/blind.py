@@ -65,7 +65,7 @@ def fit_dilations_grid(Z, Y, t_r, hrf_dur, bounds, n_grid=17, n_refine=9):
 
 
 def bd_batch(Y, t_r, lbda=1.0, theta_0=None, z_0=None, hrf_dur=20.0, bounds=None, nb_iter=100,
-             early_stopping=False, wind=4, tol=1.0e-12, verbose=0):
+             early_stopping=False, wind=4, tol=1.0e-12, verbose=0, guard=None):
     """``bd`` for a batch: ``Y`` float32 CUDA ``(V, N)``.  Same outer structure and
     cost bookkeeping as the reference (z-step with ``nb_iter`` inner iterations as
     at :324, theta-step, normalised ``J``/``r`` and raw ``g`` per outer iteration,
@@ -73,9 +73,14 @@ def bd_batch(Y, t_r, lbda=1.0, theta_0=None, z_0=None, hrf_dur=20.0, bounds=None
     per-voxel HRFs ``(V, K)`` and ``d`` with ``'J'``, ``'r'``, ``'g'`` as
     ``(nb_iter + 2, V)`` arrays and ``'theta'`` ``(V,)``.  ``lbda`` and ``theta_0`` may
     hold one value per voxel.  With ``early_stopping=False`` and ``verbose=0`` the whole loop
-    runs without a single host synchronisation."""
+    runs without a single host synchronisation.  ``guard`` (opt-in; ``None``: the environment
+    variable ``PYBOLD_AMD_PP_GUARD``, ``"1"`` is on): every z-step through the conditioning guard of
+    :func:`pybold_amd.solver.fista_solve_pp`; ``d['guard']`` then holds the counts of the last z-step,
+    ``{'float64': n, 'vector': n}``, read after the loop."""
     dev = Y.device
     V, n = Y.shape
+    guard = solver.pp_guard_opt_in(guard)
+    guard_work = solver.guard_work_buffer(V, n, dev) if guard else None
     if bounds is None:
         bounds = [(MIN_DELTA + 1.0e-1, MAX_DELTA - 1.0e-1)]
     if theta_0 is not None and (torch.is_tensor(theta_0) or np.ndim(theta_0) > 0):
@@ -115,7 +120,7 @@ def bd_batch(Y, t_r, lbda=1.0, theta_0=None, z_0=None, hrf_dur=20.0, bounds=None
         # without early stopping every voxel advances: iterate in place, no host sync at all
         Wn, _ = solver.fista_solve_pp(Y, taps, steps, lbda, int(nb_iter), W0=W,
                                       stop="loops" if early_stopping else None, tol=tol,
-                                      inplace=not early_stopping)
+                                      inplace=not early_stopping, guard_work=guard_work, guard=guard)
         return Wn
 
     def record(W, taps, eps, r=None):
@@ -159,4 +164,6 @@ def bd_batch(Y, t_r, lbda=1.0, theta_0=None, z_0=None, hrf_dur=20.0, bounds=None
     X, Z = record(W, taps, 0.0)
     d = {"J": torch.stack(J).cpu().numpy(), "r": torch.stack(R).cpu().numpy(),
          "g": torch.stack(G).cpu().numpy(), "l_alpha": [], "theta": theta.cpu().numpy()}
+    if guard:
+        d["guard"] = solver.guard_counts(guard_work)
     return X, Z, W, taps, d

@@ -30,6 +30,7 @@
 #include "fista_mfma4.h"
 #include "fista_mfma_split_grouped.h"
 #include "path.h"
+#include "guard.h"
 #include "dispatch.h"
 
 namespace {
@@ -1591,6 +1592,253 @@ int pb_fista_solve_grouped(const float* y_dev, int64_t ldy, double* w_dev, int64
   if (r.fe) return launch(lf, FORM_FAST1, b, user, true);
   if (r.we) return launch(lf, FORM_WIDE, b, user, true);
   return fail(PB_ERR_INVALID, "pb_fista_solve_grouped: no vector form re-solves N=%d K=%d", N, K);
+}
+
+// ---- the conditioning guard of the solves whose HRF lives in device memory (opt-in: the _guarded entry points) ------------
+// The marks pass (path.h: marks_wave_kernel) classes every row on gamma_2 with the bounds of the partitioned route; the rows
+// with mark 2 (and, where the call's route has a matrix-pipe form, mark 1) are listed on the device (guard.h), their warm
+// start saved; the main solve is enqueued by the plain entry point itself, over all rows; then the listed rows get their
+// warm start back and are solved again in place, mark 1 on the float32 vector form of the route's own re-solves, mark 2 on a
+// float64 kernel with per-problem taps.  Everything on the caller's stream, nothing read on the host.
+}  // extern "C"
+namespace {
+void launch_marks(const float* y, int64_t ldy, int P, int N, const double* taps, int64_t ldt, int K, const int32_t* offsets, int G,
+                  int32_t* marks, hipStream_t st) {
+  const float g64 = (float)PART_GAMMA_F64, gv = (float)part_gamma_matrix_pipe(N, K);
+  const dim3 grid((unsigned)((P + 3) / 4)), block(256);
+  if (N <= 320)
+    hipLaunchKernelGGL((pb::marks_wave_kernel<5>), grid, block, 4 * (64 * 5 + 2 * pb::LMAX_KT) * sizeof(float), st, y, ldy, P, N, taps,
+                       ldt, K, offsets, G, g64, gv, marks);
+  else if (N <= 640)
+    hipLaunchKernelGGL((pb::marks_wave_kernel<10>), grid, block, 4 * (64 * 10 + 2 * pb::LMAX_KT) * sizeof(float), st, y, ldy, P, N, taps,
+                       ldt, K, offsets, G, g64, gv, marks);
+  else
+    hipLaunchKernelGGL((pb::marks_wave_kernel<21>), grid, block, 4 * (64 * 21 + 2 * pb::LMAX_KT) * sizeof(float), st, y, ldy, P, N, taps,
+                       ldt, K, offsets, G, g64, gv, marks);
+}
+static_assert(pb::MARKS_KMAX == pb::LMAX_KT, "one tap limit for the two marks passes");
+
+// the float64 kernel that re-solves the rows with mark 2 (per-problem taps, float32 y): code 1 the one-wave register form,
+// 2 four waves, 3 / 4 the same for HRFs of 33 .. 48 taps, 5 the LDS kernel; 0: the shape has none, or the marks pass does
+// not carry it (more than 64 taps or 1 344 scans) -- no guard
+struct GuardKernel { int code; const ExactEntry* e; };
+GuardKernel guard_kernel(int N, int K, int stop_mode) {
+  if (N < 1 || N > pb::MARKS_NMAX || K < 1 || K > pb::MARKS_KMAX) return {0, nullptr};
+  if (stop_mode != PB_STOP_NONE && stop_mode != PB_STOP_LOOPS) return {0, nullptr};
+  static const int forms[4] = {F64_ONE_WAVE, F64_FOUR_WAVES, F64_LONG_HRF, F64_FOUR_WAVES_LONG_HRF};
+  for (int i = 0; i < 4; ++i) {
+    const ExactEntry* e = pick_f64(forms[i], N, K, stop_mode, F64_WIND);
+    if (e) return {i + 1, e};
+  }
+  return {gen_lds_doubles(N, K, stop_mode, 0) <= LDS_DOUBLES_MAX ? 5 : 0, nullptr};
+}
+
+struct GuardCall {
+  const char* name;
+  int32_t* work;
+  pb::GuardLayout gl;
+  GuardKernel gk;
+  bool want_vec, cold;
+  hipStream_t st;
+};
+int guard_work_check(const char* name, int P, int N, unsigned flags, const int32_t* work_dev, int64_t work_len) {
+  const pb::GuardLayout gl = pb::guard_layout(P, N, (flags & PB_FLAG_COLD_START) != 0);
+  if (!work_dev || work_len < gl.total || (reinterpret_cast<uintptr_t>(work_dev) & 7) != 0)
+    return fail(PB_ERR_INVALID, "%s: guard work buffer must hold %lld int32 words (pb_fista_guard_work_len), 8-byte aligned", name,
+                (long long)gl.total);
+  return PB_OK;
+}
+// what pb_fista_solve_pp would refuse once its route is known (checked before the guard's first launch)
+int pp_route_check(const char* name, const Route& r, int N, int K, int stop_mode, unsigned flags) {
+  if (r.path != PATH_GENERIC) return PB_OK;
+  if (flags & PB_FLAG_FORCE_FAST) return fail(PB_ERR_INVALID, "%s: no register-resident kernel for N=%d K=%d", name, N, K);
+  if (gen_lds_doubles(N, K, stop_mode, 0) > LDS_DOUBLES_MAX) return fail(PB_ERR_INVALID, "%s: N=%d K=%d exceeds LDS", name, N, K);
+  return PB_OK;
+}
+// a route of pb_fista_solve_pp puts rows on a matrix-pipe form: whole passes of a split form, or a piece of the plan of the
+// single-row entry's forms
+bool pp_route_has_pipe(const Route& r, int P, unsigned flags) {
+  if (r.path == PATH_SPLIT_LONG) return r.base > 0;
+  if (r.path != PATH_PIECES || !r.mfma || r.one_form) return false;
+  Piece pc[pb::MAX_PIECES];
+  const int npc = route_pieces(r, P, (flags & PB_FLAG_ONE_LAUNCH) != 0, true, pc);
+  bool pipe = false;
+  for (int i = 0; i < npc; ++i) pipe |= pc[i].form == FORM_MFMA || pc[i].form == FORM_MFMA2;
+  return pipe;
+}
+// a call without a guard (no float64 kernel for the shape, too many taps): the header says "no row listed"
+int guard_none(const GuardCall& g) {
+  if (hipMemsetAsync(g.work, 0, pb::GUARD_HEADER * sizeof(int32_t), g.st) != hipSuccess)
+    return fail(PB_ERR_HIP, "%s: clearing the guard header failed", g.name);
+  return PB_OK;
+}
+// before the main solve: marks, lists, the warm start of the listed rows
+int guard_before(const GuardCall& g, const float* y, int64_t ldy, double* w, int64_t ldw, int P, int N, const double* taps, int64_t ldt,
+                 int K, const int32_t* offsets_dev, int G) {
+  launch_marks(y, ldy, P, N, taps, ldt, K, offsets_dev, G, g.work + g.gl.marks, g.st);
+  pb::launch_mark_lists(P, g.want_vec ? 1 : 0, g.work, g.gl, g.st);
+  if (!g.cold) pb::launch_rows_move(true, P, N, w, ldw, g.work, g.gl, g.st);
+  return check_launch(g.name);
+}
+// after it: the warm start back, then the two lists in place.  `b`: the call's arguments with per-problem (or shared, ldt = 0)
+// taps and steps; `lf`, `vec_form`: the float32 vector form of the route's own re-solves
+template <class LF>
+int guard_after(const GuardCall& g, const pb::FistaArgs& a, const LF& lf, int vec_form) {
+  const int P = a.P;
+  if (!g.cold) pb::launch_rows_move(false, P, a.N, a.w, a.ldw, g.work, g.gl, g.st);
+  int rc = check_launch(g.name);
+  if (rc != PB_OK) return rc;
+  pb::FistaArgs b = a;
+  b.perm_side = 3;
+  b.grid_slots = P;
+  if (g.want_vec) {
+    b.perm = g.work + g.gl.listv;
+    b.range = g.work + 2;
+    rc = launch(lf, vec_form, b, g.st, true);
+    if (rc != PB_OK) return rc;
+  }
+  b.perm = g.work + g.gl.list64;
+  b.range = g.work;
+  if (g.gk.e) {
+    if (a.step_shared) {                          // (the float64 register kernels read step_vec[p])
+      double* steps = reinterpret_cast<double*>(g.work + g.gl.steps);
+      pb::launch_steps_fill(a.step_vec, steps, P, g.st);
+      b.step_vec = steps;
+      b.step_shared = 0;
+    }
+    if (g.gk.e->fn_pp(b, false, a.stop_mode, g.st) != 0)
+      return fail(PB_ERR_INVALID, "%s: float64 kernel rejected the launch (ill-conditioned series)", g.name);
+  } else {
+    launch_generic(b, a.taps_pp, a.K, 0, false, false, P < 2048 ? P : 2048, g.st);
+  }
+  return check_launch("float64 kernel (ill-conditioned series)");
+}
+}  // namespace
+extern "C" {
+
+int64_t pb_fista_guard_work_len(int P, int N, unsigned flags) {
+  return (P >= 0 && N >= 1) ? pb::guard_layout(P, N, (flags & PB_FLAG_COLD_START) != 0).total : 0;
+}
+
+int pb_fista_guard_supported(int N, int K, int stop_mode) { return guard_kernel(N, K, stop_mode).code; }
+
+int pb_fista_pp_has_matrix_pipe(int N, int K, int P, int shared, int stop_mode, unsigned flags) {
+  if (P < 1 || N < 1 || K < 1) return 0;
+  return pp_route_has_pipe(route_pp(N, K, P, shared != 0, stop_mode, true, flags), P, flags) ? 1 : 0;
+}
+
+int pb_conditioning_marks(const float* y_dev, int64_t ldy, int P, int N, const double* taps_dev, int64_t ldt, int K,
+                          const int32_t* offsets_dev, int G, int32_t* marks_dev, void* stream) {
+  if (P < 0 || N < 1 || N > pb::MARKS_NMAX || K < 1 || K > pb::MARKS_KMAX)
+    return fail(PB_ERR_INVALID, "pb_conditioning_marks: bad size (P=%d N=%d K=%d; up to %d scans and %d taps)", P, N, K, pb::MARKS_NMAX,
+                pb::MARKS_KMAX);
+  if (ldy < N || (ldt != 0 && ldt < K)) return fail(PB_ERR_INVALID, "pb_conditioning_marks: leading dimension too small");
+  if (offsets_dev && G < 1) return fail(PB_ERR_INVALID, "pb_conditioning_marks: offsets given for G=%d parcels", G);
+  if (P == 0) return PB_OK;
+  if (!y_dev || !taps_dev || !marks_dev) return fail(PB_ERR_INVALID, "pb_conditioning_marks: NULL pointer");
+  launch_marks(y_dev, ldy, P, N, taps_dev, ldt, K, offsets_dev, G, marks_dev, (hipStream_t)stream);
+  return check_launch("pb_conditioning_marks");
+}
+
+int pb_fista_solve_pp_guarded(const float* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int P, int N,
+                              const double* taps_dev, int64_t ldt, int K, const double* step_dev,
+                              double lbda, const double* lbda_dev, const double* betas_dev, int n_iter,
+                              int stop_mode, double tol, int32_t* n_done_dev, int32_t* work_dev, int64_t work_len,
+                              unsigned flags, void* stream) {
+  static const char* const name = "pb_fista_solve_pp_guarded";
+  if (P < 0 || N < 1 || K < 1 || n_iter < 0)
+    return fail(PB_ERR_INVALID, "%s: bad size (P=%d N=%d K=%d n_iter=%d)", name, P, N, K, n_iter);
+  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 problems per launch", name);
+  if (ldy < N || ldw < N || (ldt != 0 && ldt < K)) return fail(PB_ERR_INVALID, "%s: leading dimension too small", name);
+  if (P == 0) return PB_OK;
+  if (!y_dev || !w_dev || !taps_dev || !step_dev || (n_iter > 0 && !betas_dev)) return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
+  if (!n_done_dev) return fail(PB_ERR_INVALID, "%s: n_done_dev is required", name);
+  if (stop_mode != PB_STOP_NONE && stop_mode != PB_STOP_LOOPS)
+    return fail(PB_ERR_INVALID, "%s: stop_mode must be PB_STOP_NONE or PB_STOP_LOOPS", name);
+  int rc = guard_work_check(name, P, N, flags, work_dev, work_len);
+  if (rc != PB_OK) return rc;
+  const Route r = route_pp(N, K, P, ldt == 0, stop_mode, true, flags);
+  rc = pp_route_check(name, r, N, K, stop_mode, flags);
+  if (rc != PB_OK) return rc;
+  GuardCall g{name, work_dev, pb::guard_layout(P, N, (flags & PB_FLAG_COLD_START) != 0), guard_kernel(N, K, stop_mode), false,
+              (flags & PB_FLAG_COLD_START) != 0, (hipStream_t)stream};
+  if (!g.gk.code) {
+    rc = guard_none(g);
+    return rc != PB_OK ? rc : pb_fista_solve_pp(y_dev, ldy, w_dev, ldw, P, N, taps_dev, ldt, K, step_dev, lbda, lbda_dev, betas_dev,
+                                                n_iter, stop_mode, tol, n_done_dev, flags, stream);
+  }
+  // the vector list is needed where the route puts rows on the matrix pipe
+  g.want_vec = pp_route_has_pipe(r, P, flags);
+  const int vec_form = (r.path == PATH_SPLIT_LONG && r.backup_wide) ? FORM_WIDE : FORM_FAST1;
+  rc = guard_before(g, y_dev, ldy, w_dev, ldw, P, N, taps_dev, ldt, K, nullptr, 0);
+  if (rc != PB_OK) return rc;
+  rc = pb_fista_solve_pp(y_dev, ldy, w_dev, ldw, P, N, taps_dev, ldt, K, step_dev, lbda, lbda_dev, betas_dev, n_iter, stop_mode, tol,
+                         n_done_dev, flags, stream);
+  if (rc != PB_OK) return rc;
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, 1, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, stop_mode, tol, n_done_dev, flags);
+  a.y = y_dev; a.taps_pp = taps_dev; a.ldt = ldt; a.step_vec = step_dev; a.step_shared = (ldt == 0);
+  return guard_after(g, a, DeviceTapsForms{r, name, K, stop_mode}, vec_form);
+}
+
+int pb_fista_solve_grouped_guarded(const float* y_dev, int64_t ldy, double* w_dev, int64_t ldw, int P, int N,
+                                   const double* taps_dev, int64_t ldt, int K, const double* step_dev, int G,
+                                   const int32_t* offsets_host, const int32_t* offsets_dev, double lbda,
+                                   const double* lbda_dev, const double* betas_dev, int n_iter, int32_t* n_done_dev,
+                                   int32_t* work_dev, int64_t work_len, int32_t* guard_work_dev, int64_t guard_work_len,
+                                   unsigned flags, void* stream) {
+  static const char* const name = "pb_fista_solve_grouped_guarded";
+  if (P < 0 || N < 1 || K < 1 || n_iter < 0 || G < 0)
+    return fail(PB_ERR_INVALID, "%s: bad size (P=%d N=%d K=%d n_iter=%d G=%d)", name, P, N, K, n_iter, G);
+  if (P > (1 << 25)) return fail(PB_ERR_INVALID, "%s: more than 2^25 problems per launch", name);
+  if (ldy < N || ldw < N || ldt < K) return fail(PB_ERR_INVALID, "%s: leading dimension too small", name);
+  if (!pb::grouped_offsets_ok(offsets_host, G, P))
+    return fail(PB_ERR_INVALID, "%s: offsets must run 0 = offsets[0] <= ... <= offsets[G] = P (host memory)", name);
+  if (P == 0) return PB_OK;
+  if (!y_dev || !w_dev || !taps_dev || !step_dev || !offsets_dev || !work_dev || (n_iter > 0 && !betas_dev))
+    return fail(PB_ERR_INVALID, "%s: NULL pointer", name);
+  if (!n_done_dev) return fail(PB_ERR_INVALID, "%s: n_done_dev is required", name);
+  const GroupedWork wl = grouped_work(P, G, K);
+  if (work_len < wl.total || (reinterpret_cast<uintptr_t>(work_dev) & 7) != 0)
+    return fail(PB_ERR_INVALID, "%s: work buffer must hold %lld int32 words (pb_fista_grouped_work_len), 8-byte aligned", name,
+                (long long)wl.total);
+  int rc = guard_work_check(name, P, N, flags, guard_work_dev, guard_work_len);
+  if (rc != PB_OK) return rc;
+  const GroupedRoute gr = route_grouped(offsets_host, G, P, N, K, flags, true);
+  if (gr.code < 0) return fail(PB_ERR_INVALID, "%s: no matrix-pipe form for N=%d K=%d under these flags", name, N, K);
+  const unsigned vector_flags = flags & ~(PB_FLAG_FORCE_MFMA | PB_FLAG_NO_MFMA | PB_FLAG_GROUPED_SPLIT);
+  if (gr.code == 0) {
+    rc = pp_route_check(name, route_pp(N, K, P, false, PB_STOP_NONE, true, vector_flags), N, K, PB_STOP_NONE, vector_flags);
+    if (rc != PB_OK) return rc;
+  }
+  const hipStream_t user = (hipStream_t)stream;
+  GuardCall g{name, guard_work_dev, pb::guard_layout(P, N, (flags & PB_FLAG_COLD_START) != 0), guard_kernel(N, K, PB_STOP_NONE),
+              gr.code > 0, (flags & PB_FLAG_COLD_START) != 0, user};
+  // the float32 vector form of the plain call's re-solve of handed-back rows
+  const Route rv = route_pp(N, K, gr.code > 0 ? gr.row_cut : P, false, PB_STOP_NONE, true, 0u);
+  if (g.gk.code && g.want_vec && !rv.fe && !rv.we) g.gk.code = 0;
+  if (!g.gk.code) {
+    rc = guard_none(g);
+    return rc != PB_OK ? rc : pb_fista_solve_grouped(y_dev, ldy, w_dev, ldw, P, N, taps_dev, ldt, K, step_dev, G, offsets_host,
+                                                     offsets_dev, lbda, lbda_dev, betas_dev, n_iter, n_done_dev, work_dev, work_len,
+                                                     flags, stream);
+  }
+  rc = guard_before(g, y_dev, ldy, w_dev, ldw, P, N, taps_dev, ldt, K, offsets_dev, G);
+  if (rc != PB_OK) return rc;
+  rc = pb_fista_solve_grouped(y_dev, ldy, w_dev, ldw, P, N, taps_dev, ldt, K, step_dev, G, offsets_host, offsets_dev, lbda, lbda_dev,
+                              betas_dev, n_iter, n_done_dev, work_dev, work_len, flags, stream);
+  if (rc != PB_OK) return rc;
+  // every row's copy of its parcel's taps and step in the grouped workspace: written by the plain call unless its main form
+  // carried every row and the caller asked for no re-solve
+  double* taps_rows = reinterpret_cast<double*>(work_dev + wl.taps);
+  double* step_rows = reinterpret_cast<double*>(work_dev + wl.steps);
+  if (gr.code > 0 && (flags & PB_FLAG_CERT_NO_RESOLVE) && gr.row_cut >= P) {
+    const int units = pb::grouped_table(offsets_host, G, P, pb::GROUPED_WAVE_ROWS, nullptr, nullptr);
+    hipLaunchKernelGGL(pb::grouped_expand_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, user, work_dev + wl.table,
+                       work_dev + wl.first + G, taps_dev, ldt, K, step_dev, taps_rows, step_rows);
+  }
+  pb::FistaArgs a = fista_args(P, N, K, n_iter, 1, ldy, w_dev, ldw, 0.0, lbda, lbda_dev, betas_dev, PB_STOP_NONE, 0.0, n_done_dev, flags);
+  a.y = y_dev; a.taps_pp = taps_rows; a.ldt = K; a.step_vec = step_rows; a.step_shared = 0;
+  return guard_after(g, a, DeviceTapsForms{rv, name, K, PB_STOP_NONE}, rv.fe ? FORM_FAST1 : FORM_WIDE);
 }
 
 int64_t pb_hrf_normal_eq_w_grouped_work_len(int V, int G, int K) {

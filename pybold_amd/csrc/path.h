@@ -298,4 +298,91 @@ __global__ __launch_bounds__(256) void lmax_wave_kernel(const float* y, int64_t 
   if (lane == 0) out[v] = (m > 0.0f && m < f64_bound * yn) ? -(double)m : ((m < vec_bound * yn) ? 0.0 : (double)m);
 }
 
+// ---- the same pass with the taps in DEVICE memory, for the solves whose HRF lives there (pb_fista_solve_pp, one HRF for all
+// rows or one per row; pb_fista_solve_grouped, one per parcel): the wave reads its HRF from taps + row * ldt (ldt = 0: one
+// for all; `offsets` given: row = the parcel of v, found by bisection of the G + 1 offsets), keeps it in LDS as float32,
+// and computes the unit sum_{t < N} |c[t]| / sqrt(N), c = cumsum(h), itself -- a wave scan over the K <= 64 taps, c[t] =
+// c[K - 1] beyond them.  It writes a class, not a number: marks[v] = 2 where gamma_2 < gamma_f64 (float64 kernels), 1 where
+// gamma_2 < gamma_vec (off the matrix pipe), else 0, in the comparison form of lmax_wave_kernel (m < bound * unit * ||y||),
+// so that the two guards class a series alike; an all-zero series is 0.  Instantiated by capi.hip (launch_marks), like lmax_wave_kernel.
+template <int SL>
+__global__ __launch_bounds__(256) void marks_wave_kernel(const float* y, int64_t ldy, int V, int N, const double* taps, int64_t ldt,
+                                                         int K, const int32_t* offsets, int G, float gamma_f64, float gamma_vec,
+                                                         int32_t* marks) {
+  extern __shared__ float lm_smem[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int v = blockIdx.x * 4 + wv;
+  if (v >= V) return;                                      // (wave-level synchronisation only below)
+  float* s = lm_smem + wv * (64 * SL + 2 * LMAX_KT);
+  float* hs = s + 64 * SL + LMAX_KT;                       // the wave's taps, zeros from K on
+  int row = v;
+  if (offsets) {                                           // largest g in [0, G) with offsets[g] <= v
+    int lo = 0, hi = G > 0 ? G - 1 : 0;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (offsets[mid] <= v) lo = mid; else hi = mid - 1;
+    }
+    row = lo;
+  }
+  const double* tp = taps + (int64_t)row * ldt;
+  const float hv = lane < K ? (float)tp[lane] : 0.0f;
+  float c = hv;                                            // c[lane] = h[0] + ... + h[lane]
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float t = __shfl_up(c, o, 64);
+    c += lane >= o ? t : 0.0f;
+  }
+  const int kn = K < N ? K : N;
+  float csum = lane < kn ? fabsf(c) : 0.0f;
+  const float ctot = __shfl(c, 63, 64);                    // = c[K - 1]
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) csum += __shfl_xor(csum, o, 64);
+  csum += (float)(N - kn) * fabsf(ctot);
+  const float unit = csum / __builtin_sqrtf((float)N);
+  const float* yrow = y + (int64_t)v * ldy;
+  float loc[SL];
+  float run = 0.0f, ysq = 0.0f;
+#pragma unroll
+  for (int j = SL - 1; j >= 0; --j) {
+    const int t = lane * SL + j;
+    const float yv = t < N ? yrow[t] : 0.0f;
+    ysq = fmaf(yv, yv, ysq);
+    run += yv;
+    loc[j] = run;                                          // suffix sums inside the strip
+  }
+  float above = run;                                       // exclusive suffix over the lanes above
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float t = __shfl_down(above, o, 64);
+    above += (lane + o < 64) ? t : 0.0f;
+  }
+  above -= run;
+#pragma unroll
+  for (int j = 0; j < SL; ++j) s[lane * SL + j] = loc[j] + above;
+  s[64 * SL + lane] = 0.0f;                                // past the end: zeros
+  hs[lane] = hv;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  float acc[SL];
+#pragma unroll
+  for (int j = 0; j < SL; ++j) acc[j] = 0.0f;
+  for (int k0 = 0; k0 < K; k0 += 8) {                      // eight taps per round (taps beyond K are zero), SL independent chains
+    float hk[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) hk[q] = hs[k0 + q];
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+#pragma unroll
+      for (int j = 0; j < SL; ++j) acc[j] = fmaf(hk[q], s[lane * SL + j + k0 + q], acc[j]);
+  }
+  float m = 0.0f;
+#pragma unroll
+  for (int j = 0; j < SL; ++j) m = fmaxf(m, lane * SL + j < N ? fabsf(acc[j]) : 0.0f);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { m = fmaxf(m, __shfl_xor(m, o, 64)); ysq += __shfl_xor(ysq, o, 64); }
+  const float yn = __builtin_sqrtf(ysq);
+  if (lane == 0) marks[v] = (m > 0.0f && m < gamma_f64 * unit * yn) ? 2 : ((m < gamma_vec * unit * yn) ? 1 : 0);
+}
+
 }  // namespace pb

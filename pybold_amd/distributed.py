@@ -122,18 +122,24 @@ class HipOps:
         from . import solver
         self.s, self.t_r, self.hrf_dur, self.n = solver, t_r, hrf_dur, n
         self.work = None
+        self.guard_work = None                  # the conditioning guard's buffer: allocated by the first guarded z-step
 
     def hrf(self, theta):                       # (1,) -> (K,)
         return self.s.spm_hrf_batch(theta, self.t_r, self.hrf_dur)[0]
 
-    def z_step(self, Y, taps, lbda, nb_inner, W, step=None, last=True):
+    def z_step(self, Y, taps, lbda, nb_inner, W, step=None, last=True, guard=None):
         """``last=False``: an intermediate z-step of the outer loop -- the matrix-pipe kernel keeps its
         result also where the iterate is still tiny against the threshold (its accuracy guard would
-        send those voxels to the vector kernels; the next, warm-started z-step forgets such errors)."""
+        send those voxels to the vector kernels; the next, warm-started z-step forgets such errors).
+        ``guard`` (opt-in; ``None``: ``PYBOLD_AMD_PP_GUARD``): the conditioning guard of
+        :func:`pybold_amd.solver.fista_solve_pp` around the solve, its counts in ``self.guard_work``."""
         if step is None:
             step = 1.0 / self.s.gram_frobenius_batch(taps.reshape(1, -1), self.n)    # (1,)
+        guard = self.s.pp_guard_opt_in(guard)
+        if guard and (self.guard_work is None or self.guard_work.numel() < self.s.guard_work_len(Y.shape[0], Y.shape[1])):
+            self.guard_work = self.s.guard_work_buffer(Y.shape[0], Y.shape[1], Y.device)
         W, _ = self.s.fista_solve_pp(Y, taps, step, lbda, nb_inner, W0=W, inplace=True,
-                                     force=None if last else "intermediate")
+                                     force=None if last else "intermediate", guard_work=self.guard_work, guard=guard)
         return W
 
     def normal_eq(self, W, Y, K):
@@ -155,10 +161,12 @@ class HipOps:
         return self.s.theta_fit_step(msg, self.t_r, self.hrf_dur, bounds, self.n, lbda)
 
 
-def _bd_shared_device_loop(Y, t_r, lbda, theta0, hrf_dur, bounds, nb_iter, nb_inner, comm, ops):
+def _bd_shared_device_loop(Y, t_r, lbda, theta0, hrf_dur, bounds, nb_iter, nb_inner, comm, ops, guard=False):
     """The outer loop of :func:`bd_shared` with the theta-step on the device: enqueues everything on the current
     stream and returns device tensors only -- ``(W, taps, thetas [nb_iter + 1 tensors (1,)], costs [nb_iter + 1])``.
-    No host synchronisation, so the whole loop can be captured into one HIP graph (:class:`BdSharedGraph`)."""
+    No host synchronisation, so the whole loop can be captured into one HIP graph (:class:`BdSharedGraph`).
+    ``guard``: every z-step through the conditioning guard (the switch is resolved by the caller, once per loop; with it
+    off the z-steps are called exactly as before)."""
     dev = Y.device
     V, n = Y.shape
     theta = torch.full((1,), theta0, dtype=torch.float64, device=dev)
@@ -170,8 +178,12 @@ def _bd_shared_device_loop(Y, t_r, lbda, theta0, hrf_dur, bounds, nb_iter, nb_in
     thetas, costs = [theta], []
     fused = bool(getattr(ops, "fused", False))
     step = None                                  # fused: 1 / ||A^T A||_F comes out of the theta step
+    # (HipOps.z_step would read the environment itself: it is told the loop's decision; a substitute for it or an override
+    # of it -- the CPU oracle of the multi-rank test, a test's own z-step -- sees the keyword only when the guard is on)
+    gkw = {"guard": bool(guard)} if (guard or getattr(type(ops), "z_step", None) is HipOps.z_step) else {}
     for it in range(nb_iter + 1):
-        W = ops.z_step(Y, taps, lbda, nb_inner, W, step, last=(it == nb_iter)) if fused else ops.z_step(Y, taps, lbda, nb_inner, W)
+        W = (ops.z_step(Y, taps, lbda, nb_inner, W, step, last=(it == nb_iter), **gkw) if fused
+             else ops.z_step(Y, taps, lbda, nb_inner, W, **gkw))
         if fused:
             ops.normal_eq_msg(W, Y, K, msg)      # cumulative sum and ||w||_1 inside the one pass
         else:
@@ -204,7 +216,7 @@ def _check_bd_shared_args(theta_0, bounds):
 
 
 def bd_shared(Y, t_r, lbda=1.0, theta_0=None, hrf_dur=20.0, bounds=None, nb_iter=20,
-              nb_inner=100, comm=None, verbose=0, theta_solver="device", ops=None):
+              nb_inner=100, comm=None, verbose=0, theta_solver="device", ops=None, guard=None):
     """Semi-blind deconvolution with ONE HRF dilation shared by all voxels of
     all ranks (BASELINE config 4).  ``Y`` is this rank's shard, float32 CUDA
     ``(V_local, N)`` (may be empty).  Structure of ``bd``
@@ -217,8 +229,14 @@ def bd_shared(Y, t_r, lbda=1.0, theta_0=None, hrf_dur=20.0, bounds=None, nb_iter
     (cost evaluations per theta-step: passes over the data for "lbfgsb", 1 for
     "device").  With ``theta_solver="device"`` nothing is copied to the host before
     the loop ends (:class:`BdSharedGraph` submits that loop as ONE HIP graph).
+    ``guard`` (opt-in, ``theta_solver="device"`` only; ``None``: the environment variable
+    ``PYBOLD_AMD_PP_GUARD``, ``"1"`` is on): every z-step through the conditioning guard of
+    :func:`pybold_amd.solver.fista_solve_pp`; ``d['guard'] = {'float64': n, 'vector': n}`` are
+    the counts of the last z-step of this rank, read after the loop.
     """
     if theta_solver == "lbfgsb":
+        if guard:                                # (the environment variable alone does not reach this solver)
+            raise ValueError("bd_shared: the conditioning guard goes with theta_solver='device'")
         return _bd_shared_lbfgsb(Y, t_r, lbda, theta_0, hrf_dur, bounds, nb_iter, nb_inner, comm,
                                  verbose)
     if theta_solver != "device":
@@ -226,10 +244,14 @@ def bd_shared(Y, t_r, lbda=1.0, theta_0=None, hrf_dur=20.0, bounds=None, nb_iter
     comm = comm or Comm()
     ops = ops or HipOps(t_r, hrf_dur, Y.shape[1])
     theta0, bounds = _check_bd_shared_args(theta_0, bounds)
-    W, taps, thetas, costs = _bd_shared_device_loop(Y, t_r, lbda, theta0, hrf_dur, bounds, nb_iter, nb_inner, comm, ops)
+    from . import solver
+    guard = solver.pp_guard_opt_in(guard)
+    W, taps, thetas, costs = _bd_shared_device_loop(Y, t_r, lbda, theta0, hrf_dur, bounds, nb_iter, nb_inner, comm, ops, guard)
     d = {"theta": torch.cat(thetas).cpu().numpy(),
          "J": np.concatenate([[1.0], torch.cat(costs).cpu().numpy()]),
          "evals": [1] * nb_iter}
+    if guard and getattr(ops, "guard_work", None) is not None:
+        d["guard"] = solver.guard_counts(ops.guard_work)
     if verbose > 0 and comm.rank == 0:
         for it in range(nb_iter + 1):
             print("bd_shared outer %d: theta=%.6f J=%.6f" % (it, d["theta"][min(it + 1, nb_iter)], d["J"][it + 1]))
@@ -243,11 +265,17 @@ class BdSharedGraph:
     :meth:`launch`.  At small shards the loop is bound by its ~130 dependent launches (21 x 3 ... 6), not by the kernels:
     6 250 voxels 6.6 ms eager.  ``Y`` may be refilled in place between launches (same shape).
 
+    ``guard``: as for :func:`bd_shared`; the loop is captured with the guard on (a guarded z-step synchronises with the host
+    no more than a plain one).
+
     Falls back to the eager loop (``self.graph is None``, reason in ``self.fallback``) when capture is not possible:
     a communicator that cannot be captured (gloo), or a capture error."""
 
-    def __init__(self, Y, t_r, lbda=1.0, theta_0=None, hrf_dur=20.0, bounds=None, nb_iter=20, nb_inner=100, comm=None):
+    def __init__(self, Y, t_r, lbda=1.0, theta_0=None, hrf_dur=20.0, bounds=None, nb_iter=20, nb_inner=100, comm=None,
+                 guard=None):
+        from . import solver
         self.comm = comm or Comm()
+        self.guard = solver.pp_guard_opt_in(guard)   # (read once: the captured loop keeps the decision)
         self.Y, self.t_r, self.lbda, self.hrf_dur = Y, t_r, lbda, hrf_dur
         self.nb_iter, self.nb_inner = nb_iter, nb_inner
         self.theta0, self.bounds = _check_bd_shared_args(theta_0, bounds)
@@ -281,7 +309,7 @@ class BdSharedGraph:
 
     def _loop(self):
         return _bd_shared_device_loop(self.Y, self.t_r, self.lbda, self.theta0, self.hrf_dur, self.bounds, self.nb_iter,
-                                      self.nb_inner, self.comm, self.ops)
+                                      self.nb_inner, self.comm, self.ops, self.guard)
 
     def _eager(self):
         self.out = self._loop()
@@ -301,6 +329,9 @@ class BdSharedGraph:
             W = W.clone()
         d = {"theta": torch.cat(thetas).cpu().numpy(), "J": np.concatenate([[1.0], torch.cat(costs).cpu().numpy()]),
              "evals": [1] * self.nb_iter}
+        if self.guard and self.ops.guard_work is not None:
+            from . import solver
+            d["guard"] = solver.guard_counts(self.ops.guard_work)
         return W, taps.cpu().numpy(), d
 
 

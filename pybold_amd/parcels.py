@@ -33,9 +33,10 @@ def sort_by_label(labels):
     return distinct, order, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
 
 
-def _parcel_loop(Y, po, t_r, lbda, theta, hrf_dur, bounds, nb_iter, nb_inner, force):
+def _parcel_loop(Y, po, t_r, lbda, theta, hrf_dur, bounds, nb_iter, nb_inner, force, guard_work=None):
     """The outer loop on rows sorted by parcel; device tensors only, nothing returns to the host:
-    ``(W, taps (G, K), thetas [nb_iter + 1 tensors (G,)], costs [nb_iter + 1 tensors (G,)])``."""
+    ``(W, taps (G, K), thetas [nb_iter + 1 tensors (G,)], costs [nb_iter + 1 tensors (G,)])``.  ``guard_work``: the buffer
+    of the conditioning guard -- given, every z-step goes through it (:func:`pybold_amd.solver.fista_solve_grouped`)."""
     V, n = Y.shape
     dev = Y.device
     base = force if isinstance(force, int) else solver._FORCE[force]
@@ -55,7 +56,8 @@ def _parcel_loop(Y, po, t_r, lbda, theta, hrf_dur, bounds, nb_iter, nb_inner, fo
         step = 1.0 / solver.gram_frobenius_batch(taps, n)               # (G,): pybold/bold_signal.py:249-254 per parcel
         # an intermediate z-step keeps sparse iterates on the matrix pipe (HipOps.z_step(last=False)); the last one keeps the guard
         W, _ = solver.fista_solve_grouped(Y, taps, step, po, lbda, nb_inner, W0=W, inplace=True,
-                                          force=base if last else base | _lib.PB_FLAG_NO_RHO_GUARD, work=work_z)
+                                          force=base if last else base | _lib.PB_FLAG_NO_RHO_GUARD, work=work_z,
+                                          guard_work=guard_work, guard=guard_work is not None)
         solver.hrf_normal_eq_w_grouped(W, Y, K, po, work=work_ne, out=msg)
         ne, l1, yy = msg[:, :ne_len], msg[:, ne_len], msg[:, ne_len - 1]
         if not last:
@@ -69,7 +71,7 @@ def _parcel_loop(Y, po, t_r, lbda, theta, hrf_dur, bounds, nb_iter, nb_inner, fo
 
 
 def bd_parcels(Y, labels, t_r, lbda=1.0, theta_0=None, hrf_dur=20.0, bounds=None, nb_iter=20, nb_inner=100, force=None,
-               verbose=0):
+               verbose=0, guard=None):
     """``bd`` with one HRF dilation per parcel.  ``Y``: ``(V, N)``, NumPy or a float32 CUDA tensor; ``labels``: ``(V,)``
     integers, any values in any order -- the voxels with the same label share one dilation.  ``lbda``: a scalar.
     ``theta_0``: a scalar, or one start value per parcel in the order of the sorted distinct labels.  Structure, step
@@ -85,7 +87,10 @@ def bd_parcels(Y, labels, t_r, lbda=1.0, theta_0=None, hrf_dur=20.0, bounds=None
     48 taps do so only by opt-in -- ``force="gsplit"`` or ``PYBOLD_AMD_PARCELS_SPLIT=1`` in the environment, which adds
     ``PB_FLAG_GROUPED_SPLIT`` to whatever ``force`` says (:func:`pybold_amd.solver.fista_solve_grouped`) -- and on the
     per-problem vector forms otherwise.  Rows are sorted by label
-    once; with ``verbose=0`` nothing returns to the host before the loop ends."""
+    once; with ``verbose=0`` nothing returns to the host before the loop ends.  ``guard`` (opt-in; ``None``: the environment
+    variable ``PYBOLD_AMD_PP_GUARD``, ``"1"`` is on, read when the loop starts): every z-step through the conditioning guard
+    (:func:`pybold_amd.solver.fista_solve_grouped`); ``d['guard'] = {'float64': n, 'vector': n}`` are the counts of the
+    last z-step, read after the loop."""
     if not torch.is_tensor(Y):
         Y = torch.from_numpy(np.ascontiguousarray(np.asarray(Y), dtype=np.float32)).to(solver.device())
     if Y.dim() != 2 or Y.dtype != torch.float32 or not Y.is_cuda:
@@ -114,13 +119,17 @@ def bd_parcels(Y, labels, t_r, lbda=1.0, theta_0=None, hrf_dur=20.0, bounds=None
     po = solver.ParcelOffsets(offsets, dev)
     Ys = Y.index_select(0, order_dev).contiguous()
     theta = torch.from_numpy(th0).to(dev)
-    Ws, taps, thetas, costs = _parcel_loop(Ys, po, t_r, float(lbda), theta, hrf_dur, bounds, int(nb_iter), int(nb_inner), force)
+    guard_work = solver.guard_work_buffer(V, n, dev) if solver.pp_guard_opt_in(guard) else None
+    Ws, taps, thetas, costs = _parcel_loop(Ys, po, t_r, float(lbda), theta, hrf_dur, bounds, int(nb_iter), int(nb_inner), force,
+                                           guard_work)
     row_parcel = torch.repeat_interleave(torch.arange(G, device=dev), torch.from_numpy(po.sizes).to(dev))
     Xs, Zs = solver.fista_outputs_pp(Ws, taps.index_select(0, row_parcel))
     X, Z, W = (torch.empty_like(Ws).index_copy_(0, order_dev, T) for T in (Xs, Zs, Ws))
     d = {"labels": distinct, "sizes": po.sizes.copy(),
          "theta": torch.stack(thetas).cpu().numpy(),
          "J": np.concatenate([np.ones((1, G)), torch.stack(costs).cpu().numpy()])}
+    if guard_work is not None:
+        d["guard"] = solver.guard_counts(guard_work)
     if verbose > 0:
         for it in range(nb_iter + 1):
             th = d["theta"][min(it + 1, nb_iter)]

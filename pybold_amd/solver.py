@@ -6,6 +6,7 @@ HIP kernels of ``libpybold_hip.so``.  Rows are problems ("voxels"), the last
 dimension is time.
 """
 import collections
+import os
 
 import numpy as np
 import torch
@@ -800,12 +801,17 @@ def hrf_cost(Z, Y, taps):
 
 # ---- per-voxel HRFs (batched blind deconvolution) ---------------------------
 def fista_solve_pp(Y, taps, steps, lbda, n_iter, W0=None, stop=None, tol=0.0, force=None,
-                   inplace=False):
+                   inplace=False, guard_work=None, guard=False):
     """:func:`fista_solve` with one HRF and one step per problem: ``taps`` float64
     CUDA ``(V, K)``, ``steps`` float64 CUDA ``(V,)`` -- or ONE HRF ``(K,)`` and ONE
     step ``(1,)`` living in device memory and shared by every problem (the shared-HRF
     blind step: taps come straight from :func:`theta_fit`).  ``inplace=True`` iterates
-    in ``W0`` itself instead of a copy.  Returns ``(W, n_done)``."""
+    in ``W0`` itself instead of a copy.  ``guard=True`` (opt-in): the conditioning guard
+    of ``pb_fista_solve_pp_guarded`` -- rows the operator barely sees are solved again in
+    float64 (or, off the matrix pipe, on a float32 vector form), every other row keeps
+    the bits of the plain call; ``guard_work``: an int32 CUDA buffer of
+    :func:`guard_work_len` words to reuse, read afterwards by :func:`guard_counts`.
+    Returns ``(W, n_done)``."""
     lib = _lib.load()
     Y = _rows(Y, torch.float32, "Y")
     dev = Y.device
@@ -826,6 +832,17 @@ def fista_solve_pp(Y, taps, steps, lbda, n_iter, W0=None, stop=None, tol=0.0, fo
     lbda_scalar, lbda_dev = _lbda_arg(lbda, dev)
     betas = _betas_on(dev, n_iter)
     n_done = torch.empty((V,), dtype=torch.int32, device=dev)
+    if guard:
+        guard_work = _guard_work(guard_work, V, N, cold, dev)
+        with torch.cuda.device(dev):
+            rc = lib.pb_fista_solve_pp_guarded(
+                Y.data_ptr(), _ld(Y), W.data_ptr(), _ld(W), V, N, taps.data_ptr(),
+                0 if shared else _ld(taps), taps.shape[1], steps.data_ptr(), lbda_scalar,
+                lbda_dev.data_ptr() if lbda_dev is not None else None, betas.data_ptr(), int(n_iter),
+                _STOP[stop], float(tol), n_done.data_ptr(), guard_work.data_ptr(), guard_work.numel(),
+                _FORCE[force] | cold, _stream_ptr(dev))
+        _lib.check(rc, "pb_fista_solve_pp_guarded")
+        return W, n_done
     with torch.cuda.device(dev):
         rc = lib.pb_fista_solve_pp(
             Y.data_ptr(), _ld(Y), W.data_ptr(), _ld(W), V, N, taps.data_ptr(),
@@ -834,6 +851,89 @@ def fista_solve_pp(Y, taps, steps, lbda, n_iter, W0=None, stop=None, tol=0.0, fo
             _STOP[stop], float(tol), n_done.data_ptr(), _FORCE[force] | cold, _stream_ptr(dev))
     _lib.check(rc, "pb_fista_solve_pp")
     return W, n_done
+
+
+# ---- the conditioning guard of the solves whose HRF lives in device memory (opt-in; csrc/guard.h) ---------------------
+def guard_work_len(n_rows, n_scans, cold=False):
+    """int32 words of the work buffer of a guarded solve (``pb_fista_guard_work_len``); smaller for a cold start."""
+    return int(_lib.load().pb_fista_guard_work_len(int(n_rows), int(n_scans), PB_FLAG_COLD_START if cold else 0))
+
+
+def pp_guard_opt_in(guard=None):
+    """The switch of the blind-deconvolution loops (``bd`` on a 2-D batch, ``bd_shared``, ``bd_parcels``): ``guard`` as
+    given, ``None``: the environment variable ``PYBOLD_AMD_PP_GUARD`` (``"1"`` is on; the convention of
+    ``PYBOLD_AMD_PARCELS_SPLIT``).  Read when a loop starts."""
+    if guard is None:
+        return os.environ.get("PYBOLD_AMD_PP_GUARD", "0") == "1"
+    return bool(guard)
+
+
+def guard_work_buffer(n_rows, n_scans, dev, cold=False):
+    """A zeroed work buffer for guarded solves of this shape on ``dev`` (zeroed: :func:`guard_counts` reads 0 from it
+    before the first call and after calls on an empty batch, which launch nothing)."""
+    return torch.zeros((max(guard_work_len(n_rows, n_scans, cold), 8),), dtype=torch.int32, device=dev)
+
+
+def _guard_work(work, V, N, cold, dev):
+    need = guard_work_len(V, N, cold != 0)
+    if work is None or work.dtype != torch.int32 or work.numel() < need or work.device != dev:
+        work = torch.zeros((max(need, 8),), dtype=torch.int32, device=dev)      # (an empty batch launches nothing: counts 0)
+    return work
+
+
+def guard_counts(guard_work):
+    """``{'float64': n, 'vector': n}``: the rows the last guarded solve that used this work buffer solved again in
+    float64 / on the float32 vector form.  Reads two words from the device (synchronises)."""
+    head = guard_work[:4].cpu()
+    return {"float64": int(head[1]), "vector": int(head[3])}
+
+
+def guard_supported(n_scans, n_taps, stop=None):
+    """The float64 kernel a guarded solve of this shape re-solves ill-conditioned rows on (``pb_fista_guard_supported``):
+    1 one wave per row, 2 four waves, 3 / 4 the same for HRFs of 33 .. 48 taps, 5 the LDS kernel; 0: no guard for the
+    shape (more than 64 taps or 1 344 scans) -- a guarded call then runs the plain solve and marks nothing."""
+    return int(_lib.load().pb_fista_guard_supported(int(n_scans), int(n_taps), _STOP[stop]))
+
+
+def pp_uses_matrix_pipe(n_scans, n_taps, n_rows, shared=True, stop=None, force=None):
+    """Whether :func:`fista_solve_pp` puts rows of such a call on a matrix-pipe form (``pb_fista_pp_has_matrix_pipe``,
+    host-only): the calls whose guard also lists the rows to keep off the matrix pipe."""
+    return bool(_lib.load().pb_fista_pp_has_matrix_pipe(int(n_scans), int(n_taps), int(n_rows), 1 if shared else 0, _STOP[stop],
+                                                        force if isinstance(force, int) else _FORCE[force]))
+
+
+def conditioning_marks(Y, taps, offsets=None):
+    """What the conditioning guard would do with every row of ``Y`` (float32 CUDA ``(V, N)``): int32 ``(V,)`` -- 2 the
+    row is solved in float64 (``gamma_2 < 1e-2``), 1 it is kept off the matrix pipe (``gamma_2`` below 7e-2 / 3e-2 / 2e-2
+    by shape), 0 it keeps the plain call's answer.  ``gamma_2 = lambda_max / (||y||_2 sum|c| / sqrt(N))``, ``c =
+    cumsum(h)``, for the row's own HRF: ``taps`` float64 CUDA ``(K,)`` (one for all rows), ``(V, K)`` (one per row) or,
+    with ``offsets`` (``G + 1`` integers or a :class:`ParcelOffsets`), ``(G, K)`` (one per parcel).  Up to 64 taps and
+    1 344 scans (``pb_conditioning_marks``)."""
+    lib = _lib.load()
+    Y = _rows(Y, torch.float32, "Y")
+    dev = Y.device
+    V, N = Y.shape
+    if taps.dtype != torch.float64 or not taps.is_cuda:
+        raise TypeError("taps must be a float64 CUDA tensor")
+    po = None
+    if taps.dim() == 1:
+        if offsets is not None:
+            raise ValueError("offsets go with one HRF per parcel, taps (G, K)")
+        taps, ldt = taps.contiguous().reshape(1, -1), 0
+    else:
+        taps = _rows(taps, torch.float64, "taps")
+        ldt = _ld(taps)
+        if offsets is not None:
+            po = _parcel_offsets(offsets, dev, V)
+        if taps.shape[0] != (po.G if po is not None else V):
+            raise ValueError("taps must have one row per %s" % ("parcel" if po is not None else "row of Y"))
+    marks = torch.empty((V,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.pb_conditioning_marks(Y.data_ptr(), _ld(Y) if V else N, V, N, taps.data_ptr(), ldt, taps.shape[1],
+                                       po.dev.data_ptr() if po is not None else None, po.G if po is not None else 0,
+                                       marks.data_ptr(), _stream_ptr(dev))
+    _lib.check(rc, "pb_conditioning_marks")
+    return marks
 
 
 def fista_solve_pp_d(Y, taps, steps, lbda, n_iter, W0=None, want_J=False, stop=None, tol=0.0, wind=6, force=None):
@@ -1337,7 +1437,8 @@ def grouped_route(offsets, n_scans, n_taps, force=None):
     return int(code), mu.value, rc.value
 
 
-def fista_solve_grouped(Y, taps, steps, offsets, lbda, n_iter, W0=None, force=None, inplace=False, work=None):
+def fista_solve_grouped(Y, taps, steps, offsets, lbda, n_iter, W0=None, force=None, inplace=False, work=None, guard_work=None,
+                        guard=False):
     """:func:`fista_solve_pp` with one HRF and one step per PARCEL: the rows of ``Y`` (float32 CUDA ``(V, N)``) are
     contiguous by parcel, ``offsets`` (``G + 1`` integers or a :class:`ParcelOffsets`) their ranges, ``taps`` float64
     CUDA ``(G, K)``, ``steps`` float64 CUDA ``(G,)``.  129 .. 310 scans with up to 33 taps run on the matrix pipe, a
@@ -1348,7 +1449,9 @@ def fista_solve_grouped(Y, taps, steps, offsets, lbda, n_iter, W0=None, force=No
     passes and large remainders there, the rest behind them on the vector forms (:func:`grouped_route` tells) --,
     ``"gsplit_mfma"`` / ``"gsplit_mfmaonly"``: every unit there, whatever the number of rows.  Without the opt-in those
     lengths run on the vector route.  ``force`` may also be raw ``PB_FLAG_*`` bits.  No stop rule.  ``work``: an int32 CUDA buffer of
-    ``pb_fista_grouped_work_len(V, G, K)`` words to reuse.  Returns ``(W, n_done)``."""
+    ``pb_fista_grouped_work_len(V, G, K)`` words to reuse.  ``guard=True`` (opt-in): the conditioning guard of
+    :func:`fista_solve_pp` around this call (``pb_fista_solve_grouped_guarded``), ``guard_work`` its buffer.  Returns
+    ``(W, n_done)``."""
     lib = _lib.load()
     Y = _rows(Y, torch.float32, "Y")
     dev = Y.device
@@ -1368,6 +1471,17 @@ def fista_solve_grouped(Y, taps, steps, offsets, lbda, n_iter, W0=None, force=No
     need = int(lib.pb_fista_grouped_work_len(V, G, K))
     if work is None or work.dtype != torch.int32 or work.numel() < need or work.device != dev:
         work = torch.empty((max(need, 2),), dtype=torch.int32, device=dev)
+    if guard:
+        guard_work = _guard_work(guard_work, V, N, cold, dev)
+        with torch.cuda.device(dev):
+            rc = lib.pb_fista_solve_grouped_guarded(
+                Y.data_ptr(), _ld(Y) if V else N, W.data_ptr(), _ld(W) if V else N, V, N, taps.data_ptr(), _ld(taps) if G else K, K,
+                steps.data_ptr(), G, po.host.ctypes.data, po.dev.data_ptr(), lbda_scalar,
+                lbda_dev.data_ptr() if lbda_dev is not None else None, betas.data_ptr(), int(n_iter), n_done.data_ptr(),
+                work.data_ptr(), work.numel(), guard_work.data_ptr(), guard_work.numel(),
+                (force if isinstance(force, int) else _FORCE[force]) | cold, _stream_ptr(dev))
+        _lib.check(rc, "pb_fista_solve_grouped_guarded")
+        return W, n_done
     with torch.cuda.device(dev):
         rc = lib.pb_fista_solve_grouped(
             Y.data_ptr(), _ld(Y) if V else N, W.data_ptr(), _ld(W) if V else N, V, N, taps.data_ptr(), _ld(taps) if G else K, K,
